@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Hot-path benchmark: frames/s of the HIP software rasterizer on BASELINE.json's configs.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c1] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 One step = one frame of Trident's graphics-pipeline stage: the per-frame UBO + draw-list update
@@ -11,6 +11,12 @@ row bands (geometry replicated) + an RCCL all-gather of the BGRA8 bands into the
 every rank, double-buffered so frame k's gather overlaps frame k+1's kernels. value = whole frames
 per second (strong scaling: a frame's work is fixed, N GPUs share it); latency_ms = one frame end
 to end without overlap. Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step and what they rest on).
+--full adds everything else the line can hold, each measured in a pass of its own after the timed steps: the
+per-kernel event pass with the rooflines, latency_ms, the secondary configs and the Forge editor frames, the measured
+copy bandwidth, the CPU baseline, and at N > 1 the render-only / assembly-only timings. --dump-outputs DIR writes the
+last timed frame (dump_outputs).
 """
 import argparse
 import json
@@ -669,6 +675,19 @@ class BandRenderer:
             return self.xbufs[self._kx]
         return self.ring.frame
 
+    def last_outputs(self):
+        """What the most recent step() left for its caller (after a device synchronisation), as host arrays: the
+        colour this rank holds (uint8[rows, W, 4], B8G8R8A8; on the display rank of N > 1 the assembled frame) and
+        this rank's depth band (float32[rows, W]; None for a rank that renders nothing)."""
+        import numpy as np
+
+        W = self.scene.width
+        col = self.assembled_frame().cpu().numpy().view(np.uint8).reshape(-1, W, 4)
+        dep = None
+        if self.rows and self.frames:
+            dep = self.depth[(self.frames - 1) % self.inflight].cpu().numpy().reshape(-1, W)
+        return col, dep
+
     def probe_band(self):
         """One frame of this rank's band on context 0, into a scratch buffer (synchronised; no collective). An
         assemble-only display rank probes the first sender's band instead (a scratch context)."""
@@ -1088,20 +1107,26 @@ def guarded_call(what, fn, device, dist_on, rank=0, bad=lambda out: 0.0):
     return False, f"{what}: failed on another rank ({worst:g})"
 
 
-def timed_run(br, steps, warmup, dist_on, stage_timing=True, event_frames=256, warm_seconds=0.25):
+# timed_run's clock-settling batches: at most this many frames each and this much wall time in all, whatever --steps is
+SETTLE_BATCH, SETTLE_SECONDS = 2000, 4.0
+
+
+def timed_run(br, steps, warmup, dist_on, stage_timing=True, event_frames=256, warm_seconds=0.25, capture=None):
     """Time exactly `steps` frames (no per-kernel events inside the timed region), then, outside it,
     a separate pass of `event_frames` frames with HIP events around every kernel of every frame:
     the per-kernel durations (roofline.kernel_ms) rest on that many samples, not on the few frames a
     short timed run would leave.
 
     Warm-up: `warmup` frames, back-to-back frames for at least `warm_seconds` of wall time, then batches
-    of `steps` frames until two consecutive batches agree within 2 % (at most 8). The
+    of `steps` frames (at most SETTLE_BATCH each) until two consecutive batches agree within 2 % (at most 8, and
+    at most SETTLE_SECONDS of them, so that a long timed region does not multiply the time spent before it). The
     GPU leaves its idle clock state only after several ms of continuous work: after the scene upload
     (seconds of host work) 5 warm-up frames (0.6 ms) left the first timed frames at low clocks, and a
     20-frame run measured 0.134-0.140 ms/frame against 0.113-0.118 for the same frames after 50 ms of
     work (tools/step_timing.py, profiles/round3/step_timing.log). Nothing is removed from the timed
-    region; it only starts at the clock every later frame runs at. Returns (seconds, timing, frames
-    the warm-up ran)."""
+    region; it only starts at the clock every later frame runs at. capture(br), if given, runs right
+    after the timed region, while the buffers still hold the last timed frame. Returns (seconds, timing,
+    frames the warm-up ran)."""
     import torch
 
     br.warm()  # first frame per context sizes the internal queues (re-renders after TRI_E_OVERFLOW)
@@ -1119,7 +1144,7 @@ def timed_run(br, steps, warmup, dist_on, stage_timing=True, event_frames=256, w
         br.step()
     # then batches of `steps` frames until two consecutive batches agree within 2 % (at most 8 batches):
     # the clock has settled at the rate the timed frames will run at
-    batch, prev = max(steps, 20), None
+    batch, prev, spent = min(max(steps, 20), SETTLE_BATCH), None, 0.0
     for _ in range(8):
         br.drain()
         br._sync()
@@ -1130,7 +1155,8 @@ def timed_run(br, steps, warmup, dist_on, stage_timing=True, event_frames=256, w
         br._sync()
         cur = max_over_ranks(time.perf_counter() - tb, br.dev, dist_on)
         extra += batch
-        if prev is not None and abs(cur - prev) <= 0.02 * prev:
+        spent += cur  # (the max over ranks: every rank leaves the loop at the same batch)
+        if (prev is not None and abs(cur - prev) <= 0.02 * prev) or spent >= SETTLE_SECONDS:
             break
         prev = cur
     n_warm = max(warmup, 1) + extra
@@ -1150,6 +1176,8 @@ def timed_run(br, steps, warmup, dist_on, stage_timing=True, event_frames=256, w
         dist.barrier()
     dt = time.perf_counter() - t0
     br.synchronize()  # surfaces TRI_E_OVERFLOW if any timed frame overflowed
+    if capture is not None:
+        capture(br)
     timing = None
     if stage_timing:  # per-kernel durations: context 0 alone, frames back to back without overlap
         br.r.set_timing(True, 1)
@@ -1159,6 +1187,28 @@ def timed_run(br, steps, warmup, dist_on, stage_timing=True, event_frames=256, w
         timing = br.r.timing()
         br.r.set_timing(False)
     return max_over_ranks(dt, br.dev, dist_on), timing, n_warm
+
+
+DUMP_PIXELS, DUMP_SEED = 2_000_000, 0  # --dump-outputs: 2M pixels are 32 MB of colour and 8 MB of depth in float32
+
+
+def dump_outputs(dirname, color, depth):
+    """--dump-outputs: the last timed frame as dirname/color.npy (float32[n, 4]: each pixel's B, G, R, A bytes as
+    0..255) and dirname/depth.npy (float32[n]; absent when depth is None). n is every pixel of the frame in row-major
+    order, or, for a frame of more than DUMP_PIXELS pixels, the same DUMP_SEED-seeded sample of DUMP_PIXELS of them
+    (ascending pixel index) in every run, so that two builds' files compare element for element."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    n = color.shape[0] * color.shape[1]
+    pick = None
+    if n > DUMP_PIXELS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_PIXELS, replace=False))
+    flat = color.reshape(n, 4)
+    np.save(os.path.join(dirname, "color.npy"), (flat if pick is None else flat[pick]).astype(np.float32))
+    if depth is not None:
+        d = depth.reshape(-1)
+        np.save(os.path.join(dirname, "depth.npy"), (d if pick is None else d[pick]).astype(np.float32))
 
 
 # Trident-Forge's editor frame (SURVEY 8(f) row 2): the Scene and Game viewport panels of the reference's own
@@ -1396,8 +1446,16 @@ def main():
     ap.add_argument("--warm-seconds", type=float, default=0.25,
                     help="untimed back-to-back frames before the timed region (at least --warmup frames): the "
                          "GPU's clock ramp out of idle takes a few ms")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: the per-kernel event pass and the rooflines, the frame latency, "
+                         "the other configs and the Forge editor frames (secondary), the measured copy bandwidth, "
+                         "the CPU baseline and, at N > 1 or with --sim-world, the render / assembly / codec timings. "
+                         "Without it the run sets up, warms up, times --steps frames and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame as DIR/color.npy and DIR/depth.npy "
+                         "(float32; a fixed seeded sample of the pixels of a frame above 2M pixels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary configs or Forge frames")
     ap.add_argument("--sim-world", type=int, default=0,
                     help="diagnostics (1 GPU, no collective): render only band --sim-rank of an N-way split")
     ap.add_argument("--sim-rank", type=int, default=0)
@@ -1430,8 +1488,10 @@ def main():
                     help="N > 1: host-side deadline per phase (exit non-zero with every thread's stack instead of "
                          "hanging the job); 0 disables")
     ap.add_argument("--no-stage-timing", action="store_true",
-                    help="diagnostics: no per-kernel HIP events in the timed loop (roofline fields become null)")
+                    help="diagnostics, with --full: no per-kernel HIP event pass (roofline fields become null)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1548,16 +1608,25 @@ def main():
         if native_checked:
             parity["native_check_before_autotune"] = native_checked[0]
     arm_watchdog(args.watchdog_seconds if world > 1 else 0, "timed run")
-    dt, timing, n_warm = timed_run(br, args.steps, args.warmup, dist_on, not args.no_stage_timing,
-                                   warm_seconds=args.warm_seconds)
+    dumped = []
+
+    def capture(b):  # the last timed frame, before any later pass reuses its buffers
+        if rank == 0:
+            col, dep = b.last_outputs()
+            dump_outputs(args.dump_outputs, col, dep if world == 1 else None)
+            dumped.append(args.dump_outputs)
+
+    dt, timing, n_warm = timed_run(br, args.steps, args.warmup, dist_on, args.full and not args.no_stage_timing,
+                                   warm_seconds=args.warm_seconds, capture=capture if args.dump_outputs else None)
     fps = args.steps / dt
     W, H = scene.width, scene.height
     stats = br.r.frame_stats()
-    latency = br.latency_ms()  # one frame end to end (render + gather), no overlap
+    latency = br.latency_ms() if args.full else None  # one frame end to end (render + gather), no overlap
     stage, samples, rrows = rendering_rank_stage(br, timing, dist_on)  # rrows: the band those kernels rendered
     assembly = None
-    if world > 1:  # what sets the rate: the slowest rank's render alone vs the assembly alone (outside the timed region)
+    if world > 1:
         br.check()  # every packed band kept its alpha and fitted its slots (lossless)
+    if world > 1 and args.full:  # what sets the rate: the slowest rank's render alone vs the assembly alone (outside the timed region)
         render_ms = max_over_ranks(br.render_only_ms(), br.dev, dist_on)
         asm_ms = max_over_ranks(br.assembly_only_ms(), br.dev, dist_on)
         inbound = br.inbound_bytes() if rank == 0 else 0
@@ -1574,7 +1643,7 @@ def main():
                     "bound": "assembly" if asm_ms > render_ms else "render",
                     "display_renders": br.bands[0][1] > br.bands[0][0],
                     "note": "max over ranks; render and assembly each timed alone, back to back, outside the timed region"}
-    elif args.sim_world > 1:  # one band of an N-way split on one GPU: the codec's cost per band
+    elif args.sim_world > 1 and args.full:  # one band of an N-way split on one GPU: the codec's cost per band
         assembly = {"sim_world": args.sim_world, "sim_rank": args.sim_rank, "frame_alpha": br.alpha,
                     "sim_codec": args.sim_codec,
                     "codec": br.codec_ms([y1 - y0 for y0, y1 in br.bands])}
@@ -1587,11 +1656,11 @@ def main():
     raster_bytes = 8.0 * W * rrows
     achieved = raster_bytes / (raster_ms * 1e-3) / 1e9 if raster_ms > 0 else None
     frame_bytes = scene.algorithmic_bytes(rows=rrows)
-    pmc = pmc_kernel(scene.name, "k_raster")
+    pmc = pmc_kernel(scene.name, "k_raster") if args.full else None
     traffic = None if pmc is None or "hbm_bytes_per_launch" not in pmc else pmc["hbm_bytes_per_launch"] * rrows / H
 
     secondary = {}
-    if not args.no_secondary and args.config == "c3":
+    if args.full and not args.no_secondary and args.config == "c3":
         # the other BASELINE.json GPU configs, same timing protocol, and C3's grid under a non-identity model matrix
         # (how every Forge entity arrives: Renderer.cpp:417-427), so the headline's identity-draw path has its
         # general-path cost beside it
@@ -1621,7 +1690,7 @@ def main():
             secondary[s2.name] = entry
             br2.close()
             del br2
-    if not args.no_secondary and args.config == "c3" and world == 1:
+    if args.full and not args.no_secondary and args.config == "c3" and world == 1:
         # Forge's editor frame through the engine API: two panels + the present blit, and one 4K
         # viewport, beside the C-ABI line
         secondary["forge_editor_frame_c3_panels"] = forge_frame(FORGE_PANELS)
@@ -1631,9 +1700,9 @@ def main():
         secondary["forge_editor_frame_c3_4k_3inflight"] = forge_frame(FORGE_4K, frames_in_flight=3)
 
     arm_watchdog(0, "")
-    copy_gbs = device_copy_gbs(br.dev) if rank == 0 else None
+    copy_gbs = device_copy_gbs(br.dev) if rank == 0 and args.full else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(scene, args.cpu_seconds)
 
     if rank == 0:
@@ -1662,7 +1731,7 @@ def main():
             "latency_ms": latency,
             # the pipeline's fill and drain: one frame's latency beyond its share of the throughput clock, paid once
             # per timed region (0.05 ms of a 20-step C3 region is ~2.6 %, of a 200-step one ~0.3 %)
-            "fill_drain_ms": latency - dt / args.steps * 1e3,
+            "fill_drain_ms": latency - dt / args.steps * 1e3 if args.full else None,
             # the contract prices k_raster against HBM; what actually binds it is VALU issue together with the
             # L1 gather path (the VALU floor alone caps this frac near 0.17), see roofline_valu
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1689,6 +1758,13 @@ def main():
             "secondary": secondary,
             "cpu_baseline": cpu,
         }
+        line["full"] = args.full
+        if not args.full:  # a plain run measured none of these
+            for key in ("latency_ms", "fill_drain_ms", "roofline", "roofline_valu", "stage_ms", "secondary",
+                        "cpu_baseline"):
+                del line[key]
+        if dumped:
+            line["dumped_outputs"] = dumped[0]
         print(json.dumps(line), flush=True)
     arm_watchdog(args.watchdog_seconds if world > 1 else 0, "teardown")
     br.close()

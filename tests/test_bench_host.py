@@ -38,6 +38,41 @@ def test_effective_cpus_missing(tmp_path):
     assert r["quota"] is None and r["effective"] >= 1
 
 
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs above DUMP_PIXELS: the same seeded pixels in every run (ascending, colour and depth of the same
+    pixels), float32, and within 64 MB at the 2M-pixel sample the bench uses for a 4K frame."""
+    import numpy as np
+
+    assert bench.DUMP_PIXELS * (4 + 1) * 4 <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_PIXELS", 1000)
+    h, w = 37, 53  # 1961 pixels
+    idx = np.arange(h * w, dtype=np.uint32)
+    color = np.stack([idx & 0xFF, (idx >> 8) & 0xFF, (idx * 7) & 0xFF, np.full_like(idx, 255)], -1).astype(np.uint8)
+    color = color.reshape(h, w, 4)
+    depth = (idx / np.float32(h * w)).astype(np.float32).reshape(h, w)
+    bench.dump_outputs(str(tmp_path / "a"), color, depth)
+    bench.dump_outputs(str(tmp_path / "b"), color.copy(), depth.copy())
+    ca, za = np.load(tmp_path / "a" / "color.npy"), np.load(tmp_path / "a" / "depth.npy")
+    assert ca.dtype == za.dtype == np.float32 and ca.shape == (1000, 4) and za.shape == (1000,)
+    assert np.array_equal(ca, np.load(tmp_path / "b" / "color.npy"))
+    assert np.array_equal(za, np.load(tmp_path / "b" / "depth.npy"))
+    pick = np.rint(za * np.float32(h * w)).astype(np.int64)  # depth encodes the pixel index
+    assert np.all(np.diff(pick) > 0) and pick.max() < h * w
+    assert np.array_equal(ca, color.reshape(-1, 4)[pick].astype(np.float32))
+    bench.dump_outputs(str(tmp_path / "c"), color, None)  # a rank without a depth band
+    assert not (tmp_path / "c" / "depth.npy").exists() and (tmp_path / "c" / "color.npy").exists()
+
+
+def test_plain_run_options():
+    """The command line has --full and --dump-outputs DIR; --steps below 1 is refused before anything starts."""
+    import subprocess
+
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs DIR" in out.stdout
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert bad.returncode == 2 and "--steps" in bad.stderr
+
+
 def _gpurun_excluded(rel, patterns):
     """tar-style exclusion as gpurun applies .gpurunignore: a pattern with a leading './' is anchored at the
     tree's top, others match any path component suffix; a match on a directory excludes what is under it."""

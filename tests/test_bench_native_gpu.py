@@ -55,6 +55,38 @@ def test_band_renderer_native_exchange_plumbing():
     assert abi.TRI_XFER_ID_BYTES == 128
 
 
+def test_timed_run_captures_last_timed_frame(tmp_path):
+    """--dump-outputs: timed_run calls capture once, right after the timed steps, and last_outputs then holds a whole
+    finished frame (3 frames in flight, a step count that is no multiple of 3): colour and depth bit for bit the frame
+    one context renders. dump_outputs writes it whole as float32 (a frame under DUMP_PIXELS)."""
+    import numpy as np
+    from trident_raster import raster, scenes
+
+    import bench
+    import scene_cases as sc
+
+    scene = sc.grid_c3(640, 360, 60)
+    with raster.TriRaster(scene.width, scene.height, device=0) as r:
+        scenes.load_scene(r, scene)
+        r.render_frame()
+        want_col, want_dep = r.readback()
+    got = []
+    br = bench.BandRenderer(scene, 0, 1, 0, inflight=3)
+    try:
+        dt, timing, n_warm = bench.timed_run(br, 7, 2, False, stage_timing=False, warm_seconds=0.01,
+                                             capture=lambda b: got.append(b.last_outputs()))
+    finally:
+        br.close()
+    assert dt > 0 and timing is None and n_warm >= 2 and len(got) == 1
+    col, dep = got[0]
+    assert col.dtype == np.uint8 and col.shape == want_col.shape and np.array_equal(col, want_col)
+    assert dep.dtype == np.float32 and np.array_equal(dep.view(np.uint32), want_dep)
+    bench.dump_outputs(str(tmp_path), col, dep)
+    c, z = np.load(tmp_path / "color.npy"), np.load(tmp_path / "depth.npy")
+    assert c.dtype == z.dtype == np.float32 and c.shape == (640 * 360, 4) and z.shape == (640 * 360,)
+    assert np.array_equal(c, want_col.reshape(-1, 4)) and np.array_equal(z.view(np.uint32), want_dep.reshape(-1))
+
+
 def test_forge_editor_frame_secondary():
     """bench.forge_frame (the frame Forge runs, through RenderCommand::DrawFrame with its deferred fence): two small
     panels and the present blit complete and report a rate and a host cost (the shim's pixel parity after the deferred

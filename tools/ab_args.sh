@@ -8,7 +8,7 @@ i=0
 for a in "$@"; do
   i=$((i + 1))
   log=gpurun_out/abargs_$i.log
-  timeout -k 10 200 python bench.py --steps 200 --warmup 10 --no-cpu-baseline $a > $log 2>&1 || { echo "[$a] failed rc=$?"; tail -5 $log; exit 1; }
+  timeout -k 10 200 python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline $a > $log 2>&1 || { echo "[$a] failed rc=$?"; tail -5 $log; exit 1; }
   python3 -c "
 import json; d=json.loads(open('$log').read().strip().splitlines()[-1])
 st=lambda x: {k[3:]:round(v*1e3,1) for k,v in x.items() if v}

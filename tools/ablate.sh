@@ -5,12 +5,13 @@
 #   for a in 1 2; do bash tools/build_variant.sh ablate_$a -DTRI_ABLATE=$a; done
 # then run this on the GPU box.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}; export OUT  # where the logs and result lines go
+mkdir -p $OUT
 for a in 0 1 2; do
   lib=""
   [ "$a" != 0 ] && lib="TRI_RASTER_LIB=3d-renderer_amd/lib/variants/ablate_$a.so"
-  env $lib TRI_NOOP=1 timeout -k 10 200 python bench.py --steps 100 --warmup 10 --no-cpu-baseline ${EXTRA} > gpurun_out/ablate_$a.log 2>&1 || exit $?
+  env $lib TRI_NOOP=1 timeout -k 10 200 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline ${EXTRA} > $OUT/ablate_$a.log 2>&1 || exit $?
   python3 -c "
-import json,sys; d=json.loads(open('gpurun_out/ablate_$a.log').read().strip().splitlines()[-1])
+import json,sys; d=json.loads(open('$OUT/ablate_$a.log').read().strip().splitlines()[-1])
 print('ablate=$a fps=%.0f'%d['value'], {k:round(v*1e3,1) for k,v in d['stage_ms'].items()})"
 done

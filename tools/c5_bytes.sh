@@ -4,15 +4,16 @@
 # Build first: for a in 128 2048; do bash tools/build_variant.sh A$a -DTRI_ABLATE=$a; done
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out/c5b
+OUT=${OUT:-bench_out}; export OUT  # where the logs and result lines go
+mkdir -p $OUT/c5b
 for v in base A128 A2048; do
   if [ $v = base ]; then unset TRI_RASTER_LIB; else export TRI_RASTER_LIB=3d-renderer_amd/lib/variants/$v.so; fi
-  timeout -k 10 240 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum -d gpurun_out/c5b/$v -o $v --output-format csv \
-    -- python3 bench.py --config c5 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --inflight 1 > gpurun_out/c5b/$v.log 2>&1 || exit $?
+  timeout -k 10 240 rocprofv3 --pmc TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum -d $OUT/c5b/$v -o $v --output-format csv \
+    -- python3 bench.py --full --config c5 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --inflight 1 > $OUT/c5b/$v.log 2>&1 || exit $?
   python3 - "$v" <<'PY'
-import csv, glob, sys, collections
+import csv, glob, os, sys, collections
 v = sys.argv[1]
-f = glob.glob(f"gpurun_out/c5b/{v}/**/*counter_collection.csv", recursive=True)[0]
+f = glob.glob(os.environ["OUT"] + f"/c5b/{v}/**/*counter_collection.csv", recursive=True)[0]
 acc = collections.defaultdict(lambda: collections.defaultdict(float))
 for r in csv.DictReader(open(f)):
     if "k_raster" not in r["Kernel_Name"]: continue

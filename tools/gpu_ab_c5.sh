@@ -6,7 +6,7 @@ V=3d-renderer_amd/lib/variants
 ab=""
 for n in "$@"; do ab="$ab TRI_RASTER_LIB=$V/$n.so"; done
 bash tools/ab.sh $ab "" $ab "" || exit 1
-A="--config c5 --steps 50 --warmup 5 --no-cpu-baseline --no-secondary --inflight 1"
+A="--full --config c5 --steps 50 --warmup 5 --no-cpu-baseline --no-secondary --inflight 1"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d gpurun_out/kt_c5 -o kt --output-format csv -- python3 bench.py $A > gpurun_out/kt_c5.log 2>&1 || { echo trace failed; exit 1; }
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_c5_write -o pmc_write --output-format csv -- python3 bench.py $A > gpurun_out/pmc_c5_write.log 2>&1 || { echo write pass failed; exit 1; }
 timeout -k 10 200 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum -d gpurun_out/pmc_c5_sized -o pmc_sized --output-format csv -- python3 bench.py $A > gpurun_out/pmc_c5_sized.log 2>&1 || { echo sized pass failed; exit 1; }

@@ -10,7 +10,7 @@ for setting in "$@"; do
   i=$((i + 1))
   for v in ${setting}; do export "$v"; done
   timeout -k 10 200 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVES SQ_BUSY_CYCLES \
-    -d $OUT/run$i -o run$i --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary \
+    -d $OUT/run$i -o run$i --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary \
     > $OUT/run$i.log 2>&1 || { echo "[$setting] rc=$?"; tail -5 $OUT/run$i.log; exit 1; }
   for v in ${setting}; do unset "${v%%=*}"; done
   python3 - "$OUT/run$i" "$setting" <<'EOF'

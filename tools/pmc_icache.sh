@@ -8,7 +8,7 @@ rm -rf $OUT; mkdir -p $OUT
 ARGS="${*:---steps 30 --warmup 5 --no-cpu-baseline --no-secondary}"
 pass() {
     local name=$1; shift
-    timeout -k 10 120 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python3 bench.py $ARGS > $OUT/$name.log 2>&1
+    timeout -k 10 120 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python3 bench.py --full $ARGS > $OUT/$name.log 2>&1
     local rc=$?; [ $rc = 0 ] || { echo "$name rc=$rc"; tail -3 $OUT/$name.log; exit $rc; }
 }
 pass ic SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE

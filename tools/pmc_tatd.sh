@@ -10,7 +10,7 @@ timeout -k 10 60 rocprofv3 -L > $OUT/counters.txt 2>&1
 grep -oE "\b(TA|TD|TCP)_[A-Z0-9_]+" $OUT/counters.txt | sort -u > $OUT/tatd_names.txt
 pass() {
     local name=$1; shift
-    timeout -s KILL 120 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python3 bench.py $ARGS > $OUT/$name.log 2>&1
+    timeout -s KILL 120 rocprofv3 --pmc "$@" -d $OUT/$name -o $name --output-format csv -- python3 bench.py --full $ARGS > $OUT/$name.log 2>&1
     echo "$name rc=$?"
 }
 pass a TA_TA_BUSY_sum TA_BUFFER_READ_WAVEFRONTS_sum TD_TD_BUSY_sum TD_TC_STALL_sum GRBM_GUI_ACTIVE

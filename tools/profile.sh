@@ -9,7 +9,7 @@ mkdir -p $OUT
 ARGS="${BENCH_ARGS:---steps 50 --warmup 5 --no-cpu-baseline --no-secondary --inflight 1}"
 run() {  # name, rocprofv3 options...
     local name=$1; shift
-    timeout -k 10 300 rocprofv3 "$@" -d $OUT/$name -o $name --output-format csv -- python3 bench.py $ARGS > $OUT/$name.log 2>&1
+    timeout -k 10 300 rocprofv3 "$@" -d $OUT/$name -o $name --output-format csv -- python3 bench.py --full $ARGS > $OUT/$name.log 2>&1
     local rc=$?; echo "$name rc=$rc"; return $rc
 }
 rocprofv3 -L > $OUT/counters_list.txt 2>&1 || true

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for v in base ${VARIANTS:-ablate_4 ablate_16 ablate_32}; do
   lib=""
   [ "$v" != base ] && lib="TRI_RASTER_LIB=3d-renderer_amd/lib/variants/$v.so"
-  env $lib TRI_NOOP=1 timeout -k 10 200 python bench.py --steps 300 --warmup 20 --no-cpu-baseline --no-secondary \
+  env $lib TRI_NOOP=1 timeout -k 10 200 python bench.py --full --steps 300 --warmup 20 --no-cpu-baseline --no-secondary \
     --sim-world ${WORLD:-8} --sim-rank ${RANK_:-4} > gpurun_out/sa_$v.log 2>&1 || { echo "$v failed"; tail -3 gpurun_out/sa_$v.log; exit 1; }
   python3 -c "
 import json; d=json.loads(open('gpurun_out/sa_$v.log').read().strip().splitlines()[-1])

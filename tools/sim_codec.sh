@@ -7,7 +7,7 @@ out=gpurun_out/sim_codec.txt
 : > $out
 for codec in ${CODECS:-none bgr24 dbp}; do
   for r in 0 4; do
-    timeout -k 10 200 python -u bench.py --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
+    timeout -k 10 200 python -u bench.py --full --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
       --sim-codec $codec > gpurun_out/simc_${codec}_$r.json 2> gpurun_out/simc_${codec}_$r.err || { tail -20 gpurun_out/simc_${codec}_$r.err; exit 1; }
     python - "$codec" "$r" >> $out <<'P'
 import json, sys

@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for split in "0" "${SPLIT:-0,309,311,313,312,309,306,300}"; do
   for r in ${RANKS:-1 4 7}; do
     tag=$(echo $split | tr , _)
-    timeout -k 10 200 python -u bench.py --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
+    timeout -k 10 200 python -u bench.py --full --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
       --sim-display-rows $split --sim-codec dbp > gpurun_out/simr_${tag}_$r.json 2> gpurun_out/simr_${tag}_$r.err || { tail -20 gpurun_out/simr_${tag}_$r.err; exit 1; }
     python - "$tag" "$r" <<'P'
 import json, sys

@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out
 for d in ${DROWS:-135 270}; do
   for r in ${RANKS:-0 4}; do
-    timeout -k 10 200 python -u bench.py --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
+    timeout -k 10 200 python -u bench.py --full --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
       --sim-display-rows $d --sim-codec dbp > gpurun_out/simd_${d}_$r.json 2> gpurun_out/simd_${d}_$r.err || { tail -20 gpurun_out/simd_${d}_$r.err; exit 1; }
     python - "$d" "$r" <<'P'
 import json, sys

@@ -7,7 +7,7 @@ i=0
 for lib in "" $LIBS; do
   i=$((i + 1))
   for r in ${RANKS:-4}; do
-    TRI_RASTER_LIB=$lib timeout -k 10 200 python -u bench.py --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
+    TRI_RASTER_LIB=$lib timeout -k 10 200 python -u bench.py --full --steps 400 --warmup 50 --no-secondary --sim-world 8 --sim-rank $r \
       --sim-display-rows ${DROWS:-0} --sim-codec dbp --no-cpu-baseline > gpurun_out/simv_${i}_$r.json 2> gpurun_out/simv_${i}_$r.err || { tail -20 gpurun_out/simv_${i}_$r.err; exit 1; }
     python - "$i" "$r" "${lib:-default}" <<'P'
 import json, sys
