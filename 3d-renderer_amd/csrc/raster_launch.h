@@ -168,9 +168,17 @@ uint64_t tri_dbp_stream_bytes(uint64_t pixels, uint32_t slot_bytes);
 hipError_t tri_launch_dbp_unpack_bands(const uint8_t* const* src, uint32_t* const* dst, const uint64_t* n, uint32_t count,
                                        uint32_t alpha, uint32_t slot_bytes, hipStream_t stream, uint32_t* flags = nullptr);
 
+// Recording (record_yuv.hip): src width x height B8G8R8A8 (4-B aligned, pitch_bytes a multiple of 4 and at least
+// width * 4) -> dst 3 * width * height bytes at any alignment: the Y, U and V planes of the reference's fp64
+// conversion (VideoEncoder.cpp:716-736), byte for byte.
+hipError_t tri_launch_bgra_to_yuv444(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, uint8_t* dst,
+                                     hipStream_t stream);
+
 // Internal accessors for the group layer (tri_group.hip): a context's stream and device.
 hipStream_t tri_internal_stream(tri_ctx* ctx);
 int tri_internal_device(tri_ctx* ctx);
+// Whether the context renders every row of its frame (false: a row band).
+bool tri_internal_whole_frame(tri_ctx* ctx);
 // Record an error message for tri_last_error (returns `code`).
 int tri_internal_fail(int code, const char* msg);
 // The device a geometry object lives on; the UNORM8 decode table (b / 255) on a context's device.

@@ -848,6 +848,7 @@ void free_geometry(tri_geometry& g) {
 
 hipStream_t tri_internal_stream(tri_ctx* c) { return c->stream; }
 int tri_internal_device(tri_ctx* c) { return c->device; }
+bool tri_internal_whole_frame(tri_ctx* c) { return c->y0 == 0 && c->y1 == c->H; }
 int tri_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int tri_internal_geometry_device(const tri_geometry* g) { return g->device; }
 const float* tri_internal_unorm_lut(tri_ctx* c) { return c->d_lut + 256; }

@@ -1,7 +1,7 @@
 // RenderCommand.h — the static facade Trident-Forge drives the renderer through
 // (Trident/src/Renderer/RenderCommand.h:11-84), restricted to the draw path. Each call forwards to
 // the process-wide renderer (Startup::GetRenderer(), Application/Startup.h:38) — here
-// RenderCommand::GetRenderer(). AI / recording / text / gizmo entry points are outside the path.
+// RenderCommand::GetRenderer(). AI / text / gizmo entry points are outside the path.
 #pragma once
 
 #include <string>
@@ -41,6 +41,14 @@ public:
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }
+    // Viewport recording (RenderCommand.h: SetViewportRecordingEnabled / IsViewportRecording)
+    static bool SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, uint32_t width, uint32_t height,
+                                            const std::string& outputPath) {
+        return GetRenderer().SetViewportRecordingEnabled(enabled, viewportId, width, height, outputPath);
+    }
+    static bool IsViewportRecording() { return GetRenderer().IsViewportRecording(); }
+    static void GetRecordingExtent(uint32_t& width, uint32_t& height) { GetRenderer().GetRecordingExtent(width, height); }
+    static uint64_t GetRecordedFrameCount() { return GetRenderer().GetRecordedFrameCount(); }
     static size_t GetOrCreatePrimitiveMeshIndex(MeshComponent::PrimitiveType primitiveType) {
         return GetRenderer().GetOrCreatePrimitiveMeshIndex(primitiveType);
     }

@@ -18,6 +18,7 @@
 #include "../../../../include/tri_raster.h"
 #include "Camera.h"
 #include "Scene.h"
+#include "VideoEncoder.h"
 
 namespace Trident {
 
@@ -115,6 +116,23 @@ public:
     // its own frame). Changing it waits for every frame in flight and rebuilds the targets at the next DrawFrame.
     void SetFramesInFlight(uint32_t n);
     uint32_t GetFramesInFlight() const { return m_FramesInFlight; }
+    // Viewport recording (Renderer.h:205-220, Renderer.cpp:6171-6284; width and height replace the VkExtent2D).
+    // Enabling rounds an odd width or height up to the next even value (with a warning), starts a Y4M session at
+    // that extent with fps 1 (the header reads F1:1, as the reference's) and pins the viewport's target to it: while
+    // recording, SetViewport of that id keeps the recording extent (the reference guards the layout's resize the
+    // same way, Renderer.cpp:2813-2818). A start the encoder refuses (an FFmpeg container, another extension, a
+    // zero extent), or a request while SetDeviceCount > 1, leaves recording off, resizes nothing and returns false.
+    // Enabling while already recording finalises the running file first. Disabling finishes the frames in flight,
+    // finalises the file and always returns true; so do Shutdown and a SetDeviceCount above 1.
+    // While recording, every DrawFrame that renders the recorded viewport writes exactly one FRAME record holding
+    // that frame's pixels, in submission order (the reference delivers its readback one frame late): the frame is
+    // converted on the device behind its render pass (tri_recorder_capture) and written when its fence is waited for.
+    bool SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, uint32_t width, uint32_t height,
+                                     const std::string& outputPath);
+    bool IsViewportRecording() const { return m_Recording; }
+    uint32_t GetRecordingViewportId() const { return m_RecordingViewportId; }  // meaningful while recording
+    void GetRecordingExtent(uint32_t& width, uint32_t& height) const { width = m_RecordingWidth; height = m_RecordingHeight; }
+    uint64_t GetRecordedFrameCount() const { return m_VideoEncoder.GetFrameCount(); }  // of the current or last session
     uint32_t GetActiveViewportId() const { return m_ActiveViewportId; }
     ViewportInfo GetViewport() const;
     // Vulkan returned a VkDescriptorSet for ImGui (Renderer.h:235); here: an opaque handle, a pointer to
@@ -280,6 +298,8 @@ private:
         ViewportContext* m_Legacy = nullptr;  // the legacy present target among them
         ViewportContext* m_Blit = nullptr;    // the primary viewport target whose present blit was enqueued
         uint32_t m_BlitWidth = 0, m_BlitHeight = 0;
+        ViewportContext* m_Recorded = nullptr;  // the recorded viewport's target, captured into m_RecordSlot
+        uint32_t m_RecordSlot = 0;
     };
     std::deque<PendingFrame> m_Pending;  // oldest first; at most m_FramesInFlight
     void FinishOldestFrame();
@@ -291,6 +311,17 @@ private:
     std::map<uint32_t, uint32_t> m_LatestTarget;
     ViewportContext& TargetOf(uint32_t viewportId, ViewportContext& primary, uint32_t index);
     const ViewportContext* LatestTarget(uint32_t viewportId) const;
+
+    // viewport recording: the session, the recorded viewport and its pinned extent, and the device-side recorder
+    // (one slot per frame in flight; created by the first recorded DrawFrame, dropped with the viewport targets)
+    bool m_Recording = false;
+    uint32_t m_RecordingViewportId = 0;
+    uint32_t m_RecordingWidth = 0, m_RecordingHeight = 0;
+    std::string m_RecordingPath;
+    VideoEncoder m_VideoEncoder;
+    tri_recorder* m_Recorder = nullptr;
+    bool CaptureRecordedFrame(ViewportContext& target, uint32_t slot);
+    void StopRecording();  // finish the frames in flight, finalise the file
 
     glm::vec3 m_AmbientColor{0.03f};
     float m_AmbientIntensity = 1.0f;

@@ -117,6 +117,31 @@ int trident_app_draw_frame(trident_app* app);
 int trident_app_finish_frame(trident_app* app);
 /* Renderer::SetFramesInFlight (1..4; 1 = the reference's pacing). */
 int trident_app_set_frames_in_flight(trident_app* app, uint32_t n);
+/* Renderer::SetViewportRecordingEnabled: record viewport `viewport_id` to the .y4m file `path` at width x height
+ * (odd values rounded up to even; out_extent, nullable, gets the recording extent). TRI_E_STATE when the renderer
+ * refuses (an FFmpeg container or another extension, a zero extent, SetDeviceCount > 1): recording is then off.
+ * While recording, the viewport's camera is sized to the recording extent (as the panel that shows the target would
+ * size it), so the frames are those of a viewport of that extent. enabled = 0 finalises the file (path may be NULL). */
+int trident_app_set_recording(trident_app* app, int enabled, uint32_t viewport_id, uint32_t width, uint32_t height,
+                              const char* path, uint32_t out_extent[2]);
+/* Renderer::IsViewportRecording / GetRecordedFrameCount (FRAME records of the current or last session). */
+int trident_app_recording_state(trident_app* app, int* recording, uint64_t* frames);
+
+/* Trident::VideoEncoder on its own (no app, no device). begin / submit / end return TRI_OK where the encoder
+ * returns true and TRI_E_STATE where it returns false. submit_rgba: `bytes` bytes of RGBA8 rows, converted on the
+ * host; submit_planes: 3 * width * height bytes converted already (Y, U, V planes). */
+typedef struct trident_video trident_video;
+int trident_video_create(trident_video** out);
+void trident_video_destroy(trident_video* video);
+int trident_video_begin(trident_video* video, const char* path, uint32_t width, uint32_t height, uint32_t fps);
+int trident_video_submit_rgba(trident_video* video, const uint8_t* rgba, uint64_t bytes, uint32_t width,
+                              uint32_t height);
+int trident_video_submit_planes(trident_video* video, const uint8_t* yuv, uint32_t width, uint32_t height);
+int trident_video_end(trident_video* video);
+int trident_video_state(trident_video* video, int* active, uint64_t* frames);
+/* VideoEncoder::ConvertRgbaToYuv444 alone: `pixels` RGBA8 pixels -> 3 * pixels bytes, planar (alpha ignored). */
+int trident_video_convert_rgba(const uint8_t* rgba, uint64_t pixels, uint8_t* yuv);
+
 /* Renderer::GetViewportTexture: copies the viewport's image handle (TRI_E_STATE before its first frame). */
 int trident_app_viewport_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
 /* Renderer::GetGeometryUploadCount. */

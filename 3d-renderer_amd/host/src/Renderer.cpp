@@ -217,6 +217,8 @@ void Renderer::Init() {
 
 void Renderer::DestroyViewportTargets() {
     m_Pending.clear();  // (its targets go; tri_destroy / tri_group_destroy wait for their streams)
+    tri_recorder_destroy(m_Recorder);  // (waits for its captures; the next recorded DrawFrame makes a new one)
+    m_Recorder = nullptr;
     auto drop = [](ViewportContext& vc) {
         tri_destroy(vc.m_Ctx);
         tri_group_destroy(vc.m_Group);
@@ -246,6 +248,7 @@ void Renderer::DestroyViewportTargets() {
 }
 
 void Renderer::Shutdown() {
+    StopRecording();  // the frames in flight reach the file, which is finalised
     DestroyViewportTargets();
     m_Viewports.clear();
     if (m_Initialised) m_Shutdown = true;
@@ -297,6 +300,14 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         }
     }
     if (devs == m_Devices) return true;
+    if (m_Recording) {  // the recorded frames in flight are written before their targets go
+        if (devs.size() > 1) {
+            LogError("SetDeviceCount", "multi-device viewports are not recorded: the recording was finalised");
+            StopRecording();
+        } else {
+            FinishFrame();
+        }
+    }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
     return true;
@@ -852,6 +863,10 @@ void Renderer::SetViewport(uint32_t viewportId, const ViewportInfo& info) {
     ViewportContext& ctx = m_Viewports[viewportId];
     ctx.m_Info = info;
     ctx.m_Info.ViewportID = viewportId;
+    // the recorded viewport keeps the recording extent (every FRAME record has the session's size); a SetViewport
+    // after the recording ends sizes it again
+    if (m_Recording && viewportId == m_RecordingViewportId)
+        ctx.m_Info.Size = glm::vec2((float)m_RecordingWidth, (float)m_RecordingHeight);
     m_LastViewport = ctx.m_Info;
     m_ActiveViewportId = viewportId;  // Renderer.cpp:2753-2754
 }
@@ -1043,12 +1058,15 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     // RecordCommandBuffer's per-viewport render passes: the other viewports first, the primary one last
     // (Renderer.cpp:5208-5221), so the uniform block left bound is the primary viewport's
     ViewportContext* activeTarget = nullptr;
+    ViewportContext* recorded = nullptr;
     auto pass = [&](uint32_t id, ViewportContext& primary) {
         ViewportContext& vc = TargetOf(id, primary, tix);  // this frame's target of the viewport
         if (!PrepareViewport(vc)) return;
         tri_global_ubo ubo;
         UpdateUniformBuffer(GetActiveCamera(vc), ubo);
         if (!SubmitTarget(vc, ubo, draws, shadow, shadowOn)) return;
+        // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
+        if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
         lastUbo = ubo;
         submitted.push_back(&vc);
         m_LatestTarget[id] = tix;
@@ -1080,6 +1098,8 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     PendingFrame pf;
     pf.m_Targets = submitted;
     pf.m_Legacy = legacy;
+    pf.m_Recorded = recorded;
+    pf.m_RecordSlot = tix;
     if (primaryActive && m_PresentWidth && m_PresentHeight) {
         const Target t{activeTarget->m_Ctx, activeTarget->m_Group};
         if (t.Blit(m_PresentWidth, m_PresentHeight) == TRI_OK) {
@@ -1130,6 +1150,20 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
             m_PresentedWidth = (uint32_t)vc->m_Info.Size.x;  // the target PrepareViewport sized
             m_PresentedHeight = (uint32_t)vc->m_Info.Size.y;
         }
+        if (vc == p.m_Recorded && m_Recorder) {  // this frame's FRAME record, in submission order
+            // a re-rendered frame was captured incomplete: convert it again (as the present blit is redone below)
+            bool ok = rc == TRI_OK;
+            if (ok && rerendered)
+                ok = tri_recorder_release(m_Recorder, p.m_RecordSlot) == TRI_OK && CaptureRecordedFrame(*vc, p.m_RecordSlot);
+            const uint8_t* planes = nullptr;
+            if (ok && tri_recorder_wait(m_Recorder, p.m_RecordSlot, &planes) != TRI_OK) {
+                LogError("recording", tri_last_error());
+                ok = false;
+            }
+            if (ok && !m_VideoEncoder.SubmitPlanes(planes, m_RecordingWidth, m_RecordingHeight))
+                LogError("recording", "the encoder refused a frame");
+            if (tri_recorder_release(m_Recorder, p.m_RecordSlot) != TRI_OK) LogError("recording", tri_last_error());
+        }
         if (vc == p.m_Blit && rc != TRI_OK) p.m_Blit = nullptr;
         if (vc == p.m_Blit && rerendered) {  // (the first wait covered the blit behind the pass: same stream)
             if (t.Blit(p.m_BlitWidth, p.m_BlitHeight) != TRI_OK || t.Sync() != TRI_OK) {
@@ -1144,6 +1178,74 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
         m_PresentedWidth = p.m_BlitWidth;  // the blit's destination extent
         m_PresentedHeight = p.m_BlitHeight;
     }
+}
+
+// Renderer.cpp:6171-6284. The session starts before anything is resized, so a refused start changes nothing.
+bool Renderer::SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, uint32_t width, uint32_t height,
+                                           const std::string& outputPath) {
+    StopRecording();  // disabling, or a restart: the running file gets its frames in flight and is finalised
+    if (!enabled) return true;
+    if (m_Devices.size() > 1) {
+        LogError("viewport recording", "multi-device viewports (SetDeviceCount > 1) are not recorded");
+        return false;
+    }
+    const uint32_t w = width + (width & 1u), h = height + (height & 1u);  // even planes, as the reference rounds
+    if (w != width || h != height) {
+        char msg[128];
+        std::snprintf(msg, sizeof msg, "extent %ux%u adjusted to %ux%u (even dimensions)", width, height, w, h);
+        LogError("viewport recording", msg);
+    }
+    if (w > TRI_MAX_DIM || h > TRI_MAX_DIM) {
+        LogError("viewport recording", "extent beyond the framebuffer limit");
+        return false;
+    }
+    if (!m_VideoEncoder.BeginSession(outputPath, w, h, 1) || !m_VideoEncoder.IsSessionActive()) {
+        LogError("viewport recording", "the video encoder did not start a session");
+        return false;
+    }
+    FinishFrame();  // the recorded viewport's targets are about to be resized
+    m_Recording = true;
+    m_RecordingViewportId = viewportId;
+    m_RecordingWidth = w;
+    m_RecordingHeight = h;
+    m_RecordingPath = outputPath;
+    auto it = m_Viewports.find(viewportId);  // (a viewport registered later is pinned by SetViewport)
+    if (it != m_Viewports.end()) it->second.m_Info.Size = glm::vec2((float)w, (float)h);
+    tri_recorder_destroy(m_Recorder);  // a recorder of the previous extent
+    m_Recorder = nullptr;
+    return true;
+}
+
+void Renderer::StopRecording() {
+    if (!m_Recording) return;
+    FinishFrame();
+    m_Recording = false;
+    if (m_VideoEncoder.IsSessionActive() && !m_VideoEncoder.EndSession())
+        LogError("viewport recording", ("could not finalise " + m_RecordingPath).c_str());
+    tri_recorder_destroy(m_Recorder);
+    m_Recorder = nullptr;
+}
+
+// The recorded viewport's frame -> recorder slot `slot` (asynchronous). The recorder is made here, once the target
+// exists: one slot per frame in flight, on the target's device.
+bool Renderer::CaptureRecordedFrame(ViewportContext& vc, uint32_t slot) {
+    if (!vc.m_Ctx || !vc.m_HasImage) return false;  // (multi-device viewports are refused when recording starts)
+    if (vc.m_Width != m_RecordingWidth || vc.m_Height != m_RecordingHeight) {
+        LogError("recording", "the viewport target does not have the recording extent");
+        return false;
+    }
+    if (!m_Recorder) {  // (SetFramesInFlight drops it with the targets, so its slots always match)
+        if (tri_recorder_create(vc.m_Image.device, m_RecordingWidth, m_RecordingHeight, m_FramesInFlight, &m_Recorder) !=
+            TRI_OK) {
+            LogError("recording", tri_last_error());
+            return false;
+        }
+    }
+    if (tri_recorder_capture(m_Recorder, slot, vc.m_Ctx) != TRI_OK) {
+        LogError("recording", tri_last_error());
+        return false;
+    }
+    return true;
 }
 
 void Renderer::RecordFrameTiming(double ms) {  // Renderer.cpp:6286-6343

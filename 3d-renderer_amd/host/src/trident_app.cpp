@@ -361,7 +361,12 @@ int trident_app_set_viewport(trident_app* app, uint32_t viewport_id, uint32_t wi
         app->renderer.SetViewport(viewport_id, info);
         // The viewport panel resizes the camera that renders into it (ApplicationLayer.cpp:253-290).
         if (width && height) {
-            const glm::vec2 s{(float)width, (float)height};
+            glm::vec2 s{(float)width, (float)height};
+            if (app->renderer.IsViewportRecording() && app->renderer.GetRecordingViewportId() == viewport_id) {
+                uint32_t rw = 0, rh = 0;  // the recorded viewport keeps the recording extent, and so does its camera
+                app->renderer.GetRecordingExtent(rw, rh);
+                s = glm::vec2{(float)rw, (float)rh};
+            }
             if (viewport_id == 2u) app->runtime.SetViewportSize(s);
             else app->editor.SetViewportSize(s);
         }
@@ -525,6 +530,93 @@ int trident_app_set_frames_in_flight(trident_app* app, uint32_t n) {
         app->renderer.SetFramesInFlight(n);
         return TRI_OK;
     });
+}
+
+int trident_app_set_recording(trident_app* app, int enabled, uint32_t viewport_id, uint32_t width, uint32_t height,
+                              const char* path, uint32_t out_extent[2]) {
+    return Guard(app, [&] {
+        if (enabled && !path) return TRI_E_INVALID;
+        const bool ok = app->renderer.SetViewportRecordingEnabled(enabled != 0, viewport_id, width, height, path ? path : "");
+        if (out_extent) app->renderer.GetRecordingExtent(out_extent[0], out_extent[1]);
+        if (ok && enabled) {  // the panel now shows the recording extent: its camera follows (as set_viewport does)
+            uint32_t rw = 0, rh = 0;
+            app->renderer.GetRecordingExtent(rw, rh);
+            const glm::vec2 s{(float)rw, (float)rh};
+            if (viewport_id == 2u) app->runtime.SetViewportSize(s);
+            else app->editor.SetViewportSize(s);
+        }
+        return ok ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_app_recording_state(trident_app* app, int* recording, uint64_t* frames) {
+    return Guard(app, [&] {
+        if (recording) *recording = app->renderer.IsViewportRecording() ? 1 : 0;
+        if (frames) *frames = app->renderer.GetRecordedFrameCount();
+        return TRI_OK;
+    });
+}
+
+struct trident_video {
+    VideoEncoder encoder;
+};
+
+int trident_video_create(trident_video** out) {
+    if (!out) return TRI_E_INVALID;
+    *out = nullptr;
+    try {
+        *out = new trident_video();
+        return TRI_OK;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+void trident_video_destroy(trident_video* video) { delete video; }
+
+int trident_video_begin(trident_video* video, const char* path, uint32_t width, uint32_t height, uint32_t fps) {
+    if (!video || !path) return TRI_E_INVALID;
+    try {
+        return video->encoder.BeginSession(path, width, height, fps) ? TRI_OK : TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_INVALID;
+    }
+}
+
+int trident_video_submit_rgba(trident_video* video, const uint8_t* rgba, uint64_t bytes, uint32_t width, uint32_t height) {
+    if (!video) return TRI_E_INVALID;
+    try {
+        VideoEncoder::RecordedFrame frame;
+        if (rgba && bytes) frame.m_Pixels.assign(rgba, rgba + bytes);
+        frame.m_Width = width;
+        frame.m_Height = height;
+        return video->encoder.SubmitFrame(frame) ? TRI_OK : TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+int trident_video_submit_planes(trident_video* video, const uint8_t* yuv, uint32_t width, uint32_t height) {
+    if (!video) return TRI_E_INVALID;
+    return video->encoder.SubmitPlanes(yuv, width, height) ? TRI_OK : TRI_E_STATE;
+}
+
+int trident_video_end(trident_video* video) {
+    if (!video) return TRI_E_INVALID;
+    return video->encoder.EndSession() ? TRI_OK : TRI_E_STATE;
+}
+
+int trident_video_state(trident_video* video, int* active, uint64_t* frames) {
+    if (!video) return TRI_E_INVALID;
+    if (active) *active = video->encoder.IsSessionActive() ? 1 : 0;
+    if (frames) *frames = video->encoder.GetFrameCount();
+    return TRI_OK;
+}
+
+int trident_video_convert_rgba(const uint8_t* rgba, uint64_t pixels, uint8_t* yuv) {
+    if (pixels && (!rgba || !yuv)) return TRI_E_INVALID;
+    VideoEncoder::ConvertRgbaToYuv444(rgba, pixels, yuv);
+    return TRI_OK;
 }
 
 int trident_app_finish_frame(trident_app* app) {

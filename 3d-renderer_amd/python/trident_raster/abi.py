@@ -261,6 +261,12 @@ CABI_FUNCTIONS = [
     ("tri_xfer_comm_create_loopback", C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]),
     ("tri_dbp_unpack_bands", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32,
                                        C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("tri_convert_yuv444", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("tri_recorder_create", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_recorder_destroy", C.c_int, [C.c_void_p]),
+    ("tri_recorder_capture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("tri_recorder_wait", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_recorder_release", C.c_int, [C.c_void_p, C.c_uint32]),
     ("tri_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("tri_get_timing", C.c_int, [C.c_void_p, C.POINTER(TriTiming)]),
     ("tri_get_frame_stats", C.c_int, [C.c_void_p, C.POINTER(TriFrameStats)]),

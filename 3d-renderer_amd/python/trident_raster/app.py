@@ -71,6 +71,17 @@ _APP_FUNCTIONS = [
     ("trident_app_set_ai_blend_strength", C.c_int, [C.c_void_p, C.c_float]),
     ("trident_app_submit_ai_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("trident_app_read_present", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("trident_app_set_recording", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p,
+                                            C.POINTER(C.c_uint32 * 2)]),
+    ("trident_app_recording_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("trident_video_create", C.c_int, [C.POINTER(C.c_void_p)]),
+    ("trident_video_destroy", None, [C.c_void_p]),
+    ("trident_video_begin", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("trident_video_submit_rgba", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
+    ("trident_video_submit_planes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("trident_video_end", C.c_int, [C.c_void_p]),
+    ("trident_video_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("trident_video_convert_rgba", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
 ]
 
 _lib = None
@@ -244,6 +255,21 @@ class TridentApp:
         """Wait for the last draw_frame's frame (Renderer::FinishFrame; the next draw_frame does it first)."""
         _check(self._lib.trident_app_finish_frame(self._h), "finish_frame")
 
+    def set_recording(self, enabled, viewport_id=0, width=0, height=0, path=None):
+        """Renderer::SetViewportRecordingEnabled -> (accepted, (width, height) of the recording extent)."""
+        ext = (C.c_uint32 * 2)()
+        rc = self._lib.trident_app_set_recording(self._h, 1 if enabled else 0, viewport_id, width, height,
+                                                 os.fsencode(path) if path is not None else None, C.byref(ext))
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_recording")
+        return rc == abi.TRI_OK, (ext[0], ext[1])
+
+    def recording_state(self):
+        """(Renderer::IsViewportRecording, GetRecordedFrameCount)."""
+        rec, frames = C.c_int(), C.c_uint64()
+        _check(self._lib.trident_app_recording_state(self._h, C.byref(rec), C.byref(frames)), "recording_state")
+        return bool(rec.value), frames.value
+
     def read_pixels(self, viewport_id, width, height, depth=True):
         rgba = np.zeros((height, width, 4), np.uint8)
         d = np.zeros((height, width), np.float32) if depth else None
@@ -341,6 +367,65 @@ class TridentApp:
         _check(self._lib.trident_app_read_present(self._h, out.ctypes.data, width, height), "read_present")
         return out
 
+
+class VideoEncoder:
+    """Trident::VideoEncoder on its own (Y4M sessions on the host); every method returns the encoder's bool."""
+
+    def __init__(self):
+        self._lib = load_library()
+        h = C.c_void_p()
+        _check(self._lib.trident_video_create(C.byref(h)), "trident_video_create")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.trident_video_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _bool(self, rc, what):
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, what)
+        return rc == abi.TRI_OK
+
+    def begin(self, path, width, height, fps):
+        return self._bool(self._lib.trident_video_begin(self._h, os.fsencode(path), width, height, fps), "video_begin")
+
+    def submit_rgba(self, rgba, width, height):
+        """SubmitFrame: RGBA8 rows (any array; its bytes are the pixel buffer, which may be empty)."""
+        a = np.ascontiguousarray(rgba, np.uint8)
+        return self._bool(self._lib.trident_video_submit_rgba(self._h, a.ctypes.data if a.size else None, a.size, width,
+                                                              height), "video_submit_rgba")
+
+    def submit_planes(self, yuv, width, height):
+        a = np.ascontiguousarray(yuv, np.uint8)
+        if a.size != 3 * width * height:
+            raise ValueError("submit_planes: 3 * width * height bytes expected")
+        return self._bool(self._lib.trident_video_submit_planes(self._h, a.ctypes.data, width, height),
+                          "video_submit_planes")
+
+    def end(self):
+        return self._bool(self._lib.trident_video_end(self._h), "video_end")
+
+    def state(self):
+        """(IsSessionActive, frames written)."""
+        act, frames = C.c_int(), C.c_uint64()
+        _check(self._lib.trident_video_state(self._h, C.byref(act), C.byref(frames)), "video_state")
+        return bool(act.value), frames.value
+
+
+def convert_rgba(rgba):
+    """VideoEncoder::ConvertRgbaToYuv444 on the host: RGBA8 pixels [..., 4] -> uint8 [3, pixels] (Y, U, V planes)."""
+    lib = load_library()
+    a = np.ascontiguousarray(rgba, np.uint8).reshape(-1, 4)
+    out = np.empty((3, a.shape[0]), np.uint8)
+    _check(lib.trident_video_convert_rgba(a.ctypes.data, a.shape[0], out.ctypes.data), "video_convert_rgba")
+    return out
 
 
 def load_image(path, flip=True):

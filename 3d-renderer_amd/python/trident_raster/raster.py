@@ -304,6 +304,59 @@ def dbp_bytes(pixels, slot_bytes):
     return int(_lib.tri_dbp_bytes(pixels, slot_bytes))
 
 
+def convert_yuv444(src_ptr, width, height, pitch_bytes, dst_ptr, stream_ptr=None):
+    """tri_convert_yuv444: B8G8R8A8 rows (pitch_bytes apart) -> the Y, U, V planes (3 * width * height bytes) on the
+    device, stream-ordered."""
+    load_library()
+    _check(_lib.tri_convert_yuv444(C.c_void_p(src_ptr) if src_ptr else None, width, height, pitch_bytes,
+                                   C.c_void_p(dst_ptr) if dst_ptr else None, C.c_void_p(stream_ptr) if stream_ptr else None))
+
+
+class TriRecorder:
+    """tri_recorder: `slots` device + pinned YUV 4:4:4 buffers of one extent; capture is asynchronous."""
+
+    def __init__(self, width, height, slots, device=-1):
+        lib = load_library()
+        r = C.c_void_p()
+        _check(lib.tri_recorder_create(device, width, height, slots, C.byref(r)))
+        self._r = r
+        self.width, self.height, self.slots = width, height, slots
+
+    def close(self):
+        if self._r:
+            _lib.tri_recorder_destroy(self._r)
+            self._r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def capture(self, slot, raster):
+        _check(_lib.tri_recorder_capture(self._r, slot, raster._ctx))
+
+    def wait_pointer(self, slot):
+        p = C.c_void_p()
+        _check(_lib.tri_recorder_wait(self._r, slot, C.byref(p)))
+        return p.value
+
+    def wait(self, slot):
+        """The slot's planes, uint8 [3, height, width]: a view of the pinned buffer, valid until release."""
+        p = self.wait_pointer(slot)
+        buf = (C.c_uint8 * (3 * self.width * self.height)).from_address(p)
+        return np.frombuffer(buf, np.uint8).reshape(3, self.height, self.width)
+
+    def release(self, slot):
+        _check(_lib.tri_recorder_release(self._r, slot))
+
+
 def copy_device_to_host(ptr, nbytes, device=0):
     """hipMemcpy of `nbytes` at a device pointer (a tri_image handle) into a numpy byte array."""
     hip = C.CDLL("libamdhip64.so")

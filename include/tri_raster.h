@@ -347,6 +347,39 @@ uint64_t tri_dbp_bytes(uint64_t pixels, uint32_t slot_bytes);
 int tri_dbp_unpack_bands(const void* const* streams_in, void* const* bgra8, const uint64_t* pixels, uint32_t count,
                          uint32_t alpha, uint32_t slot_bytes, void* hip_stream);
 
+/* ---- viewport recording (Renderer::SetViewportRecordingEnabled / SubmitViewportFrame, Renderer.h:205-220) ----
+ * The reference reads the frame back and converts it on the host (VideoEncoder::ConvertRgbaToYuv444,
+ * VideoEncoder.cpp:716-736); here the conversion runs on the device behind the frame and the planes come back
+ * through pinned memory while the next frames render.
+ * tri_convert_yuv444: B8G8R8A8 (device pointer, 4-B aligned, rows pitch_bytes apart: a multiple of 4, at least
+ * width * 4) -> 3 * width * height bytes at any alignment (device pointer): the Y plane, then U, then V, each
+ * width * height bytes, rows top to bottom — one Y4M C444 FRAME payload. Per pixel, in IEEE double and this order:
+ *   Y = 0.299 R + 0.587 G + 0.114 B,  U = -0.169 R - 0.331 G + 0.5 B + 128,  V = 0.5 R - 0.419 G - 0.081 B + 128,
+ * clamped to [0, 255] and truncated (grey 128 gives Y = 127); alpha is ignored. Stream-ordered on hip_stream
+ * (NULL = the null stream). Bytes beyond `width` in a pitched row are not read. */
+int tri_convert_yuv444(const void* device_bgra8, uint32_t width, uint32_t height, uint32_t pitch_bytes,
+                       void* device_yuv, void* hip_stream);
+/* A recorder owns `slots` (1..8) device YUV buffers of one extent, as many pinned host buffers, a copy stream and
+ * per-slot events, on one device (-1 = current). Each slot is idle or busy:
+ *   tri_recorder_capture  (idle -> busy, asynchronous) on the context's stream, behind its last tri_render,
+ *                         converts the colour target tri_bind_output currently binds into the slot, then copies it
+ *                         to the slot's pinned buffer on the recorder's stream. TRI_E_STATE: a busy slot, a
+ *                         row-band context (as tri_blit_linear); TRI_E_INVALID: a context of another extent or
+ *                         on another device, a slot out of range.
+ *   tri_recorder_wait     waits for the slot's copy and returns the pinned planes (tri_convert_yuv444's layout),
+ *                         valid until the release. TRI_E_STATE for an idle slot.
+ *   tri_recorder_release  (busy -> idle) first waits for a capture that has not finished, so the slot's next
+ *                         capture cannot race the copy; releasing an idle slot is TRI_OK.
+ * A frame that tri_synchronize reports as TRI_E_OVERFLOW was captured incomplete: release the slot and capture
+ * again after the re-render. One host thread per recorder. Multi-device frames (tri_group) are out of scope: a
+ * recorder captures single contexts only. tri_recorder_destroy waits for the captures in flight; NULL is TRI_OK. */
+typedef struct tri_recorder tri_recorder;
+int tri_recorder_create(int32_t device, uint32_t width, uint32_t height, uint32_t slots, tri_recorder** out);
+int tri_recorder_destroy(tri_recorder* recorder);
+int tri_recorder_capture(tri_recorder* recorder, uint32_t slot, tri_ctx* ctx);
+int tri_recorder_wait(tri_recorder* recorder, uint32_t slot, const uint8_t** yuv);
+int tri_recorder_release(tri_recorder* recorder, uint32_t slot);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
