@@ -173,6 +173,10 @@ hipError_t tri_launch_dbp_unpack_bands(const uint8_t* const* src, uint32_t* cons
 // conversion (VideoEncoder.cpp:716-736), byte for byte.
 hipError_t tri_launch_bgra_to_yuv444(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, uint8_t* dst,
                                      hipStream_t stream);
+// The AI input tensor (frame_tensor.hip): the same source -> dst width * height * 4 floats (4-B aligned; 16-B aligned
+// for the 16-B store path), R, G, B, A per pixel, each (float)byte * (1.0f / 255.0f) (Renderer.cpp:1111-1389).
+hipError_t tri_launch_bgra_to_rgba_f32(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, float* dst,
+                                       hipStream_t stream);
 
 // Internal accessors for the group layer (tri_group.hip): a context's stream and device.
 hipStream_t tri_internal_stream(tri_ctx* ctx);

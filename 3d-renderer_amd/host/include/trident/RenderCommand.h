@@ -1,7 +1,7 @@
 // RenderCommand.h — the static facade Trident-Forge drives the renderer through
 // (Trident/src/Renderer/RenderCommand.h:11-84), restricted to the draw path. Each call forwards to
 // the process-wide renderer (Startup::GetRenderer(), Application/Startup.h:38) — here
-// RenderCommand::GetRenderer(). AI / text / gizmo entry points are outside the path.
+// RenderCommand::GetRenderer(). Text / gizmo entry points are outside the path.
 #pragma once
 
 #include <string>
@@ -49,6 +49,25 @@ public:
     static bool IsViewportRecording() { return GetRenderer().IsViewportRecording(); }
     static void GetRecordingExtent(uint32_t& width, uint32_t& height) { GetRenderer().GetRecordingExtent(width, height); }
     static uint64_t GetRecordedFrameCount() { return GetRenderer().GetRecordedFrameCount(); }
+    // Dataset capture (RenderCommand.h:69-77)
+    static void SetFrameDatasetCaptureEnabled(bool enabled) { GetRenderer().SetFrameDatasetCaptureEnabled(enabled); }
+    static bool IsFrameDatasetCaptureEnabled() { return GetRenderer().IsFrameDatasetCaptureEnabled(); }
+    static void SetFrameDatasetCaptureDirectory(const std::string& directory) {
+        GetRenderer().SetFrameDatasetCaptureDirectory(directory);
+    }
+    static std::string GetFrameDatasetCaptureDirectory() { return GetRenderer().GetFrameDatasetCaptureDirectory(); }
+    static void SetFrameDatasetCaptureInterval(uint32_t interval) { GetRenderer().SetFrameDatasetCaptureInterval(interval); }
+    static uint32_t GetFrameDatasetCaptureInterval() { return GetRenderer().GetFrameDatasetCaptureInterval(); }
+    // The AI loop's ends (the frame generator itself lives outside the library)
+    static bool SetAiReadbackEnabled(bool enabled) { return GetRenderer().SetAiReadbackEnabled(enabled); }
+    static bool IsAiReadbackEnabled() { return GetRenderer().IsAiReadbackEnabled(); }
+    static void SetAiThrottleIntervals(uint32_t readbackMs, uint32_t inferenceMs) {
+        GetRenderer().SetAiThrottleIntervals(readbackMs, inferenceMs);
+    }
+    static bool TryAcquireRenderedFrame(std::vector<float>& out) { return GetRenderer().TryAcquireRenderedFrame(out); }
+    static bool SubmitAiOutput(const float* data, size_t count, const int64_t* shape, size_t rank) {
+        return GetRenderer().SubmitAiOutput(data, count, shape, rank);
+    }
     static size_t GetOrCreatePrimitiveMeshIndex(MeshComponent::PrimitiveType primitiveType) {
         return GetRenderer().GetOrCreatePrimitiveMeshIndex(primitiveType);
     }

@@ -18,6 +18,7 @@
 #include "../../../../include/tri_raster.h"
 #include "Camera.h"
 #include "Scene.h"
+#include "FrameDatasetRecorder.h"
 #include "VideoEncoder.h"
 
 namespace Trident {
@@ -133,6 +134,49 @@ public:
     uint32_t GetRecordingViewportId() const { return m_RecordingViewportId; }  // meaningful while recording
     void GetRecordingExtent(uint32_t& width, uint32_t& height) const { width = m_RecordingWidth; height = m_RecordingHeight; }
     uint64_t GetRecordedFrameCount() const { return m_VideoEncoder.GetFrameCount(); }  // of the current or last session
+    // Frame readback for AI consumers (SetReadbackEnabled / ResolvePendingReadback / TryAcquireRenderedFrame,
+    // Renderer.cpp:984-995, :1111-1389). SetAiReadbackEnabled stands in for m_FrameGenerator.IsInitialised() in the
+    // reference's l_ReadbackRequired (:787): the generator lives outside the library and says so here. While enabled,
+    // a DrawFrame that renders the active viewport on one device converts it on the device, behind its pass, into a
+    // channels-last RGBA float tensor (tri_framegrab, one slot per frame in flight; each value float(byte) *
+    // (1.0f / 255.0f)), provided the readback throttle has elapsed at submission; when a present extent is set and
+    // differs from the viewport's, nothing is captured (the reference skips the copy, :5301-5337). The frame's fence
+    // resolves the capture (again after an overflow re-render, as recording does): its floats become the pending
+    // readback, a newer frame replacing an unconsumed one. Refused (false) while SetDeviceCount > 1, which also turns
+    // it off. Independent of viewport recording.
+    bool SetAiReadbackEnabled(bool enabled);
+    bool IsAiReadbackEnabled() const { return m_AiReadback; }
+    // The readback and inference throttles in milliseconds (Renderer.h:522-523: 66 and 66); 0 disables one.
+    void SetAiThrottleIntervals(uint32_t readbackMs, uint32_t inferenceMs);
+    // The pending tensor, once: true moves it into `out` (width * height * 4 floats) and clears it (:984-995). Subject
+    // to the inference throttle (:933-940): false until it has elapsed since the last acquisition. When dataset
+    // capture is on, the tensor is recorded as the input sample with shape {1, H, W, 4} (:973-977). Public here
+    // because the generator is outside.
+    bool TryAcquireRenderedFrame(std::vector<float>& out);
+    // The same into the caller's memory (`capacity` floats; too few: false, and the tensor stays pending). Until the
+    // next DrawFrame the pending tensor still lies in the grab's pinned buffer, so this is its only host copy.
+    bool TryAcquireRenderedFrame(float* out, size_t capacity);
+    void GetFrameReadbackExtent(uint32_t& width, uint32_t& height) const { width = m_FrameReadbackWidth; height = m_FrameReadbackHeight; }
+    // The latest resolved tensor where it was made, for a consumer on the same device: valid until the next
+    // DrawFrame. false before the first resolved frame.
+    bool GetFrameReadbackDeviceTensor(const float** device, uint32_t& width, uint32_t& height);
+    // The generator's output (ProcessAiFrame, Renderer.cpp:913-931): `shape` must have rank 3 (HWC) or 4 (NHWC), else
+    // false and nothing changes. Dimensions <= 0 fall back to the readback extent and channel count. The data is
+    // normalised as NormaliseAndReorderAiOutput does (:358-415: scaled by 1/255 when max > 1 + 1e-3 or min < -1e-3,
+    // channels 0 and 2 swapped when there are at least 3, clamped to [0, 1]), recorded as the oldest pending
+    // sample's output when dataset capture is on, and handed to SubmitAiInterpolation at the canonical shape.
+    bool SubmitAiOutput(const float* data, size_t count, const int64_t* shape, size_t rank);
+    // The normalisation alone, in place, on whole pixels of `channels` floats (unchanged, with a log line, for a
+    // channel count <= 0 or one that does not divide the element count).
+    static void NormaliseAndReorderAiOutput(std::vector<float>& data, int64_t channels);
+    // Frame dataset capture (Renderer.cpp:2498-2525, :6393-6400). Init honours TRIDENT_DATASET_CAPTURE_ENABLE (any
+    // non-empty value) and TRIDENT_DATASET_CAPTURE_DIR (:551-576). Disabling and Shutdown write what is queued.
+    void SetFrameDatasetCaptureEnabled(bool enabled);
+    void SetFrameDatasetCaptureDirectory(const std::string& directory);  // empty: current_path()/DatasetCapture
+    void SetFrameDatasetCaptureInterval(uint32_t interval);              // at least 1
+    bool IsFrameDatasetCaptureEnabled() const { return m_FrameDatasetCaptureEnabled; }
+    const std::string& GetFrameDatasetCaptureDirectory() const { return m_FrameDatasetCaptureDirectory; }
+    uint32_t GetFrameDatasetCaptureInterval() const { return m_FrameDatasetCaptureInterval; }
     uint32_t GetActiveViewportId() const { return m_ActiveViewportId; }
     ViewportInfo GetViewport() const;
     // Vulkan returned a VkDescriptorSet for ImGui (Renderer.h:235); here: an opaque handle, a pointer to
@@ -300,6 +344,8 @@ private:
         uint32_t m_BlitWidth = 0, m_BlitHeight = 0;
         ViewportContext* m_Recorded = nullptr;  // the recorded viewport's target, captured into m_RecordSlot
         uint32_t m_RecordSlot = 0;
+        ViewportContext* m_Grabbed = nullptr;  // the active viewport's target, captured into the grab's m_RecordSlot
+        uint64_t m_GrabGeneration = 0;         // ... of this grab (a rebuilt grab holds nothing of this frame)
     };
     std::deque<PendingFrame> m_Pending;  // oldest first; at most m_FramesInFlight
     void FinishOldestFrame();
@@ -322,6 +368,34 @@ private:
     tri_recorder* m_Recorder = nullptr;
     bool CaptureRecordedFrame(ViewportContext& target, uint32_t slot);
     void StopRecording();  // finish the frames in flight, finalise the file
+
+    // AI readback: the device-side grab (made by the first captured DrawFrame, dropped with the viewport targets and
+    // when the active viewport's extent changes), the throttles and the pending tensor
+    bool m_AiReadback = false;
+    tri_framegrab* m_Grab = nullptr;
+    uint32_t m_GrabWidth = 0, m_GrabHeight = 0;
+    uint64_t m_GrabGeneration = 0;
+    int32_t m_GrabHeldSlot = -1;  // the slot whose device tensor GetFrameReadbackDeviceTensor hands out
+    const float* m_GrabDeviceTensor = nullptr;
+    const float* m_GrabHostTensor = nullptr;  // the held slot's pinned buffer
+    bool m_PendingInSlot = false;             // the pending readback is m_GrabHostTensor (else m_PendingFrameReadback)
+    size_t FrameReadbackCount() const { return (size_t)m_FrameReadbackWidth * m_FrameReadbackHeight * s_FrameReadbackChannelCount; }
+    void ReleaseHeldReadbackSlot(bool keepPending);
+    bool AiInferenceThrottleElapsed();
+    std::chrono::milliseconds m_AiReadbackInterval{66}, m_AiInferenceInterval{66};
+    std::chrono::steady_clock::time_point m_NextAiReadbackTime{}, m_NextAiInferenceTime{};
+    std::vector<float> m_PendingFrameReadback;
+    uint32_t m_FrameReadbackWidth = 0, m_FrameReadbackHeight = 0;
+    static constexpr uint32_t s_FrameReadbackChannelCount = 4;
+    bool CaptureReadbackFrame(ViewportContext& target, uint32_t slot);
+    void ResolveReadbackFrame(ViewportContext& target, uint32_t slot, bool ok, bool rerendered);
+    void DropGrab();
+    // dataset capture
+    FrameDatasetRecorder m_FrameDatasetRecorder;
+    bool m_FrameDatasetCaptureEnabled = false;
+    std::string m_FrameDatasetCaptureDirectory;
+    uint32_t m_FrameDatasetCaptureInterval = 1;
+    void SyncFrameDatasetRecorder();
 
     glm::vec3 m_AmbientColor{0.03f};
     float m_AmbientIntensity = 1.0f;

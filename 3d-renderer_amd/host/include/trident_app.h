@@ -142,6 +142,52 @@ int trident_video_state(trident_video* video, int* active, uint64_t* frames);
 /* VideoEncoder::ConvertRgbaToYuv444 alone: `pixels` RGBA8 pixels -> 3 * pixels bytes, planar (alpha ignored). */
 int trident_video_convert_rgba(const uint8_t* rgba, uint64_t pixels, uint8_t* yuv);
 
+/* ---- AI readback and dataset capture ---- */
+/* Renderer::SetFrameDatasetCaptureDirectory (when `directory` is not NULL; "" = the default directory), ...Interval
+ * (when interval != 0) and ...Enabled, in this order. Disabling writes every queued sample before it returns. */
+int trident_app_set_dataset_capture(trident_app* app, int enabled, const char* directory, uint32_t interval);
+/* The getters: IsFrameDatasetCaptureEnabled, GetFrameDatasetCaptureInterval, and the directory copied into
+ * `directory` (capacity bytes with the terminator; TRI_E_INVALID when it does not fit). Every pointer is nullable. */
+int trident_app_dataset_capture_state(trident_app* app, int* enabled, uint32_t* interval, char* directory,
+                                      uint32_t capacity);
+/* Renderer::SetAiThrottleIntervals(readback_ms, inference_ms) (0 disables a throttle), then SetAiReadbackEnabled.
+ * TRI_E_STATE when the renderer refuses (SetDeviceCount > 1). */
+int trident_app_set_ai_readback(trident_app* app, int enabled, uint32_t readback_ms, uint32_t inference_ms);
+/* Renderer::IsAiReadbackEnabled. */
+int trident_app_ai_readback_state(trident_app* app, int* enabled);
+/* Renderer::TryAcquireRenderedFrame: *got = 1 and width * height * 4 floats in `out` (R, G, B, A per pixel) when a
+ * tensor was pending and the inference throttle has elapsed, else *got = 0. TRI_E_INVALID, with the tensor left
+ * pending, when `capacity` (in floats) is too small. width and height (nullable) always get
+ * Renderer::GetFrameReadbackExtent, the extent to size `out` for (0 x 0 before the first resolved frame). */
+int trident_app_acquire_frame(trident_app* app, float* out, uint64_t capacity, uint32_t* width, uint32_t* height, int* got);
+/* Renderer::GetFrameReadbackDeviceTensor: the latest tensor on the device (*got = 0 before one was resolved), valid
+ * until the next draw_frame. Waits for the frames in flight. */
+int trident_app_readback_device_tensor(trident_app* app, const float** device, uint32_t* width, uint32_t* height, int* got);
+/* Renderer::SubmitAiOutput: TRI_OK where it returns true, TRI_E_STATE where it returns false. */
+int trident_app_submit_ai_output(trident_app* app, const float* data, uint64_t count, const int64_t* shape, uint32_t rank);
+/* Renderer::NormaliseAndReorderAiOutput alone, in place (no app, no device). */
+int trident_ai_normalise_output(float* data, uint64_t count, int64_t channels);
+
+/* Trident::FrameDatasetRecorder on its own (no app, no device). record_input / record_output forward to
+ * RecordInputFrame (rank 0: the default shape) / RecordAiOutput; enable(0) and flush return once the queued files are
+ * written. state: the next sample index and the inputs still waiting for an output. */
+typedef struct trident_dataset trident_dataset;
+int trident_dataset_create(trident_dataset** out);
+void trident_dataset_destroy(trident_dataset* dataset);
+int trident_dataset_set_directory(trident_dataset* dataset, const char* directory);
+int trident_dataset_set_interval(trident_dataset* dataset, uint32_t interval);
+int trident_dataset_enable(trident_dataset* dataset, int enabled);
+int trident_dataset_reset(trident_dataset* dataset);
+int trident_dataset_record_input(trident_dataset* dataset, const float* data, uint64_t count, uint32_t width,
+                                 uint32_t height, uint32_t channels, const int64_t* shape, uint32_t rank);
+int trident_dataset_record_output(trident_dataset* dataset, const float* data, uint64_t count, const int64_t* shape,
+                                  uint32_t rank);
+int trident_dataset_flush(trident_dataset* dataset);
+int trident_dataset_state(trident_dataset* dataset, int* enabled, uint32_t* interval, uint64_t* next_index,
+                          uint64_t* pending);
+/* FrameDatasetRecorder::WriteNpyFile alone: TRI_OK, or TRI_E_STATE where it refuses (no file is written then). */
+int trident_dataset_write_npy(const char* path, const float* data, uint64_t count, const int64_t* shape, uint32_t rank);
+
 /* Renderer::GetViewportTexture: copies the viewport's image handle (TRI_E_STATE before its first frame). */
 int trident_app_viewport_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
 /* Renderer::GetGeometryUploadCount. */

@@ -12,7 +12,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <limits>
 
 namespace Trident {
@@ -23,6 +25,12 @@ constexpr const char* kDefaultTextureKey = "renderer://default-white";
 constexpr size_t kInvalidMeshIndex = std::numeric_limits<size_t>::max();
 
 void LogError(const char* what, const char* detail) { std::fprintf(stderr, "[Trident] %s: %s\n", what, detail); }
+
+std::string DefaultDatasetDirectory() {  // current_path()/DatasetCapture (Renderer.cpp:551, :2508-2511)
+    std::error_code ec;
+    const std::filesystem::path cwd = std::filesystem::current_path(ec);
+    return ((ec ? std::filesystem::path(".") : cwd) / "DatasetCapture").string();
+}
 
 Geometry::Mesh BuildPrimitiveQuadMesh() {
     Geometry::Mesh mesh;
@@ -211,6 +219,18 @@ void Renderer::Init() {
     m_TextureSlotLookup.emplace(kDefaultTextureKey, 0u);
     m_PerformanceHistory.assign(s_PerformanceHistorySize, FrameTimingSample{});
     CreateSkyboxCubemap();  // CreateDefaultSkybox (Renderer.cpp:3806-3816)
+    // dataset capture starts disabled at the default directory; the environment can enable it (Renderer.cpp:551-576)
+    m_FrameDatasetCaptureDirectory = DefaultDatasetDirectory();
+    m_FrameDatasetCaptureInterval = 1;
+    const char* enableCapture = std::getenv("TRIDENT_DATASET_CAPTURE_ENABLE");
+    if (enableCapture && *enableCapture) {
+        const char* directory = std::getenv("TRIDENT_DATASET_CAPTURE_DIR");
+        if (directory && *directory) SetFrameDatasetCaptureDirectory(directory);
+        SetFrameDatasetCaptureEnabled(true);
+        LogError("frame dataset capture enabled, writing samples to", m_FrameDatasetCaptureDirectory.c_str());
+    } else {
+        SetFrameDatasetCaptureEnabled(false);
+    }
     m_Initialised = true;
     m_Shutdown = false;
 }
@@ -219,6 +239,7 @@ void Renderer::DestroyViewportTargets() {
     m_Pending.clear();  // (its targets go; tri_destroy / tri_group_destroy wait for their streams)
     tri_recorder_destroy(m_Recorder);  // (waits for its captures; the next recorded DrawFrame makes a new one)
     m_Recorder = nullptr;
+    DropGrab();  // (likewise; the next captured DrawFrame makes a new one)
     auto drop = [](ViewportContext& vc) {
         tri_destroy(vc.m_Ctx);
         tri_group_destroy(vc.m_Group);
@@ -250,6 +271,8 @@ void Renderer::DestroyViewportTargets() {
 void Renderer::Shutdown() {
     StopRecording();  // the frames in flight reach the file, which is finalised
     DestroyViewportTargets();
+    m_FrameDatasetRecorder.Flush();  // every queued sample is on disk
+    m_PendingFrameReadback.clear();
     m_Viewports.clear();
     if (m_Initialised) m_Shutdown = true;
     m_Initialised = false;
@@ -307,6 +330,10 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         } else {
             FinishFrame();
         }
+    }
+    if (m_AiReadback && devs.size() > 1) {
+        LogError("SetDeviceCount", "multi-device viewports have no AI readback: it was turned off");
+        SetAiReadbackEnabled(false);
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
@@ -1047,6 +1074,9 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     const uint32_t inflight = m_Devices.size() > 1 ? 1u : m_FramesInFlight;
     while (m_Pending.size() >= inflight) FinishOldestFrame();
     const uint32_t tix = (uint32_t)(m_FrameCount++ % inflight);
+    // the device tensor handed out by GetFrameReadbackDeviceTensor was valid until here: its slot serves again (an
+    // unconsumed pending tensor moves from the slot's pinned buffer into host memory first)
+    ReleaseHeldReadbackSlot(true);
     GatherDraws();
     PrepareBonePaletteBuffer();
     std::vector<tri_draw> draws;
@@ -1059,6 +1089,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     // (Renderer.cpp:5208-5221), so the uniform block left bound is the primary viewport's
     ViewportContext* activeTarget = nullptr;
     ViewportContext* recorded = nullptr;
+    ViewportContext* grabbed = nullptr;
     auto pass = [&](uint32_t id, ViewportContext& primary) {
         ViewportContext& vc = TargetOf(id, primary, tix);  // this frame's target of the viewport
         if (!PrepareViewport(vc)) return;
@@ -1067,6 +1098,16 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         if (!SubmitTarget(vc, ubo, draws, shadow, shadowOn)) return;
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
+        // AI readback: the active viewport's tensor, likewise, when the readback throttle has elapsed (ResolvePending-
+        // Readback's interval, Renderer.cpp:1111-1140) and the viewport has the present extent (:5301-5337)
+        if (m_AiReadback && id == m_ActiveViewportId && vc.m_Ctx &&
+            !(m_PresentWidth && m_PresentHeight && (m_PresentWidth != vc.m_Width || m_PresentHeight != vc.m_Height))) {
+            const auto now = std::chrono::steady_clock::now();
+            if (now >= m_NextAiReadbackTime && CaptureReadbackFrame(vc, tix)) {
+                m_NextAiReadbackTime = now + m_AiReadbackInterval;
+                grabbed = &vc;
+            }
+        }
         lastUbo = ubo;
         submitted.push_back(&vc);
         m_LatestTarget[id] = tix;
@@ -1100,6 +1141,8 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     pf.m_Legacy = legacy;
     pf.m_Recorded = recorded;
     pf.m_RecordSlot = tix;
+    pf.m_Grabbed = grabbed;
+    pf.m_GrabGeneration = m_GrabGeneration;
     if (primaryActive && m_PresentWidth && m_PresentHeight) {
         const Target t{activeTarget->m_Ctx, activeTarget->m_Group};
         if (t.Blit(m_PresentWidth, m_PresentHeight) == TRI_OK) {
@@ -1164,6 +1207,8 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
                 LogError("recording", "the encoder refused a frame");
             if (tri_recorder_release(m_Recorder, p.m_RecordSlot) != TRI_OK) LogError("recording", tri_last_error());
         }
+        if (vc == p.m_Grabbed && m_Grab && p.m_GrabGeneration == m_GrabGeneration)
+            ResolveReadbackFrame(*vc, p.m_RecordSlot, rc == TRI_OK, rerendered);
         if (vc == p.m_Blit && rc != TRI_OK) p.m_Blit = nullptr;
         if (vc == p.m_Blit && rerendered) {  // (the first wait covered the blit behind the pass: same stream)
             if (t.Blit(p.m_BlitWidth, p.m_BlitHeight) != TRI_OK || t.Sync() != TRI_OK) {
@@ -1246,6 +1291,221 @@ bool Renderer::CaptureRecordedFrame(ViewportContext& vc, uint32_t slot) {
         return false;
     }
     return true;
+}
+
+// ---- AI readback and dataset capture ---------------------------------------------------------------------------
+
+namespace {
+
+// ParseTensorShapeNhwc + BuildCanonicalNhwcShape (Renderer.cpp:269-327): {1, H, W, C} of a rank-3 (HWC) or rank-4
+// (NHWC) shape, a dimension <= 0 (dynamic) replaced by the fallback.
+bool CanonicalNhwcShape(const int64_t* shape, size_t rank, uint32_t fallbackWidth, uint32_t fallbackHeight,
+                        uint32_t fallbackChannels, int64_t (&out)[4]) {
+    if (!shape || (rank != 3 && rank != 4)) return false;
+    const int64_t* hwc = shape + (rank == 4 ? 1 : 0);
+    auto resolve = [](int64_t v, int64_t fallback) { return std::max<int64_t>(v <= 0 ? fallback : v, 0); };
+    out[0] = 1;
+    out[1] = resolve(hwc[0], (int64_t)fallbackHeight);
+    out[2] = resolve(hwc[1], (int64_t)fallbackWidth);
+    out[3] = resolve(hwc[2], (int64_t)fallbackChannels);
+    return true;
+}
+
+}  // namespace
+
+// Renderer.cpp:358-415, in its order: scale, swap, clamp.
+void Renderer::NormaliseAndReorderAiOutput(std::vector<float>& data, int64_t channels) {
+    if (data.empty()) return;
+    if (channels <= 0) {
+        LogError("AI output", "invalid channel count");
+        return;
+    }
+    const size_t ch = (size_t)channels;
+    if (data.size() % ch != 0) {
+        LogError("AI output", "the element count is no multiple of the channel count");
+        return;
+    }
+    const auto mm = std::minmax_element(data.begin(), data.end());
+    const float lo = *mm.first, hi = *mm.second;
+    constexpr float kTolerance = 1.0e-3f;
+    if (hi > 1.0f + kTolerance || lo < -kTolerance) {
+        const float scale = 1.0f / 255.0f;
+        for (float& v : data) v *= scale;
+    }
+    if (ch >= 3)
+        for (size_t p = 0; p < data.size(); p += ch) std::swap(data[p], data[p + 2]);
+    for (float& v : data) v = std::min(std::max(v, 0.0f), 1.0f);
+}
+
+bool Renderer::SetAiReadbackEnabled(bool enabled) {
+    if (enabled && m_Devices.size() > 1) {
+        LogError("AI readback", "multi-device viewports (SetDeviceCount > 1) have no AI readback");
+        return false;
+    }
+    if (enabled == m_AiReadback) return true;
+    if (!enabled) {  // the captures in flight are dropped with the grab
+        FinishFrame();
+        DropGrab();
+        m_PendingFrameReadback.clear();
+    }
+    m_AiReadback = enabled;
+    return true;
+}
+
+void Renderer::SetAiThrottleIntervals(uint32_t readbackMs, uint32_t inferenceMs) {
+    m_AiReadbackInterval = std::chrono::milliseconds(readbackMs);
+    m_AiInferenceInterval = std::chrono::milliseconds(inferenceMs);
+    m_NextAiReadbackTime = m_NextAiInferenceTime = std::chrono::steady_clock::time_point{};  // both elapse at once
+}
+
+void Renderer::DropGrab() {
+    ReleaseHeldReadbackSlot(true);
+    tri_framegrab_destroy(m_Grab);  // (waits for its captures)
+    m_Grab = nullptr;
+    ++m_GrabGeneration;
+}
+
+// The slot that holds the latest resolved tensor goes back to the grab. While it was held, the pending readback lived
+// in its pinned buffer (no copy unless it is needed): `keepPending` copies an unconsumed one into m_PendingFrameReadback.
+void Renderer::ReleaseHeldReadbackSlot(bool keepPending) {
+    if (m_PendingInSlot && keepPending && m_GrabHostTensor)
+        m_PendingFrameReadback.assign(m_GrabHostTensor, m_GrabHostTensor + FrameReadbackCount());
+    m_PendingInSlot = false;
+    if (m_Grab && m_GrabHeldSlot >= 0 && tri_framegrab_release(m_Grab, (uint32_t)m_GrabHeldSlot) != TRI_OK)
+        LogError("AI readback", tri_last_error());
+    m_GrabHeldSlot = -1;
+    m_GrabDeviceTensor = nullptr;
+    m_GrabHostTensor = nullptr;
+}
+
+// The active viewport's frame -> grab slot `slot` (asynchronous). The grab is made here, once the target exists: one
+// slot per frame in flight, on the target's device, with pinned host copies; a target of another extent (the viewport
+// was resized) gets a new grab.
+bool Renderer::CaptureReadbackFrame(ViewportContext& vc, uint32_t slot) {
+    if (!vc.m_Ctx || !vc.m_HasImage) return false;
+    if (m_Grab && (m_GrabWidth != vc.m_Width || m_GrabHeight != vc.m_Height)) DropGrab();
+    if (!m_Grab) {  // (SetFramesInFlight drops it with the targets, so its slots always match)
+        if (tri_framegrab_create(vc.m_Image.device, vc.m_Width, vc.m_Height, m_FramesInFlight, TRI_GRAB_HOST_COPY,
+                                 &m_Grab) != TRI_OK) {
+            LogError("AI readback", tri_last_error());
+            m_Grab = nullptr;
+            return false;
+        }
+        m_GrabWidth = vc.m_Width;
+        m_GrabHeight = vc.m_Height;
+    }
+    if (tri_framegrab_capture(m_Grab, slot, vc.m_Ctx) != TRI_OK) {
+        LogError("AI readback", tri_last_error());
+        return false;
+    }
+    return true;
+}
+
+// After the frame's fence: the slot's floats become the pending readback (a newer frame replaces an unconsumed one),
+// and the slot stays busy until the next DrawFrame, so that its device tensor can be handed out and its pinned buffer
+// can serve TryAcquireRenderedFrame without a copy in between.
+void Renderer::ResolveReadbackFrame(ViewportContext& vc, uint32_t slot, bool ok, bool rerendered) {
+    // a re-rendered frame was captured incomplete: convert it again
+    if (ok && rerendered) ok = tri_framegrab_release(m_Grab, slot) == TRI_OK && CaptureReadbackFrame(vc, slot);
+    const float* host = nullptr;
+    const float* device = nullptr;
+    if (ok && tri_framegrab_wait(m_Grab, slot, &host, &device) != TRI_OK) {
+        LogError("AI readback", tri_last_error());
+        ok = false;
+    }
+    if (!ok) {  // the tensor pending so far stays
+        if (tri_framegrab_release(m_Grab, slot) != TRI_OK) LogError("AI readback", tri_last_error());
+        return;
+    }
+    ReleaseHeldReadbackSlot(false);  // (an older frame's slot: this frame replaces what it held)
+    m_PendingFrameReadback.clear();
+    m_FrameReadbackWidth = m_GrabWidth;
+    m_FrameReadbackHeight = m_GrabHeight;
+    m_GrabHeldSlot = (int32_t)slot;
+    m_GrabDeviceTensor = device;
+    m_GrabHostTensor = host;
+    m_PendingInSlot = true;
+}
+
+bool Renderer::TryAcquireRenderedFrame(std::vector<float>& out) {
+    if (!m_PendingInSlot && m_PendingFrameReadback.empty()) {
+        AiInferenceThrottleElapsed();  // (the reference arms the throttle before it looks for a frame, :933-943)
+        return false;
+    }
+    out.resize(FrameReadbackCount());  // (a vector the caller reuses is not allocated again)
+    return TryAcquireRenderedFrame(out.data(), out.size());
+}
+
+bool Renderer::AiInferenceThrottleElapsed() {  // Renderer.cpp:933-940
+    const auto now = std::chrono::steady_clock::now();
+    if (now < m_NextAiInferenceTime) return false;
+    m_NextAiInferenceTime = now + m_AiInferenceInterval;
+    return true;
+}
+
+bool Renderer::TryAcquireRenderedFrame(float* out, size_t capacity) {
+    const size_t n = FrameReadbackCount();
+    const bool pending = m_PendingInSlot || !m_PendingFrameReadback.empty();
+    if (pending && (!out || capacity < n)) return false;  // (it stays pending, and the throttle is not armed)
+    if (!AiInferenceThrottleElapsed() || !pending) return false;
+    std::memcpy(out, m_PendingInSlot ? m_GrabHostTensor : m_PendingFrameReadback.data(), n * sizeof(float));
+    m_PendingInSlot = false;
+    m_PendingFrameReadback.clear();
+    if (m_FrameDatasetCaptureEnabled) {  // the exact tensor the generator gets (:973-977)
+        const int64_t shape[4] = {1, (int64_t)m_FrameReadbackHeight, (int64_t)m_FrameReadbackWidth,
+                                  (int64_t)s_FrameReadbackChannelCount};
+        m_FrameDatasetRecorder.RecordInputFrame(out, n, m_FrameReadbackWidth, m_FrameReadbackHeight,
+                                                s_FrameReadbackChannelCount, shape, 4);
+    }
+    return true;
+}
+
+bool Renderer::GetFrameReadbackDeviceTensor(const float** device, uint32_t& width, uint32_t& height) {
+    FinishFrame();  // (on demand, as the other readers: the latest frame's capture is resolved)
+    if (!device || !m_Grab || m_GrabHeldSlot < 0 || !m_GrabDeviceTensor) return false;
+    *device = m_GrabDeviceTensor;
+    width = m_GrabWidth;
+    height = m_GrabHeight;
+    return true;
+}
+
+bool Renderer::SubmitAiOutput(const float* data, size_t count, const int64_t* shape, size_t rank) {
+    int64_t canonical[4];
+    if (!CanonicalNhwcShape(shape, rank, m_FrameReadbackWidth, m_FrameReadbackHeight, s_FrameReadbackChannelCount, canonical)) {
+        LogError("AI output", "the tensor must be channels-last: [height, width, channels] or [1, height, width, channels]");
+        return false;
+    }
+    if (!data || count == 0) return false;  // (TryConsumeOutput's empty output, Renderer.cpp:915)
+    std::vector<float> output(data, data + count);
+    NormaliseAndReorderAiOutput(output, canonical[3]);
+    if (m_FrameDatasetCaptureEnabled) m_FrameDatasetRecorder.RecordAiOutput(output.data(), output.size(), canonical, 4);
+    if ((uint64_t)canonical[1] * (uint64_t)canonical[2] * (uint64_t)canonical[3] != (uint64_t)count ||
+        canonical[1] > (int64_t)UINT32_MAX || canonical[2] > (int64_t)UINT32_MAX || canonical[3] > (int64_t)UINT32_MAX) {
+        LogError("AI output", "the element count does not match the shape: the blend frame is unchanged");
+        return false;
+    }
+    return SubmitAiInterpolation(output.data(), (uint32_t)canonical[2], (uint32_t)canonical[1], (uint32_t)canonical[3]);
+}
+
+void Renderer::SetFrameDatasetCaptureEnabled(bool enabled) {
+    m_FrameDatasetCaptureEnabled = enabled;
+    SyncFrameDatasetRecorder();
+}
+
+void Renderer::SetFrameDatasetCaptureDirectory(const std::string& directory) {
+    m_FrameDatasetCaptureDirectory = directory.empty() ? DefaultDatasetDirectory() : directory;
+    SyncFrameDatasetRecorder();
+}
+
+void Renderer::SetFrameDatasetCaptureInterval(uint32_t interval) {
+    m_FrameDatasetCaptureInterval = std::max<uint32_t>(1u, interval);
+    m_FrameDatasetRecorder.SetSampleInterval(m_FrameDatasetCaptureInterval);
+}
+
+void Renderer::SyncFrameDatasetRecorder() {  // Renderer.cpp:6393-6398
+    m_FrameDatasetRecorder.SetCaptureDirectory(m_FrameDatasetCaptureDirectory);
+    m_FrameDatasetRecorder.SetSampleInterval(m_FrameDatasetCaptureInterval);
+    m_FrameDatasetRecorder.EnableCapture(m_FrameDatasetCaptureEnabled);
 }
 
 void Renderer::RecordFrameTiming(double ms) {  // Renderer.cpp:6286-6343

@@ -38,6 +38,17 @@ int Guard(trident_app* app, F&& f) {
     }
 }
 
+template <typename F>
+int GuardDataset(trident_dataset* dataset, F&& f) {
+    if (!dataset) return TRI_E_INVALID;
+    try {
+        f();
+        return TRI_OK;
+    } catch (const std::exception&) {
+        return TRI_E_INVALID;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -617,6 +628,152 @@ int trident_video_convert_rgba(const uint8_t* rgba, uint64_t pixels, uint8_t* yu
     if (pixels && (!rgba || !yuv)) return TRI_E_INVALID;
     VideoEncoder::ConvertRgbaToYuv444(rgba, pixels, yuv);
     return TRI_OK;
+}
+
+int trident_app_set_dataset_capture(trident_app* app, int enabled, const char* directory, uint32_t interval) {
+    return Guard(app, [&] {
+        if (directory) app->renderer.SetFrameDatasetCaptureDirectory(directory);
+        if (interval) app->renderer.SetFrameDatasetCaptureInterval(interval);
+        app->renderer.SetFrameDatasetCaptureEnabled(enabled != 0);
+        return TRI_OK;
+    });
+}
+
+int trident_app_dataset_capture_state(trident_app* app, int* enabled, uint32_t* interval, char* directory, uint32_t capacity) {
+    return Guard(app, [&] {
+        if (enabled) *enabled = app->renderer.IsFrameDatasetCaptureEnabled() ? 1 : 0;
+        if (interval) *interval = app->renderer.GetFrameDatasetCaptureInterval();
+        if (directory) {
+            const std::string& d = app->renderer.GetFrameDatasetCaptureDirectory();
+            if (d.size() + 1 > capacity) return TRI_E_INVALID;
+            std::memcpy(directory, d.c_str(), d.size() + 1);
+        }
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_ai_readback(trident_app* app, int enabled, uint32_t readback_ms, uint32_t inference_ms) {
+    return Guard(app, [&] {
+        app->renderer.SetAiThrottleIntervals(readback_ms, inference_ms);
+        return app->renderer.SetAiReadbackEnabled(enabled != 0) ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_app_ai_readback_state(trident_app* app, int* enabled) {
+    return Guard(app, [&] {
+        if (enabled) *enabled = app->renderer.IsAiReadbackEnabled() ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_acquire_frame(trident_app* app, float* out, uint64_t capacity, uint32_t* width, uint32_t* height, int* got) {
+    return Guard(app, [&] {
+        if (!got) return TRI_E_INVALID;
+        *got = 0;
+        uint32_t w = 0, h = 0;
+        app->renderer.GetFrameReadbackExtent(w, h);
+        if (width) *width = w;
+        if (height) *height = h;
+        // (checked before the acquisition: a tensor that does not fit stays pending)
+        if (!out || capacity < (uint64_t)w * h * 4u) return w && h ? TRI_E_INVALID : TRI_OK;
+        *got = app->renderer.TryAcquireRenderedFrame(out, (size_t)capacity) ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_readback_device_tensor(trident_app* app, const float** device, uint32_t* width, uint32_t* height, int* got) {
+    return Guard(app, [&] {
+        if (!device || !got) return TRI_E_INVALID;
+        uint32_t w = 0, h = 0;
+        *device = nullptr;
+        *got = app->renderer.GetFrameReadbackDeviceTensor(device, w, h) ? 1 : 0;
+        if (width) *width = w;
+        if (height) *height = h;
+        return TRI_OK;
+    });
+}
+
+int trident_app_submit_ai_output(trident_app* app, const float* data, uint64_t count, const int64_t* shape, uint32_t rank) {
+    return Guard(app, [&] { return app->renderer.SubmitAiOutput(data, (size_t)count, shape, rank) ? TRI_OK : TRI_E_STATE; });
+}
+
+int trident_ai_normalise_output(float* data, uint64_t count, int64_t channels) {
+    if (count && !data) return TRI_E_INVALID;
+    try {
+        std::vector<float> v(data, data + count);
+        Renderer::NormaliseAndReorderAiOutput(v, channels);
+        if (count) std::memcpy(data, v.data(), count * sizeof(float));
+        return TRI_OK;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+struct trident_dataset {
+    FrameDatasetRecorder recorder;
+};
+
+int trident_dataset_create(trident_dataset** out) {
+    if (!out) return TRI_E_INVALID;
+    *out = nullptr;
+    try {
+        *out = new trident_dataset();
+        return TRI_OK;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+void trident_dataset_destroy(trident_dataset* dataset) { delete dataset; }
+
+int trident_dataset_set_directory(trident_dataset* dataset, const char* directory) {
+    return GuardDataset(dataset, [&] { dataset->recorder.SetCaptureDirectory(directory ? directory : ""); });
+}
+
+int trident_dataset_set_interval(trident_dataset* dataset, uint32_t interval) {
+    return GuardDataset(dataset, [&] { dataset->recorder.SetSampleInterval(interval); });
+}
+
+int trident_dataset_enable(trident_dataset* dataset, int enabled) {
+    return GuardDataset(dataset, [&] { dataset->recorder.EnableCapture(enabled != 0); });
+}
+
+int trident_dataset_reset(trident_dataset* dataset) {
+    return GuardDataset(dataset, [&] { dataset->recorder.Reset(); });
+}
+
+int trident_dataset_record_input(trident_dataset* dataset, const float* data, uint64_t count, uint32_t width, uint32_t height,
+                                 uint32_t channels, const int64_t* shape, uint32_t rank) {
+    return GuardDataset(dataset, [&] {
+        dataset->recorder.RecordInputFrame(data, (size_t)count, width, height, channels, shape, rank);
+    });
+}
+
+int trident_dataset_record_output(trident_dataset* dataset, const float* data, uint64_t count, const int64_t* shape,
+                                  uint32_t rank) {
+    return GuardDataset(dataset, [&] { dataset->recorder.RecordAiOutput(data, (size_t)count, shape, rank); });
+}
+
+int trident_dataset_flush(trident_dataset* dataset) {
+    return GuardDataset(dataset, [&] { dataset->recorder.Flush(); });
+}
+
+int trident_dataset_state(trident_dataset* dataset, int* enabled, uint32_t* interval, uint64_t* next_index, uint64_t* pending) {
+    if (!dataset) return TRI_E_INVALID;
+    if (enabled) *enabled = dataset->recorder.IsCaptureEnabled() ? 1 : 0;
+    if (interval) *interval = dataset->recorder.GetSampleInterval();
+    if (next_index) *next_index = dataset->recorder.GetNextSampleIndex();
+    if (pending) *pending = dataset->recorder.GetPendingSampleCount();
+    return TRI_OK;
+}
+
+int trident_dataset_write_npy(const char* path, const float* data, uint64_t count, const int64_t* shape, uint32_t rank) {
+    if (!path) return TRI_E_INVALID;
+    try {
+        return FrameDatasetRecorder::WriteNpyFile(path, data, (size_t)count, shape, rank) ? TRI_OK : TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_INVALID;
+    }
 }
 
 int trident_app_finish_frame(trident_app* app) {

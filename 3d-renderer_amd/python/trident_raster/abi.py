@@ -204,6 +204,7 @@ TRI_GROUP_NO_PACK = 0x1
 TRI_GROUP_STAGE_BANDS = 0x2
 TRI_GROUP_PACK_BGR24 = 0x4
 TRI_XFER_ID_BYTES = 128
+TRI_GRAB_HOST_COPY = 0x1  # tri_framegrab_create
 
 
 class TriXferConfig(C.Structure):
@@ -267,6 +268,12 @@ CABI_FUNCTIONS = [
     ("tri_recorder_capture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("tri_recorder_wait", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("tri_recorder_release", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("tri_convert_rgba_f32", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("tri_framegrab_create", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_framegrab_destroy", C.c_int, [C.c_void_p]),
+    ("tri_framegrab_capture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("tri_framegrab_wait", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    ("tri_framegrab_release", C.c_int, [C.c_void_p, C.c_uint32]),
     ("tri_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("tri_get_timing", C.c_int, [C.c_void_p, C.POINTER(TriTiming)]),
     ("tri_get_frame_stats", C.c_int, [C.c_void_p, C.POINTER(TriFrameStats)]),

@@ -82,6 +82,30 @@ _APP_FUNCTIONS = [
     ("trident_video_end", C.c_int, [C.c_void_p]),
     ("trident_video_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     ("trident_video_convert_rgba", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("trident_app_set_dataset_capture", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_uint32]),
+    ("trident_app_dataset_capture_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.c_char_p,
+                                                    C.c_uint32]),
+    ("trident_app_set_ai_readback", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32]),
+    ("trident_app_ai_readback_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("trident_app_acquire_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    ("trident_app_readback_device_tensor", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32),
+                                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    ("trident_app_submit_ai_output", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32]),
+    ("trident_ai_normalise_output", C.c_int, [C.c_void_p, C.c_uint64, C.c_int64]),
+    ("trident_dataset_create", C.c_int, [C.POINTER(C.c_void_p)]),
+    ("trident_dataset_destroy", None, [C.c_void_p]),
+    ("trident_dataset_set_directory", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("trident_dataset_set_interval", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("trident_dataset_enable", C.c_int, [C.c_void_p, C.c_int]),
+    ("trident_dataset_reset", C.c_int, [C.c_void_p]),
+    ("trident_dataset_record_input", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.POINTER(C.c_int64), C.c_uint32]),
+    ("trident_dataset_record_output", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32]),
+    ("trident_dataset_flush", C.c_int, [C.c_void_p]),
+    ("trident_dataset_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64)]),
+    ("trident_dataset_write_npy", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32]),
 ]
 
 _lib = None
@@ -367,6 +391,69 @@ class TridentApp:
         _check(self._lib.trident_app_read_present(self._h, out.ctypes.data, width, height), "read_present")
         return out
 
+    # ---- AI readback and dataset capture (the frame generator itself lives outside) ----
+    def set_dataset_capture(self, enabled, directory=None, interval=0):
+        """Renderer::SetFrameDatasetCaptureDirectory (unless None) / ...Interval (unless 0) / ...Enabled. Disabling
+        returns once the queued samples are on disk."""
+        _check(self._lib.trident_app_set_dataset_capture(self._h, 1 if enabled else 0,
+                                                         os.fsencode(directory) if directory is not None else None,
+                                                         interval), "set_dataset_capture")
+
+    def dataset_capture_state(self):
+        """(IsFrameDatasetCaptureEnabled, GetFrameDatasetCaptureDirectory, GetFrameDatasetCaptureInterval)."""
+        en, iv, buf = C.c_int(), C.c_uint32(), C.create_string_buffer(4096)
+        _check(self._lib.trident_app_dataset_capture_state(self._h, C.byref(en), C.byref(iv), buf, len(buf)),
+               "dataset_capture_state")
+        return bool(en.value), os.fsdecode(buf.value), iv.value
+
+    def set_ai_readback(self, enabled, readback_ms=66, inference_ms=66):
+        """Renderer::SetAiThrottleIntervals + SetAiReadbackEnabled -> accepted (False while SetDeviceCount > 1)."""
+        rc = self._lib.trident_app_set_ai_readback(self._h, 1 if enabled else 0, readback_ms, inference_ms)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_ai_readback")
+        return rc == abi.TRI_OK
+
+    def ai_readback_enabled(self):
+        en = C.c_int()
+        _check(self._lib.trident_app_ai_readback_state(self._h, C.byref(en)), "ai_readback_state")
+        return bool(en.value)
+
+    def acquire_frame(self, out=None):
+        """Renderer::TryAcquireRenderedFrame: float32 [h, w, 4] (R, G, B, A), or None when nothing is pending (or the
+        inference throttle has not elapsed). `out`: a C-contiguous float32 array of at least h * w * 4 elements to
+        fill instead of a new one (its first h * w * 4 elements are returned, shaped)."""
+        w, h, got = C.c_uint32(), C.c_uint32(), C.c_int()
+        # (a call without a buffer only reports the extent to size for; the tensor stays pending)
+        rc = self._lib.trident_app_acquire_frame(self._h, None, 0, C.byref(w), C.byref(h), C.byref(got))
+        if not (w.value and h.value):
+            _check(rc, "acquire_frame")
+            return None
+        n = h.value * w.value * 4
+        if out is None:
+            out = np.empty(n, np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < n:
+            raise ValueError("acquire_frame: out must be C-contiguous float32 with at least h * w * 4 elements")
+        _check(self._lib.trident_app_acquire_frame(self._h, out.ctypes.data, out.size, C.byref(w), C.byref(h),
+                                                   C.byref(got)), "acquire_frame")
+        return out.reshape(-1)[:n].reshape(h.value, w.value, 4) if got.value else None
+
+    def readback_device_tensor(self):
+        """Renderer::GetFrameReadbackDeviceTensor: (device pointer, width, height) of the latest tensor, valid until
+        the next draw_frame, or None."""
+        p, w, h, got = C.c_void_p(), C.c_uint32(), C.c_uint32(), C.c_int()
+        _check(self._lib.trident_app_readback_device_tensor(self._h, C.byref(p), C.byref(w), C.byref(h), C.byref(got)),
+               "readback_device_tensor")
+        return (p.value, w.value, h.value) if got.value else None
+
+    def submit_ai_output(self, data, shape):
+        """Renderer::SubmitAiOutput: the generator's output (any float array) with its tensor shape -> accepted."""
+        a = np.ascontiguousarray(data, np.float32)
+        sh = (C.c_int64 * len(shape))(*[int(x) for x in shape]) if len(shape) else None
+        rc = self._lib.trident_app_submit_ai_output(self._h, a.ctypes.data if a.size else None, a.size, sh, len(shape))
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "submit_ai_output")
+        return rc == abi.TRI_OK
+
 
 class VideoEncoder:
     """Trident::VideoEncoder on its own (Y4M sessions on the host); every method returns the encoder's bool."""
@@ -417,6 +504,85 @@ class VideoEncoder:
         act, frames = C.c_int(), C.c_uint64()
         _check(self._lib.trident_video_state(self._h, C.byref(act), C.byref(frames)), "video_state")
         return bool(act.value), frames.value
+
+
+class DatasetRecorder:
+    """Trident::FrameDatasetRecorder on its own (no app, no device)."""
+
+    def __init__(self):
+        self._lib = load_library()
+        h = C.c_void_p()
+        _check(self._lib.trident_dataset_create(C.byref(h)), "trident_dataset_create")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            self._lib.trident_dataset_destroy(self._h)  # (writes what is queued)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _shape(shape):
+        shape = [] if shape is None else [int(x) for x in shape]
+        return ((C.c_int64 * len(shape))(*shape) if shape else None), len(shape)
+
+    def set_directory(self, directory):
+        _check(self._lib.trident_dataset_set_directory(self._h, os.fsencode(directory)), "dataset_set_directory")
+
+    def set_interval(self, interval):
+        _check(self._lib.trident_dataset_set_interval(self._h, interval), "dataset_set_interval")
+
+    def enable(self, enabled):
+        _check(self._lib.trident_dataset_enable(self._h, 1 if enabled else 0), "dataset_enable")
+
+    def reset(self):
+        _check(self._lib.trident_dataset_reset(self._h), "dataset_reset")
+
+    def record_input(self, data, width, height, channels, shape=None):
+        a = np.ascontiguousarray(data, np.float32)
+        sh, rank = self._shape(shape)
+        _check(self._lib.trident_dataset_record_input(self._h, a.ctypes.data if a.size else None, a.size, width, height,
+                                                      channels, sh, rank), "dataset_record_input")
+
+    def record_output(self, data, shape=None):
+        a = np.ascontiguousarray(data, np.float32)
+        sh, rank = self._shape(shape)
+        _check(self._lib.trident_dataset_record_output(self._h, a.ctypes.data if a.size else None, a.size, sh, rank),
+               "dataset_record_output")
+
+    def flush(self):
+        _check(self._lib.trident_dataset_flush(self._h), "dataset_flush")
+
+    def state(self):
+        """(enabled, interval, next sample index, inputs waiting for an output)."""
+        en, iv, nxt, pend = C.c_int(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(self._lib.trident_dataset_state(self._h, C.byref(en), C.byref(iv), C.byref(nxt), C.byref(pend)),
+               "dataset_state")
+        return bool(en.value), iv.value, nxt.value, pend.value
+
+
+def write_npy(path, data, shape):
+    """FrameDatasetRecorder::WriteNpyFile alone -> written (False: refused, no file)."""
+    lib = load_library()
+    a = np.ascontiguousarray(data, np.float32)
+    sh, rank = DatasetRecorder._shape(shape)
+    rc = lib.trident_dataset_write_npy(os.fsencode(path), a.ctypes.data if a.size else None, a.size, sh, rank)
+    if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+        _check(rc, "dataset_write_npy")
+    return rc == abi.TRI_OK
+
+
+def normalise_ai_output(data, channels):
+    """Renderer::NormaliseAndReorderAiOutput on a copy: float32, flat."""
+    lib = load_library()
+    a = np.array(data, np.float32).reshape(-1)
+    _check(lib.trident_ai_normalise_output(a.ctypes.data if a.size else None, a.size, channels), "ai_normalise_output")
+    return a
 
 
 def convert_rgba(rgba):

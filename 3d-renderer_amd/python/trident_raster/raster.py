@@ -357,6 +357,64 @@ class TriRecorder:
         _check(_lib.tri_recorder_release(self._r, slot))
 
 
+def convert_rgba_f32(src_ptr, width, height, pitch_bytes, dst_ptr, stream_ptr=None):
+    """tri_convert_rgba_f32: B8G8R8A8 rows (pitch_bytes apart) -> width * height * 4 float32 (R, G, B, A per pixel,
+    byte * (1 / 255) in float32) on the device, stream-ordered."""
+    load_library()
+    _check(_lib.tri_convert_rgba_f32(C.c_void_p(src_ptr) if src_ptr else None, width, height, pitch_bytes,
+                                     C.c_void_p(dst_ptr) if dst_ptr else None, C.c_void_p(stream_ptr) if stream_ptr else None))
+
+
+class FrameGrab:
+    """tri_framegrab: `slots` device float32 RGBA tensors of one extent (pinned host copies too with host_copy);
+    capture is asynchronous."""
+
+    def __init__(self, width, height, slots, device=-1, host_copy=False):
+        lib = load_library()
+        g = C.c_void_p()
+        _check(lib.tri_framegrab_create(device, width, height, slots, abi.TRI_GRAB_HOST_COPY if host_copy else 0, C.byref(g)))
+        self._g = g
+        self.width, self.height, self.slots, self.host_copy = width, height, slots, host_copy
+
+    def close(self):
+        if self._g:
+            _lib.tri_framegrab_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def capture(self, slot, raster):
+        _check(_lib.tri_framegrab_capture(self._g, slot, raster._ctx))
+
+    def wait_pointers(self, slot, host=True, device=True):
+        """(pinned pointer or None, device pointer or None) of the slot, after the events they depend on."""
+        h, d = C.c_void_p(), C.c_void_p()
+        _check(_lib.tri_framegrab_wait(self._g, slot, C.byref(h) if host else None, C.byref(d) if device else None))
+        return (h.value if host else None), (d.value if device else None)
+
+    def wait(self, slot):
+        """(the pinned tensor, float32 [height, width, 4], or None without host_copy; the device pointer). Both are
+        valid until release."""
+        h, d = self.wait_pointers(slot, host=self.host_copy)
+        if h is None:
+            return None, d
+        buf = (C.c_float * (4 * self.width * self.height)).from_address(h)
+        return np.frombuffer(buf, np.float32).reshape(self.height, self.width, 4), d
+
+    def release(self, slot):
+        _check(_lib.tri_framegrab_release(self._g, slot))
+
+
 def copy_device_to_host(ptr, nbytes, device=0):
     """hipMemcpy of `nbytes` at a device pointer (a tri_image handle) into a numpy byte array."""
     hip = C.CDLL("libamdhip64.so")

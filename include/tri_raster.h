@@ -380,6 +380,46 @@ int tri_recorder_capture(tri_recorder* recorder, uint32_t slot, tri_ctx* ctx);
 int tri_recorder_wait(tri_recorder* recorder, uint32_t slot, const uint8_t** yuv);
 int tri_recorder_release(tri_recorder* recorder, uint32_t slot);
 
+/* ---- frame tensors for AI consumers (Renderer::SetReadbackEnabled / ResolvePendingReadback /
+ * TryAcquireRenderedFrame, Renderer.cpp:984-995, :1111-1389) ----
+ * The reference reads the primary viewport back and builds the frame generator's input on the host; here the
+ * conversion runs on the device behind the frame, and the tensor can stay there for a consumer on the same device.
+ * tri_convert_rgba_f32: B8G8R8A8 (device pointer, 4-B aligned, rows pitch_bytes apart: a multiple of 4, at least
+ * width * 4) -> width * height * 4 floats, tightly packed, at a 4-B aligned device pointer (16-B aligned is faster):
+ * channels-last, R, G, B, A per pixel (memory bytes 2, 1, 0, 3 of the source pixel), rows top to bottom. Every value
+ * is exactly (float)byte * (1.0f / 255.0f): one float32 multiply by the constant 0x3B808081, not a division
+ * (255 gives exactly 1.0f). Stream-ordered on hip_stream (NULL = the null stream). Bytes beyond `width` in a pitched
+ * row are not read. Errors as tri_convert_yuv444, plus TRI_E_INVALID for an output that is not 4-B aligned. */
+int tri_convert_rgba_f32(const void* device_bgra8, uint32_t width, uint32_t height, uint32_t pitch_bytes,
+                         void* device_f32, void* hip_stream);
+/* A grab is the tensor counterpart of tri_recorder, with the same slot protocol and error codes. It owns `slots`
+ * (1..8) device tensors of one extent and per-slot events on one device (-1 = current); with TRI_GRAB_HOST_COPY it
+ * also owns as many pinned host buffers and a copy stream (without the flag nothing ever crosses PCIe). Other flag
+ * bits are TRI_E_INVALID.
+ *   tri_framegrab_capture  (idle -> busy, asynchronous) on the context's stream, behind its last tri_render,
+ *                          converts the colour target tri_bind_output currently binds into the slot's device tensor
+ *                          (tri_convert_rgba_f32's layout and arithmetic); with TRI_GRAB_HOST_COPY it then copies
+ *                          the tensor to the slot's pinned buffer on the grab's stream, behind an event.
+ *                          TRI_E_STATE: a busy slot, a row-band context; TRI_E_INVALID: a context of another extent
+ *                          or on another device, a slot out of range.
+ *   tri_framegrab_wait     either out-pointer may be NULL (not both). `device` waits for the conversion and returns
+ *                          the device tensor; `host` waits for the copy and returns the pinned tensor. Both stay
+ *                          valid until the release. TRI_E_STATE for an idle slot, and for `host` on a grab created
+ *                          without TRI_GRAB_HOST_COPY.
+ *   tri_framegrab_release  (busy -> idle) first waits for a capture that has not finished, so the slot's next
+ *                          capture cannot race the conversion or the copy; releasing an idle slot is TRI_OK.
+ * A frame that tri_synchronize reports as TRI_E_OVERFLOW was captured incomplete: release the slot and capture
+ * again after the re-render. One host thread per grab; single contexts only (no tri_group).
+ * tri_framegrab_destroy waits for the captures in flight; NULL is TRI_OK. */
+#define TRI_GRAB_HOST_COPY 1u
+typedef struct tri_framegrab tri_framegrab;
+int tri_framegrab_create(int32_t device, uint32_t width, uint32_t height, uint32_t slots, uint32_t flags,
+                         tri_framegrab** out);
+int tri_framegrab_destroy(tri_framegrab* grab);
+int tri_framegrab_capture(tri_framegrab* grab, uint32_t slot, tri_ctx* ctx);
+int tri_framegrab_wait(tri_framegrab* grab, uint32_t slot, const float** host, const float** device);
+int tri_framegrab_release(tri_framegrab* grab, uint32_t slot);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
