@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <vector>
 #include "raster_common.h"
 
 // k_setup occupancy target (waves per SIMD); with 4 waves per workgroup, also its workgroups per CU
@@ -178,6 +179,37 @@ hipError_t tri_launch_bgra_to_yuv444(const void* src, uint32_t width, uint32_t h
 hipError_t tri_launch_bgra_to_rgba_f32(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, float* dst,
                                        hipStream_t stream);
 
+// The text overlay (text_overlay.hip; include/tri_raster.h "text overlay"). A wave of k_text_overlay scans its
+// bin's quad references TRI_TEXT_SCAN_CHUNK at a time (one per lane) and walks the ballot of the hits in order: the
+// ballot is the per-round list, TRI_TEXT_LIST_CAP entries; a strip under more quads takes more rounds. Screen bins are
+// TRI_TEXT_BIN x TRI_TEXT_BIN pixels. (Mirrored in python/trident_raster/abi.py; the tests size themselves from them.)
+#define TRI_TEXT_SCAN_CHUNK 64
+#define TRI_TEXT_LIST_CAP 64
+#define TRI_TEXT_BIN 32
+// One quad as the kernel reads it: snapped corners (mirroring resolved: X0 < X1, Y0 < Y1), u, v at (X0, Y0) and their
+// span to (X1, Y1), the colour.
+struct TriTextQuadDev {
+    int32_t X0, Y0, X1, Y1;
+    float u0, du, v0, dv;
+    float rgba[4];
+};
+static_assert(sizeof(TriTextQuadDev) == 48, "TriTextQuadDev layout");
+// What tri_text_build derives from a context's quads (host only): `blob` is the device image — nquads TriTextQuadDev,
+// at off_refs nrefs uint4 {quad, x0 | x1 << 16, y0 | y1 << 16, 0} (inclusive pixel boxes) filed per bin in
+// submission order, at off_rows nbx * nby uint2 {first, end} reference ranges — and the launch's bin box.
+struct TriTextPlan {
+    std::vector<uint8_t> blob;
+    size_t off_refs = 0, off_rows = 0;
+    uint32_t nquads = 0, nrefs = 0;
+    uint32_t bx0 = 0, by0 = 0, nbx = 0, nby = 0;
+};
+bool tri_text_quads_finite(const tri_text_quad* quads, uint32_t count);
+// rows [y0, y1) of a frame W wide: quads that cover no pixel centre there are dropped (nquads 0: nothing to launch)
+void tri_text_build(const tri_text_quad* quads, uint32_t count, int32_t W, int32_t y0, int32_t y1, TriTextPlan& plan);
+// color: the context's first row; d_blob: plan.blob on the device (16-B aligned)
+hipError_t tri_launch_text(uint32_t* color, int32_t W, int32_t y0, int32_t y1, const TriTextPlan& plan,
+                           const uint8_t* d_blob, const uint8_t* atlas, uint32_t aw, uint32_t ah, hipStream_t stream);
+
 // Internal accessors for the group layer (tri_group.hip): a context's stream and device.
 hipStream_t tri_internal_stream(tri_ctx* ctx);
 int tri_internal_device(tri_ctx* ctx);
@@ -187,4 +219,5 @@ bool tri_internal_whole_frame(tri_ctx* ctx);
 int tri_internal_fail(int code, const char* msg);
 // The device a geometry object lives on; the UNORM8 decode table (b / 255) on a context's device.
 int tri_internal_geometry_device(const tri_geometry* geometry);
+int tri_internal_font_device(const tri_font* font);
 const float* tri_internal_unorm_lut(tri_ctx* ctx);

@@ -326,6 +326,26 @@ int tri_group_set_draws(tri_group* g, const tri_draw* d, uint32_t n) {
     return each(g, [&](tri_ctx* c) { return tri_set_draws(c, d, n); });
 }
 
+int tri_group_set_text(tri_group* g, tri_font* const* fonts, const tri_text_quad* q, uint32_t n) {
+    if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_set_text: null group");
+    if (!fonts || !n) return each(g, [&](tri_ctx* c) { return tri_set_text(c, nullptr, nullptr, 0); });
+    // fonts: one per distinct device, in any order; resolve every band first so that a failure changes no band
+    std::vector<tri_font*> use(g->n, nullptr);
+    for (uint32_t r = 0; r < g->n; ++r) {
+        for (size_t i = 0; i < g->udev.size() && !use[r]; ++i)
+            if (fonts[i] && tri_internal_font_device(fonts[i]) == g->dev[r]) use[r] = fonts[i];
+        if (!use[r]) return tri_internal_fail(TRI_E_INVALID, "tri_group_set_text: no font on a band's device");
+    }
+    if (!q) return tri_internal_fail(TRI_E_INVALID, "tri_group_set_text: null quads");
+    if (n > TRI_MAX_TEXT_QUADS || !tri_text_quads_finite(q, n))
+        return tri_internal_fail(TRI_E_INVALID, "tri_group_set_text: too many quads or a non-finite coordinate");
+    for (uint32_t r = 0; r < g->n; ++r) {
+        const int rc = tri_set_text(g->ctx[r], use[r], q, n);
+        if (rc) return rc;
+    }
+    return TRI_OK;
+}
+
 int tri_group_render(tri_group* g) {
     if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_render: null group");
     const int32_t ddev = g->dev[g->display];

@@ -96,6 +96,13 @@ struct tri_geometry {
     bool geometry_set = false;
 };
 
+// One A8 coverage atlas on one device (tri_font_create).
+struct tri_font {
+    int device = 0;
+    uint8_t* d_alpha = nullptr;
+    uint32_t w = 0, h = 0;
+};
+
 struct tri_ctx {
     tri_config cfg{};
     int device = 0;
@@ -187,6 +194,16 @@ struct tri_ctx {
     uint32_t* d_shadow = nullptr; size_t cap_shadow = 0;
     uint32_t s_nbx = 0, s_nbins = 0, s_bin_cap = 0;
     bool shadow_rendered = false;  // a frame with the current map size has been enqueued
+
+    // text overlay (tri_set_text): the caller's quads, what tri_text_build made of them for this context's rows, and
+    // its device image, uploaded through a pinned staging buffer of its own at the next tri_render
+    tri_font* text_font = nullptr;
+    std::vector<tri_text_quad> text_quads;
+    TriTextPlan text_plan;
+    bool text_dirty = false;
+    uint8_t* d_text = nullptr; size_t cap_text = 0;
+    void* h_text = nullptr; size_t cap_h_text = 0;
+    hipEvent_t text_free = nullptr;  // the staging buffer's last copy has run
 
     uint32_t* d_color_own = nullptr;
     float* d_depth_own = nullptr;
@@ -547,6 +564,34 @@ int resolve_draws(tri_ctx* c) {
     return TRI_OK;
 }
 
+// The text overlay's device image (TriTextPlan::blob), staged as resolve_draws stages the draws: the pinned buffer is
+// rewritten only after its previous copy ran, and the copy rides the stream behind the frames still reading the old
+// image.
+int upload_text(tri_ctx* c) {
+    if (!c->text_dirty) return TRI_OK;
+    tri_text_build(c->text_quads.data(), (uint32_t)c->text_quads.size(), c->W, c->y0, c->y1, c->text_plan);
+    const size_t bytes = c->text_plan.blob.size();
+    if (bytes) {
+        int rc;
+        if (bytes > c->cap_text) {  // (hipFree waits for the device: no frame still reads the old image)
+            if ((rc = grow(c->d_text, c->cap_text, bytes * 2))) return rc;
+        }
+        if (c->text_free) HIP_TRY(hipEventSynchronize(c->text_free));
+        if (bytes > c->cap_h_text) {
+            if (c->h_text) HIP_TRY(hipHostFree(c->h_text));
+            c->h_text = nullptr;
+            c->cap_h_text = bytes * 2;
+            HIP_TRY(hipHostMalloc(&c->h_text, c->cap_h_text, hipHostMallocDefault));
+        }
+        std::memcpy(c->h_text, c->text_plan.blob.data(), bytes);
+        HIP_TRY(hipMemcpyAsync(c->d_text, c->h_text, bytes, hipMemcpyHostToDevice, c->stream));
+        if (!c->text_free) HIP_TRY(hipEventCreateWithFlags(&c->text_free, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->text_free, c->stream));
+    }
+    c->text_dirty = false;
+    return TRI_OK;
+}
+
 // A stride near nchunks / golden ratio, coprime to nchunks.
 uint32_t chunk_stride(uint32_t n) {
     if (n <= 2) return 1;
@@ -851,6 +896,7 @@ int tri_internal_device(tri_ctx* c) { return c->device; }
 bool tri_internal_whole_frame(tri_ctx* c) { return c->y0 == 0 && c->y1 == c->H; }
 int tri_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int tri_internal_geometry_device(const tri_geometry* g) { return g->device; }
+int tri_internal_font_device(const tri_font* f) { return f->device; }
 const float* tri_internal_unorm_lut(tri_ctx* c) { return c->d_lut + 256; }
 
 extern "C" {
@@ -936,6 +982,9 @@ int tri_destroy(tri_ctx* c) {
     f(c->d_bin_count); f(c->d_bin_list); f(c->d_ctr);
     f(c->d_color_own); f(c->d_depth_own); f(c->d_present);
     f(c->d_lpos); f(c->d_lsnap); f(c->d_sbin_count); f(c->d_sbin_list); f(c->d_shadow);
+    f(c->d_text);
+    if (c->h_text) (void)hipHostFree(c->h_text);
+    if (c->text_free) (void)hipEventDestroy(c->text_free);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     f(c->d_args);
@@ -1201,7 +1250,70 @@ int tri_frame_alpha(tri_ctx* c, int32_t* alpha) {
         const float t = (float)ta / 255.0f;
         uniform = (int32_t)unorm8_host((c->mat0.base_color_factor[3] * d.pc.tint[3]) * t) == a;
     }
+    if (c->text_font && !c->text_quads.empty()) uniform = false;  // the text pass blends into the alpha channel
     *alpha = uniform ? a : -1;
+    return TRI_OK;
+}
+
+int tri_font_create(int32_t device, const uint8_t* alpha, uint32_t width, uint32_t height, tri_font** out) {
+    if (!alpha || !out) return fail(TRI_E_INVALID, "tri_font_create: null argument");
+    *out = nullptr;
+    if (width == 0 || height == 0 || width > TRI_MAX_DIM || height > TRI_MAX_DIM)
+        return fail(TRI_E_INVALID, "tri_font_create: atlas %ux%u outside 1..%d", width, height, TRI_MAX_DIM);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TRI_E_HIP, "tri_font_create: no HIP device available");
+    int dev = device;
+    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+    if (dev >= ndev) return fail(TRI_E_INVALID, "tri_font_create: device %d of %d", dev, ndev);
+    HIP_TRY(hipSetDevice(dev));
+    tri_font* f = new tri_font();
+    f->device = dev;
+    f->w = width;
+    f->h = height;
+    const size_t bytes = (size_t)width * height;
+    if (hipMalloc(&f->d_alpha, bytes) != hipSuccess) {
+        delete f;
+        return fail(TRI_E_OOM, "tri_font_create: atlas allocation failed");
+    }
+    // a blocking copy, then the device idle: contexts read the atlas on non-blocking streams of their own
+    if (hipMemcpy(f->d_alpha, alpha, bytes, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(f->d_alpha);
+        delete f;
+        return fail(TRI_E_HIP, "tri_font_create: atlas upload failed");
+    }
+    *out = f;
+    return TRI_OK;
+}
+
+int tri_font_destroy(tri_font* f) {
+    if (!f) return TRI_OK;
+    (void)hipSetDevice(f->device);
+    if (f->d_alpha) (void)hipFree(f->d_alpha);  // waits for the device: no text pass still samples it
+    delete f;
+    return TRI_OK;
+}
+
+int tri_set_text(tri_ctx* c, tri_font* font, const tri_text_quad* q, uint32_t n) {
+    if (!c) return fail(TRI_E_INVALID, "tri_set_text: null context");
+    if (n && !q) return fail(TRI_E_INVALID, "tri_set_text: null quads");
+    if (n > TRI_MAX_TEXT_QUADS) return fail(TRI_E_INVALID, "tri_set_text: %u quads (at most %u)", n, TRI_MAX_TEXT_QUADS);
+    if (font && n) {
+        if (font->device != c->device)
+            return fail(TRI_E_INVALID, "tri_set_text: font on device %d, context on device %d", font->device, c->device);
+        if (!tri_text_quads_finite(q, n)) return fail(TRI_E_INVALID, "tri_set_text: non-finite quad coordinate");
+    }
+    if (!font || !n) {  // no overlay: tri_render enqueues exactly the frame's own launches
+        c->text_font = nullptr;
+        c->text_quads.clear();
+        c->text_plan = TriTextPlan{};
+        c->text_dirty = false;
+        return TRI_OK;
+    }
+    c->text_font = font;
+    if (n == c->text_quads.size() && std::memcmp(c->text_quads.data(), q, n * sizeof(tri_text_quad)) == 0)
+        return TRI_OK;  // unchanged (a static label): keep the device image
+    c->text_quads.assign(q, q + n);
+    c->text_dirty = true;
     return TRI_OK;
 }
 
@@ -1453,6 +1565,13 @@ int tri_render(tri_ctx* c) {
     TRI_HSTAMP(3);
     HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev));
     c->launched = true;
+    // the text pass (TextRenderer::RecordViewport, after the mesh / sky pass): only when quads are set. A
+    // TRI_E_OVERFLOW re-render restarts from the clear, so the overlay is reapplied by construction.
+    if (c->text_font && !c->text_quads.empty()) {
+        if ((rc = upload_text(c))) return rc;
+        HIP_TRY(tri_launch_text(c->d_color, c->W, c->y0, c->y1, c->text_plan, c->d_text, c->text_font->d_alpha,
+                                c->text_font->w, c->text_font->h, c->stream));
+    }
     if (timed) c->pending.push_back(ts);
     if (fp.shadow_on) c->shadow_rendered = true;
 #ifdef TRI_HOST_TIMING

@@ -38,6 +38,10 @@ public:
     static glm::mat4 GetViewportViewMatrix(uint32_t id) { return GetRenderer().GetViewportViewMatrix(id); }
     static glm::mat4 GetViewportProjectionMatrix(uint32_t id) { return GetRenderer().GetViewportProjectionMatrix(id); }
     static glm::vec4 GetClearColor() { return GetRenderer().GetClearColor(); }
+    // Text overlay (RenderCommand::SubmitText)
+    static void SubmitText(uint32_t viewportId, const glm::vec2& position, const glm::vec4& color, const std::string& text) {
+        GetRenderer().SubmitText(viewportId, position, color, text);
+    }
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }

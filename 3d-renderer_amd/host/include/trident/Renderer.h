@@ -20,6 +20,7 @@
 #include "Scene.h"
 #include "FrameDatasetRecorder.h"
 #include "VideoEncoder.h"
+#include "TextRenderer.h"
 
 namespace Trident {
 
@@ -86,6 +87,17 @@ public:
     // Renderer.cpp:3830). Changing it re-runs the discovery; GetSkyboxSource names what was loaded
     // ("PNG fallback", "Default directory", ... or "solid 0x808080").
     void SetAssetsDirectory(const std::string& directory);
+    // Text overlay (Renderer::SubmitText, Renderer.h:229, Renderer.cpp:6065-6079 -> TextRenderer::QueueText): queues
+    // `text` for the viewport's next DrawFrame, drawn inside its pass after the sprites (the library's text pass,
+    // tri_set_text) and therefore part of everything that takes the target afterwards: the pixels, the present blit,
+    // a recorded frame, the AI tensor. The queue is cleared every DrawFrame; empty text is ignored; text for a viewport
+    // id that does not render this frame is dropped, and the legacy present path draws none (the reference records
+    // text for viewport contexts only). The first SubmitText loads <assets directory>/Fonts/JetBrainsMono-Regular.ttf
+    // at 32 px unless SetTextFont named a font; without a font an error is logged once and text is absent.
+    void SubmitText(uint32_t viewportId, const glm::vec2& position, const glm::vec4& color, const std::string& text);
+    // Names the font file and pixel height instead of the default; false (the previous font stays) when it cannot
+    // be loaded. Waits for the frames in flight.
+    bool SetTextFont(const std::string& path, float pixelHeight);
     const std::string& GetSkyboxSource() const { return m_SkyboxSource; }
     glm::vec4 GetClearColor() const { return m_ClearColor; }
 
@@ -366,6 +378,16 @@ private:
     std::string m_RecordingPath;
     VideoEncoder m_VideoEncoder;
     tri_recorder* m_Recorder = nullptr;
+
+    // text overlay: the font and the frame's queue, and one device atlas per device (made by the first DrawFrame
+    // with text, dropped with the viewport targets and when the font changes)
+    TextRenderer m_TextRenderer;
+    bool m_TextFontTried = false;  // the default font was looked for (and logged if missing)
+    std::map<int32_t, tri_font*> m_Fonts;
+    uint64_t m_FontsVersion = 0;  // TextRenderer::GetFontVersion the atlases were made from
+    std::vector<tri_text_quad> m_TextQuads;
+    void DropFonts();
+    bool SetTargetText(ViewportContext& target, uint32_t viewportId);  // before the target's tri_render
     bool CaptureRecordedFrame(ViewportContext& target, uint32_t slot);
     void StopRecording();  // finish the frames in flight, finalise the file
 

@@ -188,6 +188,29 @@ int trident_dataset_state(trident_dataset* dataset, int* enabled, uint32_t* inte
 /* FrameDatasetRecorder::WriteNpyFile alone: TRI_OK, or TRI_E_STATE where it refuses (no file is written then). */
 int trident_dataset_write_npy(const char* path, const float* data, uint64_t count, const int64_t* shape, uint32_t rank);
 
+/* ---- text overlay ---- */
+/* Renderer::SubmitText: `bytes` bytes of UTF-8 (no terminator needed) at `position` (viewport pixels) in `color`
+ * (RGBA) for the viewport's next draw_frame. */
+int trident_app_submit_text(trident_app* app, uint32_t viewport_id, const float position[2], const float color[4],
+                            const char* text, uint32_t bytes);
+/* Renderer::SetTextFont: TRI_OK, or TRI_E_STATE where it returns false (the previous font stays). */
+int trident_app_set_font(trident_app* app, const char* path, float pixel_height);
+/* Trident::TextRenderer on its own (no app, no device): load a TrueType file (TRI_E_STATE where LoadFontFile returns
+ * false), then read what it baked. atlas: out = NULL queries the extent, else capacity must hold width * height
+ * coverage bytes. glyph: ResolveGlyph(codepoint) as offset.xy, size.xy, uv_min.xy, uv_max.xy, advance.
+ * metrics: line advance, scale (pixels per font unit), pixel height. layout: one string at `position` into at most
+ * `capacity` quads; *count gets how many the string needs (TRI_E_INVALID, nothing written, when capacity is short). */
+typedef struct trident_font trident_font;
+int trident_font_create(trident_font** out);
+void trident_font_destroy(trident_font* font);
+int trident_font_load(trident_font* font, const char* path, float pixel_height);
+int trident_font_load_memory(trident_font* font, const uint8_t* data, uint64_t size, float pixel_height);
+int trident_font_atlas(trident_font* font, uint8_t* out, uint64_t capacity, uint32_t* width, uint32_t* height);
+int trident_font_glyph(trident_font* font, uint32_t codepoint, float out[9]);
+int trident_font_metrics(trident_font* font, float out[3]);
+int trident_font_layout(trident_font* font, const float position[2], const float color[4], const char* text,
+                        uint32_t bytes, tri_text_quad* out, uint32_t capacity, uint32_t* count);
+
 /* Renderer::GetViewportTexture: copies the viewport's image handle (TRI_E_STATE before its first frame). */
 int trident_app_viewport_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
 /* Renderer::GetGeometryUploadCount. */

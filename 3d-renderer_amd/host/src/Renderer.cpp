@@ -266,6 +266,89 @@ void Renderer::DestroyViewportTargets() {
     for (tri_geometry* g : m_DeviceGeometry) tri_geometry_destroy(g);
     m_DeviceGeometry.clear();
     m_DeviceGeometryGeneration.clear();
+    DropFonts();
+}
+
+void Renderer::DropFonts() {  // only while no context that was given one can still render with it
+    for (auto& it : m_Fonts) tri_font_destroy(it.second);
+    m_Fonts.clear();
+}
+
+void Renderer::SubmitText(uint32_t viewportId, const glm::vec2& position, const glm::vec4& color, const std::string& text) {
+    if (text.empty()) return;
+    if (!m_TextRenderer.IsLoaded() && !m_TextFontTried) {  // TextRenderer::LoadDefaultFont (TextRenderer.cpp:261-284)
+        m_TextFontTried = true;
+        const std::string path = m_AssetsDirectory + "/Fonts/JetBrainsMono-Regular.ttf";
+        if (!m_TextRenderer.LoadFontFile(path, 32.0f))
+            LogError("TextRenderer could not load the default font", path.c_str());
+    }
+    m_TextRenderer.QueueText(viewportId, position, color, text);  // (ignored without a font)
+}
+
+bool Renderer::SetTextFont(const std::string& path, float pixelHeight) {
+    m_TextFontTried = true;  // an embedder that names a font does not get the default behind its back
+    FinishFrame();           // no frame in flight samples the atlas that is about to go
+    if (!m_TextRenderer.LoadFontFile(path, pixelHeight)) return false;  // (the previous font stays)
+    auto clear = [](ViewportContext& vc) {  // every later frame sets its text anew, with the new atlas
+        if (vc.m_Group) tri_group_set_text(vc.m_Group, nullptr, nullptr, 0);
+        else if (vc.m_Ctx) tri_set_text(vc.m_Ctx, nullptr, nullptr, 0);
+    };
+    for (auto& it : m_Viewports) clear(it.second);
+    for (auto& it : m_RingTargets)
+        for (ViewportContext& vc : it.second) clear(vc);
+    DropFonts();
+    m_FontsVersion = m_TextRenderer.GetFontVersion();
+    m_TextRenderer.BeginFrame();  // quads of the old glyph table are not drawn with the new atlas
+    return true;
+}
+
+// The viewport's queued text onto this frame's target (count 0 when nothing is queued): called for every target
+// before its tri_render, so ring targets (SetFramesInFlight > 1), which are separate contexts, each carry the text
+// of the frame they render.
+bool Renderer::SetTargetText(ViewportContext& vc, uint32_t viewportId) {
+    m_TextQuads.clear();
+    m_TextRenderer.LayoutViewport(viewportId, m_TextQuads);
+    if (m_TextQuads.empty()) {
+        const int rc = vc.m_Group ? tri_group_set_text(vc.m_Group, nullptr, nullptr, 0) : tri_set_text(vc.m_Ctx, nullptr, nullptr, 0);
+        return rc == TRI_OK;
+    }
+    if (m_FontsVersion != m_TextRenderer.GetFontVersion()) {
+        DropFonts();  // (SetTextFont has waited for the frames and cleared the targets' text)
+        m_FontsVersion = m_TextRenderer.GetFontVersion();
+    }
+    auto fontOn = [&](int32_t device) -> tri_font* {
+        auto it = m_Fonts.find(device);
+        if (it != m_Fonts.end()) return it->second;
+        tri_font* f = nullptr;
+        if (tri_font_create(device, m_TextRenderer.AtlasPixels().data(), TextRenderer::s_AtlasSize, TextRenderer::s_AtlasSize,
+                            &f) != TRI_OK) {
+            LogError("text atlas", tri_last_error());
+            return nullptr;
+        }
+        m_Fonts.emplace(device, f);
+        return f;
+    };
+    int rc;
+    if (vc.m_Group) {
+        std::vector<tri_font*> fonts;  // one per distinct device
+        std::vector<int32_t> seen;
+        for (int32_t d : m_Devices) {
+            if (std::find(seen.begin(), seen.end(), d) != seen.end()) continue;
+            seen.push_back(d);
+            tri_font* f = fontOn(d);
+            if (!f) return false;
+            fonts.push_back(f);
+        }
+        rc = tri_group_set_text(vc.m_Group, fonts.data(), m_TextQuads.data(), (uint32_t)m_TextQuads.size());
+    } else {
+        tri_image img{};
+        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK) return false;
+        tri_font* f = fontOn(img.device);
+        if (!f) return false;
+        rc = tri_set_text(vc.m_Ctx, f, m_TextQuads.data(), (uint32_t)m_TextQuads.size());
+    }
+    if (rc != TRI_OK) LogError("text overlay", tri_last_error());
+    return rc == TRI_OK;
 }
 
 void Renderer::Shutdown() {
@@ -1095,6 +1178,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         if (!PrepareViewport(vc)) return;
         tri_global_ubo ubo;
         UpdateUniformBuffer(GetActiveCamera(vc), ubo);
+        if (!SetTargetText(vc, id)) LogError("DrawFrame", "the text overlay of this frame is missing");
         if (!SubmitTarget(vc, ubo, draws, shadow, shadowOn)) return;
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
@@ -1122,6 +1206,8 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     // the skybox, the meshes and the sprites go straight into the present image at the swapchain extent,
     // cleared to the clear colour, with the uniform block last recorded: the null-camera update
     // (GetActiveCamera()) when no viewport rendered (:5223-5226), else the last viewport pass's.
+    // the queue lasts one frame (TextRenderer::BeginFrame): text for ids that rendered no pass is dropped
+    m_TextRenderer.BeginFrame();
     ViewportContext* legacy = nullptr;
     if (!primaryActive && m_PresentWidth && m_PresentHeight) {
         m_LegacyTarget.m_Info.Size = glm::vec2((float)m_PresentWidth, (float)m_PresentHeight);

@@ -568,6 +568,106 @@ int trident_app_recording_state(trident_app* app, int* recording, uint64_t* fram
     });
 }
 
+struct trident_font {
+    TextRenderer text;
+};
+
+int trident_app_submit_text(trident_app* app, uint32_t viewport_id, const float position[2], const float color[4],
+                            const char* text, uint32_t bytes) {
+    return Guard(app, [&] {
+        if (!position || !color || (bytes && !text)) return TRI_E_INVALID;
+        app->renderer.SubmitText(viewport_id, glm::vec2(position[0], position[1]),
+                                 glm::vec4(color[0], color[1], color[2], color[3]), std::string(text ? text : "", bytes));
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_font(trident_app* app, const char* path, float pixel_height) {
+    return Guard(app, [&] {
+        if (!path) return TRI_E_INVALID;
+        return app->renderer.SetTextFont(path, pixel_height) ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_font_create(trident_font** out) {
+    if (!out) return TRI_E_INVALID;
+    *out = nullptr;
+    try {
+        *out = new trident_font();
+        return TRI_OK;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+void trident_font_destroy(trident_font* font) { delete font; }
+
+int trident_font_load(trident_font* font, const char* path, float pixel_height) {
+    if (!font || !path) return TRI_E_INVALID;
+    try {
+        return font->text.LoadFontFile(path, pixel_height) ? TRI_OK : TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+int trident_font_load_memory(trident_font* font, const uint8_t* data, uint64_t size, float pixel_height) {
+    if (!font || !data) return TRI_E_INVALID;
+    try {
+        return font->text.LoadFontMemory(data, (size_t)size, pixel_height) ? TRI_OK : TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+int trident_font_atlas(trident_font* font, uint8_t* out, uint64_t capacity, uint32_t* width, uint32_t* height) {
+    if (!font) return TRI_E_INVALID;
+    if (!font->text.IsLoaded()) return TRI_E_STATE;
+    if (width) *width = TextRenderer::s_AtlasSize;
+    if (height) *height = TextRenderer::s_AtlasSize;
+    if (!out) return TRI_OK;
+    const std::vector<uint8_t>& a = font->text.AtlasPixels();
+    if (capacity < a.size()) return TRI_E_INVALID;
+    std::memcpy(out, a.data(), a.size());
+    return TRI_OK;
+}
+
+int trident_font_glyph(trident_font* font, uint32_t codepoint, float out[9]) {
+    if (!font || !out) return TRI_E_INVALID;
+    if (!font->text.IsLoaded()) return TRI_E_STATE;
+    const TextRenderer::Glyph& g = font->text.ResolveGlyph((char32_t)codepoint);
+    const float v[9] = {g.m_Offset.x, g.m_Offset.y, g.m_Size.x, g.m_Size.y, g.m_UVMin.x, g.m_UVMin.y,
+                        g.m_UVMax.x, g.m_UVMax.y, g.m_Advance};
+    std::memcpy(out, v, sizeof v);
+    return TRI_OK;
+}
+
+int trident_font_metrics(trident_font* font, float out[3]) {
+    if (!font || !out) return TRI_E_INVALID;
+    if (!font->text.IsLoaded()) return TRI_E_STATE;
+    out[0] = font->text.GetLineAdvance();
+    out[1] = font->text.GetScale();
+    out[2] = font->text.GetFontPixelHeight();
+    return TRI_OK;
+}
+
+int trident_font_layout(trident_font* font, const float position[2], const float color[4], const char* text,
+                        uint32_t bytes, tri_text_quad* out, uint32_t capacity, uint32_t* count) {
+    if (!font || !position || !color || !count || (bytes && !text)) return TRI_E_INVALID;
+    if (!font->text.IsLoaded()) return TRI_E_STATE;
+    try {
+        std::vector<tri_text_quad> quads;
+        font->text.LayoutText(glm::vec2(position[0], position[1]), glm::vec4(color[0], color[1], color[2], color[3]),
+                              std::string_view(text ? text : "", bytes), quads);
+        *count = (uint32_t)quads.size();
+        if (quads.size() > capacity || (!quads.empty() && !out)) return TRI_E_INVALID;
+        if (!quads.empty()) std::memcpy(out, quads.data(), quads.size() * sizeof(tri_text_quad));
+        return TRI_OK;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
 struct trident_video {
     VideoEncoder encoder;
 };

@@ -207,6 +207,23 @@ TRI_XFER_ID_BYTES = 128
 TRI_GRAB_HOST_COPY = 0x1  # tri_framegrab_create
 
 
+# text overlay (include/tri_raster.h; the scan chunk, per-round list capacity and bin edge of k_text_overlay are
+# csrc/raster_launch.h's)
+TRI_MAX_TEXT_QUADS = 65536
+TRI_TEXT_SCAN_CHUNK, TRI_TEXT_LIST_CAP, TRI_TEXT_BIN = 64, 64, 32
+
+
+class TriTextQuad(C.Structure):
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float),
+                ("u0", C.c_float), ("v0", C.c_float), ("u1", C.c_float), ("v1", C.c_float),
+                ("rgba", C.c_float * 4)]
+
+
+# one row per quad: x0, y0, x1, y1, u0, v0, u1, v1, r, g, b, a
+TEXT_QUAD_DTYPE = np.dtype(("<f4", 12))
+assert C.sizeof(TriTextQuad) == 48 and TEXT_QUAD_DTYPE.itemsize == 48
+
+
 class TriXferConfig(C.Structure):
     _fields_ = [("width", C.c_uint32), ("band_y", C.POINTER(C.c_uint32)), ("display", C.c_uint32),
                 ("format", C.c_uint32), ("slot_bytes", C.c_uint32), ("alpha", C.c_uint32), ("nbuf", C.c_uint32)]
@@ -274,6 +291,10 @@ CABI_FUNCTIONS = [
     ("tri_framegrab_capture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("tri_framegrab_wait", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("tri_framegrab_release", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("tri_font_create", C.c_int, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_font_destroy", C.c_int, [C.c_void_p]),
+    ("tri_set_text", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("tri_group_set_text", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32]),
     ("tri_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("tri_get_timing", C.c_int, [C.c_void_p, C.POINTER(TriTiming)]),
     ("tri_get_frame_stats", C.c_int, [C.c_void_p, C.POINTER(TriFrameStats)]),

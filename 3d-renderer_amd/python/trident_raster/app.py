@@ -106,6 +106,18 @@ _APP_FUNCTIONS = [
     ("trident_dataset_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint64)]),
     ("trident_dataset_write_npy", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32]),
+    ("trident_app_submit_text", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4),
+                                          C.c_char_p, C.c_uint32]),
+    ("trident_app_set_font", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
+    ("trident_font_create", C.c_int, [C.POINTER(C.c_void_p)]),
+    ("trident_font_destroy", None, [C.c_void_p]),
+    ("trident_font_load", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
+    ("trident_font_load_memory", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float]),
+    ("trident_font_atlas", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("trident_font_glyph", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 9)]),
+    ("trident_font_metrics", C.c_int, [C.c_void_p, C.POINTER(C.c_float * 3)]),
+    ("trident_font_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4), C.c_char_p,
+                                      C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
 ]
 
 _lib = None
@@ -267,6 +279,20 @@ class TridentApp:
     def set_skybox(self, faces):
         f = np.ascontiguousarray(faces, np.uint8)
         _check(self._lib.trident_app_set_skybox(self._h, f.ctypes.data, f.shape[1]), "set_skybox")
+
+    def submit_text(self, viewport_id, position, color, text):
+        """Renderer::SubmitText: text (str, encoded as UTF-8, or bytes as they are) for the viewport's next frame."""
+        data = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        pos, col = (C.c_float * 2)(*position), (C.c_float * 4)(*color)
+        _check(self._lib.trident_app_submit_text(self._h, viewport_id, C.byref(pos), C.byref(col), data, len(data)),
+               "submit_text")
+
+    def set_font(self, path, pixel_height=32.0):
+        """Renderer::SetTextFont; returns its bool."""
+        rc = self._lib.trident_app_set_font(self._h, os.fsencode(path), pixel_height)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_font")
+        return rc == abi.TRI_OK
 
     def draw_frame(self):
         _check(self._lib.trident_app_draw_frame(self._h), "draw_frame")
@@ -504,6 +530,75 @@ class VideoEncoder:
         act, frames = C.c_int(), C.c_uint64()
         _check(self._lib.trident_video_state(self._h, C.byref(act), C.byref(frames)), "video_state")
         return bool(act.value), frames.value
+
+
+class Font:
+    """Trident::TextRenderer on its own (no app, no device): load a TrueType file, read the baked atlas, the glyph
+    table and the metrics, lay a string out into tri_text_quad rows."""
+
+    def __init__(self, path=None, pixel_height=32.0):
+        self._lib = load_library()
+        h = C.c_void_p()
+        _check(self._lib.trident_font_create(C.byref(h)), "trident_font_create")
+        self._h = h
+        if path is not None and not self.load(path, pixel_height):
+            raise ValueError(f"font {path} could not be loaded")
+
+    def close(self):
+        if self._h:
+            self._lib.trident_font_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _bool(self, rc, what):
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, what)
+        return rc == abi.TRI_OK
+
+    def load(self, path, pixel_height=32.0):
+        return self._bool(self._lib.trident_font_load(self._h, os.fsencode(path), pixel_height), "font_load")
+
+    def load_memory(self, data, pixel_height=32.0):
+        a = np.frombuffer(bytes(data), np.uint8)
+        if a.size == 0:
+            return False
+        return self._bool(self._lib.trident_font_load_memory(self._h, a.ctypes.data, a.size, pixel_height),
+                          "font_load_memory")
+
+    def atlas(self):
+        """uint8 [height, width] coverage."""
+        w, h = C.c_uint32(), C.c_uint32()
+        _check(self._lib.trident_font_atlas(self._h, None, 0, C.byref(w), C.byref(h)), "font_atlas")
+        out = np.empty((h.value, w.value), np.uint8)
+        _check(self._lib.trident_font_atlas(self._h, out.ctypes.data, out.size, None, None), "font_atlas")
+        return out
+
+    def glyph(self, codepoint):
+        """ResolveGlyph(codepoint): float32 (offset.x, offset.y, size.x, size.y, u0, v0, u1, v1, advance)."""
+        out = (C.c_float * 9)()
+        _check(self._lib.trident_font_glyph(self._h, codepoint, C.byref(out)), "font_glyph")
+        return np.array(out[:], np.float32)
+
+    def metrics(self):
+        """(line advance, scale in pixels per font unit, pixel height)."""
+        out = (C.c_float * 3)()
+        _check(self._lib.trident_font_metrics(self._h, C.byref(out)), "font_metrics")
+        return tuple(np.array(out[:], np.float32))
+
+    def layout(self, text, position, color=(1.0, 1.0, 1.0, 1.0)):
+        """float32 [n, 12] tri_text_quad rows of one string (str -> UTF-8, or bytes as they are)."""
+        data = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+        pos, col = (C.c_float * 2)(*position), (C.c_float * 4)(*color)
+        out = np.zeros((max(len(data), 1), 12), np.float32)  # at most one quad per byte
+        n = C.c_uint32()
+        _check(self._lib.trident_font_layout(self._h, C.byref(pos), C.byref(col), data, len(data), out.ctypes.data,
+                                             out.shape[0], C.byref(n)), "font_layout")
+        return out[:n.value].copy()
 
 
 class DatasetRecorder:

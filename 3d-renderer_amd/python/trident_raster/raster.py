@@ -166,6 +166,12 @@ class TriRaster:
         arr, n = abi.draws_array(draws)
         _check(_lib.tri_set_draws(self._ctx, arr, n))
 
+    def set_text(self, font, quads):
+        """tri_set_text: float32 [n, 12] rows (x0, y0, x1, y1, u0, v0, u1, v1, r, g, b, a) composited over every
+        following frame in row order; font None or no rows removes the overlay."""
+        q = _text_quads(quads)
+        _check(_lib.tri_set_text(self._ctx, font._f if font is not None else None, _ptr(q), q.shape[0]))
+
     def set_stream(self, stream_ptr):
         _check(_lib.tri_set_stream(self._ctx, C.c_void_p(stream_ptr) if stream_ptr else None))
 
@@ -236,6 +242,40 @@ class TriRaster:
         s = abi.TriFrameStats()
         _check(_lib.tri_get_frame_stats(self._ctx, C.byref(s)))
         return {k: getattr(s, k) for k, _ in abi.TriFrameStats._fields_}
+
+
+def _text_quads(quads):
+    q = np.ascontiguousarray(quads if quads is not None else np.zeros((0, 12)), dtype=np.float32)
+    if q.size == 0:
+        return q.reshape(0, 12)
+    if q.ndim != 2 or q.shape[1] != 12:
+        raise ValueError("text quads must be float32 [n, 12]")
+    return q
+
+
+class TriFont:
+    """tri_font: one A8 coverage atlas (uint8 [h, w]) on one device."""
+
+    def __init__(self, alpha, device=-1):
+        lib = load_library()
+        a = np.ascontiguousarray(alpha, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("a font atlas is uint8 [h, w]")
+        f = C.c_void_p()
+        _check(lib.tri_font_create(device, _ptr(a), a.shape[1], a.shape[0], C.byref(f)))
+        self._f = f
+        self.width, self.height = a.shape[1], a.shape[0]
+
+    def close(self):
+        if self._f:
+            _lib.tri_font_destroy(self._f)
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class TriGeometry:
@@ -503,6 +543,19 @@ class TriGroup:
     def set_draws(self, draws):
         arr, n = abi.draws_array(draws)
         _check(_lib.tri_group_set_draws(self._g, arr, n))
+
+    def set_text(self, fonts, quads):
+        """tri_group_set_text: fonts = one TriFont per distinct device of the group (any order); None or no rows
+        removes the overlay."""
+        q = _text_quads(quads)
+        if not fonts or q.shape[0] == 0:
+            _check(_lib.tri_group_set_text(self._g, None, None, 0))
+            return
+        ndev = len(set(self._devs[:]))
+        if len(fonts) < ndev:
+            raise ValueError(f"{ndev} devices need {ndev} fonts")
+        arr = (C.c_void_p * len(fonts))(*[f._f.value for f in fonts])
+        _check(_lib.tri_group_set_text(self._g, arr, _ptr(q), q.shape[0]))
 
     def render(self):
         _check(_lib.tri_group_render(self._g))

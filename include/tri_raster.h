@@ -420,6 +420,51 @@ int tri_framegrab_capture(tri_framegrab* grab, uint32_t slot, tri_ctx* ctx);
 int tri_framegrab_wait(tri_framegrab* grab, uint32_t slot, const float** host, const float** device);
 int tri_framegrab_release(tri_framegrab* grab, uint32_t slot);
 
+/* ---- text overlay (Renderer::SubmitText -> TextRenderer::QueueText / RecordViewport, Text.vert / Text.frag) ----
+ * The reference draws queued text inside the viewport's render pass, after the sprites: one textured quad per glyph
+ * (6 vertices of TextVertex), cull NONE, no depth test or write, blend SRC_ALPHA / ONE_MINUS_SRC_ALPHA for colour and
+ * ONE / ONE_MINUS_SRC_ALPHA for alpha. Here tri_render appends the same pass on the context's stream whenever quads
+ * are set, so everything that takes the colour target after the frame (tri_readback, tri_blit_linear,
+ * tri_recorder_capture, tri_framegrab_capture, tri_xfer_frame, the group's assembly) sees the overlay. The pass,
+ * exactly (float32 unless stated):
+ *   - each corner snaps as X = (int32_t)rintf(x * 256.0f) (the main pass's 8-bit snap), after x * 256.0f is pinned to
+ *     [-2^29, 2^29] (2^21 pixels, 256 times TRI_MAX_DIM: the differences of snapped values then fit int32; a quad
+ *     reaching further is drawn as if it ended there, tx and ty included); a quad with x1 < x0 (y1 < y0) is drawn
+ *     mirrored: its corners swap together with their u (v);
+ *   - pixel (px, py) is covered iff X0 <= px * 256 + 128 < X1 and Y0 <= py * 256 + 128 < Y1 (the top-left rule of the
+ *     quad's two triangles; a zero-area quad covers nothing);
+ *   - tx = (float)(px * 256 + 128 - X0) / (float)(X1 - X0), u = u0 + tx * (u1 - u0), v likewise;
+ *   - alpha = the atlas (byte / 255.0f) sampled LINEAR, CLAMP_TO_EDGE, level 0 at (u, v) (x = u * width - 0.5);
+ *   - src = clamp((r, g, b, a) * alpha, 0, 1); out.rgb = src.rgb * src.a + dst.rgb * (1 - src.a),
+ *     out.a = src.a + dst.a * (1 - src.a): the colour is multiplied by alpha twice, as the reference's is;
+ *   - quads blend in submission order, and after every quad the pixel is rounded to B8G8R8A8_UNORM
+ *     (clamp, * 255 + 0.5, truncate); the next quad reads byte / 255.0f. Pixels no quad covers are not written;
+ *     depth is neither read nor written.
+ * A tri_font is the atlas's alpha plane on one device (the reference uploads RGBA with RGB = 255 and samples .a only,
+ * TextRenderer.cpp:374-379): width, height in 1..TRI_MAX_DIM, rows top to bottom. device -1 = the current device.
+ * tri_font_destroy only after every context that uses the font dropped it (tri_set_text with another font, NULL or
+ * count 0, or tri_destroy); NULL is TRI_OK.
+ * The pass runs behind the frame's last timing stamp: tri_timing (ms_frame and the stages) does not include it. */
+typedef struct tri_font tri_font;
+int tri_font_create(int32_t device, const uint8_t* alpha, uint32_t width, uint32_t height, tri_font** out);
+int tri_font_destroy(tri_font* font);
+
+/* One glyph quad (TextRenderer::RecordViewport's 6 vertices, TextRenderer.cpp:144-193). */
+typedef struct tri_text_quad {
+    float x0, y0, x1, y1; /* viewport pixels, full-frame coordinates, y down          */
+    float u0, v0, u1, v1; /* normalised atlas coordinates at (x0, y0) / (x1, y1)      */
+    float rgba[4];        /* TextVertex::m_Color                                       */
+} tri_text_quad;
+#define TRI_MAX_TEXT_QUADS 65536u
+
+/* The quads every following tri_render of ctx composites over its frame, until the next tri_set_text. The array is
+ * copied (free on return; safe with frames in flight). count == 0 or font == NULL removes the overlay. A row-band
+ * context takes the same full-frame coordinates and composites its own rows only (also under tri_bind_output).
+ * While quads are set, tri_frame_alpha reports -1 (text changes the alpha channel). TRI_E_INVALID — the previous
+ * text stays — for null quads with a non-zero count, a count above TRI_MAX_TEXT_QUADS, a non-finite coordinate, a
+ * font on another device. */
+int tri_set_text(tri_ctx* ctx, tri_font* font, const tri_text_quad* quads, uint32_t count);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
@@ -552,6 +597,11 @@ int tri_group_upload_ai_frame(tri_group* group, const uint8_t* rgba8_unorm, uint
 int tri_group_set_shadow(tri_group* group, const tri_shadow_config* config);
 int tri_group_set_frame(tri_group* group, const tri_global_ubo* ubo, const float clear_rgba[4]);
 int tri_group_set_draws(tri_group* group, const tri_draw* draws, uint32_t draw_count);
+/* tri_set_text on every band with the same full-frame quads (each band composites its own rows). fonts: one atlas per
+ * distinct device of the group, in any order (as tri_group_bind_geometry's objects: a band takes the one on its
+ * device; TRI_E_INVALID — no band changed — if a band's device has none). fonts == NULL or count == 0 removes the
+ * overlay. */
+int tri_group_set_text(tri_group* group, tri_font* const* fonts, const tri_text_quad* quads, uint32_t count);
 /* Enqueue every band, then the assembly onto the display device (asynchronous). */
 int tri_group_render(tri_group* group);
 /* Wait for every band and the assembly; TRI_E_OVERFLOW as tri_synchronize (re-render the frame). */
@@ -600,6 +650,7 @@ static_assert(sizeof(tri_material_record) == 32, "MaterialUniformBuffer is 32 by
 static_assert(sizeof(tri_shadow_config) == 80, "tri_shadow_config layout");
 static_assert(sizeof(tri_group_config) == 32, "tri_group_config layout");
 static_assert(sizeof(tri_image) == 32, "tri_image layout");
+static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
 #endif
 
 #endif /* TRI_RASTER_H */
