@@ -1589,14 +1589,16 @@ __device__ __forceinline__ void raster_serial(const TriRec& r, int32_t cx0, int3
     }
 }
 
-// Span walk (the per-lane path of 32x32 bins, triangles under 64 px on a side): each row's covered pixels
+// Span walk (the per-lane path of 32x32 and 64x64 bins, triangles under 64 px on a side): each row's covered pixels
 // are the integer x with f_k(x) = F_k + A_k (x - cx0) >= 0 for k = 0..2, an interval [L, R] found from the
 // three crossings v_k = -F_k / A_k instead of testing every bbox pixel (the bbox of a C3 triangle is ~3x
 // its area). Exact: with |A_k| < 2^14, |F_k| < 2^22 (exact in float, and stepped by B_k exactly) and v_rcp's 1-ulp
 // reciprocal, t = fma(-F, 1/A, -/+delta) lies within 2^-16 of v -/+ delta for |v| <= 64, and a
 // non-integer v is at least 1/|A| > 2^-14 from every integer, so with delta = 2^-15 ceil(t) = ceil(v) on
 // the left (A > 0) and floor(t) = floor(v) on the right (A < 0), integer v included; crossings further
-// than 64 px lie outside the 32-px bin either way. A horizontal edge (A = 0) empties the row when F < 0
+// than 64 px lie outside the bin either way, at 64-px bins too: x - cx0 runs over [0, wmax] with wmax <= 63, since
+// cx0 >= the bin's first column, and the bounds on A_k and F_k come from the triangle's own box (under 64 px),
+// not from the bin's (tests/test_raster_paths_gpu.py walks it at 64 px). A horizontal edge (A = 0) empties the row when F < 0
 // (scale 2^100 on the left side). Then the same keys as raster_serial over [L, R] only.
 template <int BL>
 __device__ __forceinline__ void raster_span(const TriRec& r, int32_t cx0, int32_t cx1, int32_t cy0, int32_t cy1,

@@ -304,3 +304,425 @@ def near_clip_single(w=640, h=480, n=60, shadow=False):
     if shadow:
         scenes.with_shadow(s, 512)
     return s
+
+
+# ---- raster paths chosen by a threshold (frame size, density, a queue capacity) --------------------
+def expected_bin_size(w, band_rows, h, nprims):
+    """The bin grid tri_render chooses (choose_bin_grid, restated): 64-px bins once the context would hold more than
+    16384 bins of 32 px; 16-px bins on small grids (fewer than 4096 bins of 32 px) of sparse frames (fewer than 0.05
+    triangles per pixel of the WHOLE frame, while the bins count the band's rows only); 32-px bins otherwise."""
+    n32 = -(-w // 32) * -(-band_rows // 32)
+    if n32 > 16384:
+        return 64
+    if n32 < 4096 and nprims / (w * h) < 0.05:
+        return 16
+    return 32
+
+
+def counted_triangles(w=320, h=240, ntris=3840):
+    """The spinning cube's twelve triangles repeated up to exactly `ntris` primitives: a frame whose only
+    interesting property is its primitive count (the density threshold of the bin grid)."""
+    s = scenes.scene_c1_cube(1, w, h)
+    s.indices = np.tile(s.indices, -(-ntris // 12))[:3 * ntris].copy()
+    s.meshes = np.array([(0, 3 * ntris, 0, 0)], abi.MESH_RANGE_DTYPE)
+    s.skybox = None
+    s.name = f"counted_{ntris}"
+    return s
+
+
+def _pixel_scene(name, w, h, pos, rng):
+    """World x, y in pixels under the orthographic mapping of pixel_aligned_triangles; pos: float [n, 3, 3]."""
+    n = pos.shape[0]
+    v = np.zeros(3 * n, abi.VERTEX_DTYPE)
+    v["position"] = np.asarray(pos, F).reshape(-1, 3)
+    v["normal"] = (0, 0, 1)
+    v["color"] = rng.uniform(0.2, 1.0, size=(3 * n, 3)).astype(F)
+    v["texcoord"] = rng.uniform(0, 1, size=(3 * n, 2)).astype(F)
+    idx = np.arange(3 * n, dtype=np.uint32)
+    meshes = np.array([(0, idx.size, 0, 0)], abi.MESH_RANGE_DTYPE)
+    view = np.eye(4, dtype=F)
+    proj = np.eye(4, dtype=F)
+    proj[0, 0], proj[3, 0] = F(2.0 / w), F(-1.0)
+    proj[1, 1], proj[3, 1] = F(2.0 / h), F(-1.0)
+    cam = (w / 2.0, h / 2.0, 50.0)
+    draws = [abi.make_draw(0, np.eye(4, dtype=F), material_index=0)]
+    return scenes.Scene(name, w, h, v, idx, meshes, draws, scenes.pack_ubo(view, proj, cam, []),
+                        materials=[((1, 1, 1, 1), (0.1, 0.5, 1.0, 0.0))])
+
+
+def snapped_xy(scene):
+    """The 24.8 fixed-point vertex positions of an orthographic single-draw scene with identity model and view,
+    recomputed in float32 from DESIGN §4's rules: clip = P * p summed term by term, x_d = x_c * (1 / w_c),
+    x_f = x_d * W/2 + W/2, X = rint(x_f * 256). Returns int64 X, Y per vertex record."""
+    P = np.array(scene.ubo.projection, F).reshape(4, 4)  # [col][row]
+    p = scene.vertices["position"].astype(F)
+    out = []
+    for row, half in ((0, F(scene.width) * F(0.5)), (1, F(scene.height) * F(0.5))):
+        c = F(P[0, row]) * p[:, 0]
+        c = (c + F(P[1, row]) * p[:, 1]).astype(F)
+        c = (c + F(P[2, row]) * p[:, 2]).astype(F)
+        c = (c + F(P[3, row])).astype(F)
+        f = ((c * F(1.0)).astype(F) * half + half).astype(F)
+        out.append(np.rint((f * F(256.0)).astype(F)).astype(np.int64))
+    return out[0], out[1]
+
+
+def bin_entry_counts(scene, bin_px, big_area=96):
+    """Per bin of bin_px pixels: how many set-up triangles (front-facing, a pixel centre inside the bounding box,
+    as DESIGN §4 sets a triangle up) an orthographic scene queues there, and how many of them are 'large' there
+    (bounding box inside the bin above big_area pixels). Counted from the snapped vertices alone."""
+    X, Y = snapped_xy(scene)
+    t = scene.indices.reshape(-1, 3).astype(np.int64)
+    X, Y = X[t], Y[t]
+    S = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (Y[:, 1] - Y[:, 0]) * (X[:, 2] - X[:, 0])
+    px0 = np.maximum(-((128 - X.min(1)) >> 8), 0)
+    px1 = np.minimum((X.max(1) - 128) >> 8, scene.width - 1)
+    py0 = np.maximum(-((128 - Y.min(1)) >> 8), 0)
+    py1 = np.minimum((Y.max(1) - 128) >> 8, scene.height - 1)
+    keep = (S < 0) & (px0 <= px1) & (py0 <= py1)
+    nbx, nby = -(-scene.width // bin_px), -(-scene.height // bin_px)
+    total = np.zeros((nby, nbx), np.int64)
+    large = np.zeros((nby, nbx), np.int64)
+    for a0, a1, b0, b1 in zip(px0[keep], px1[keep], py0[keep], py1[keep]):
+        for by in range(b0 // bin_px, b1 // bin_px + 1):
+            for bx in range(a0 // bin_px, a1 // bin_px + 1):
+                total[by, bx] += 1
+                cw = min(a1, bx * bin_px + bin_px - 1) - max(a0, bx * bin_px) + 1
+                ch = min(b1, by * bin_px + bin_px - 1) - max(b0, by * bin_px) + 1
+                large[by, bx] += cw * ch > big_area
+    return total, large
+
+
+def crowded_regions(w, h, bin_px=64):
+    """An interior bin, one in the last (ragged) column, one in the last row and the corner bin, as (bx, by)."""
+    nbx, nby = -(-w // bin_px), -(-h // bin_px)
+    return [(nbx // 3, nby // 3), (nbx - 1, nby // 2), (nbx // 2, nby - 1), (nbx - 1, nby - 1)]
+
+
+def crowded_bins(w=4100, h=4100, regions=None, per_region=640, seed=5, stack=1100, bin_px=64):
+    """Bins that hold far more entries than a workgroup has lanes, in the style of pixel_aligned_triangles
+    (orthographic, quarter-pixel vertices, random depths): per_region small triangles (2-12 px, both windings, so
+    more are emitted than survive the cull) centred inside the frame's part of each listed bin_px region, and over
+    the first region a stack of `stack` front-facing quads that each fill the bin (2 * stack large triangles in one
+    bin: more than the large-triangle queue of any instantiation holds, so the rest take the per-lane fallback).
+    Every region exceeds the initial per-bin capacity of the bin list (256 entries)."""
+    rng = np.random.default_rng(seed)
+    regions = crowded_regions(w, h, bin_px) if regions is None else regions
+    tris = []
+    for bx, by in regions:
+        x0, y0 = bx * bin_px, by * bin_px
+        x1, y1 = min(x0 + bin_px, w), min(y0 + bin_px, h)
+        made = 0
+        while made < per_region:
+            size = rng.uniform(2.0, 12.0)
+            cx, cy = rng.uniform(x0 + 0.5, x1 - 0.5), rng.uniform(y0 + 0.5, y1 - 0.5)
+            p = np.array([(cx + size * rng.uniform(-0.5, 0.5), cy + size * rng.uniform(-0.5, 0.5)) for _ in range(3)])
+            q = np.round(p * 4.0) / 4.0
+            S = (q[1, 0] - q[0, 0]) * (q[2, 1] - q[0, 1]) - (q[1, 1] - q[0, 1]) * (q[2, 0] - q[0, 0])
+            z = rng.uniform(0.05, 0.95, size=3)
+            tris.append([(q[i, 0], q[i, 1], z[i]) for i in range(3)])
+            # a front-facing triangle whose box holds a pixel centre of the region's own pixels is an entry
+            inside = (np.floor(q[:, 0].max() - 0.5) >= np.ceil(max(q[:, 0].min(), x0) - 0.5)) and \
+                     (np.floor(q[:, 1].max() - 0.5) >= np.ceil(max(q[:, 1].min(), y0) - 0.5)) and \
+                     np.ceil(q[:, 0].min() - 0.5) <= x1 - 1 and np.ceil(q[:, 1].min() - 0.5) <= y1 - 1
+            made += bool(S < 0 and inside)
+    bx, by = regions[0]
+    for _ in range(stack):
+        j = rng.integers(0, 33, size=4) * 0.25  # the quad overhangs the bin by 0 .. 8 px on each side
+        x0, y0 = bx * bin_px - j[0], by * bin_px - j[1]
+        x1, y1 = bx * bin_px + bin_px + j[2], by * bin_px + bin_px + j[3]
+        z = rng.uniform(0.05, 0.95, size=4)
+        c = [(x0, y0, z[0]), (x1, y0, z[1]), (x1, y1, z[2]), (x0, y1, z[3])]
+        tris.append([c[0], c[2], c[1]])
+        tris.append([c[0], c[3], c[2]])
+    order = rng.permutation(len(tris))  # large and small entries interleaved in primitive order
+    s = _pixel_scene("crowded_bins", w, h, np.asarray(tris, np.float64)[order], rng)
+    return s
+
+
+def stacked_quads(w, h, n=1100, draws=1, textured=False, seed=9, box=None):
+    """n front-facing quads (2 n large triangles) stacked over one box of the frame (default: the 40 x 40 px around
+    its centre, overhanging by up to 6 px), random per-vertex depths: one bin holds more large triangles than the
+    large-triangle queue of any instantiation (192, 512 or 1024 entries) and more entries than the initial bin-list
+    capacity. draws > 1 splits the index range into that many draws."""
+    rng = np.random.default_rng(seed)
+    bx0, by0, bx1, by1 = box if box is not None else (w // 2 - 20, h // 2 - 20, w // 2 + 20, h // 2 + 20)
+    tris = []
+    for _ in range(n):
+        j = rng.integers(0, 25, size=4) * 0.25
+        x0, y0, x1, y1 = bx0 - j[0], by0 - j[1], bx1 + j[2], by1 + j[3]
+        z = rng.uniform(0.05, 0.95, size=4)
+        c = [(x0, y0, z[0]), (x1, y0, z[1]), (x1, y1, z[2]), (x0, y1, z[3])]
+        tris.append([c[0], c[2], c[1]])
+        tris.append([c[0], c[3], c[2]])
+    s = _pixel_scene(f"stacked_quads_{draws}", w, h, np.asarray(tris, np.float64), rng)
+    if draws > 1:
+        cuts = [(k * 2 * n // draws) * 3 for k in range(draws + 1)]
+        s.meshes = np.array([(a, b - a, 0, 0) for a, b in zip(cuts[:-1], cuts[1:])], abi.MESH_RANGE_DTYPE)
+        s.draws = [abi.make_draw(k, np.eye(4, dtype=F), material_index=0,
+                                 tint=(1.0 - 0.1 * k, 0.6 + 0.1 * k, 0.8, 1.0)) for k in range(draws)]
+    if textured:
+        s.textures = [(2, checker_texture(8, 16, 4))]
+        for d in s.draws:
+            d.pc.texture_slot = 2
+    return s
+
+
+# ---- dense homogeneous clipping ----------------------------------------------------------------------
+CLIP_WMIN, CLIP_GUARD_PX = 1e-5, 16000.0  # the clip planes of DESIGN §4: w >= 1e-5, z >= 0, |x_fb|, |y_fb| <= 16000 px
+
+
+def clip_polygon_sizes(scene):
+    """Float64 Sutherland-Hodgman over the six clip planes (w >= WMIN, z >= 0, the guard band), per triangle of
+    the scene that is not trivially rejected and has a vertex outside a plane: the clipped polygon's vertex
+    count (0: nothing left). Written from the plane list alone, after tests/test_oracle_clip_f64.py's clipper."""
+    W, H = scene.width, scene.height
+    gx, gy = 2.0 * CLIP_GUARD_PX / W - 1.0, 2.0 * CLIP_GUARD_PX / H - 1.0
+    planes = [lambda c: c[3] - CLIP_WMIN, lambda c: c[2], lambda c: c[0] + gx * c[3], lambda c: gx * c[3] - c[0],
+              lambda c: c[1] + gy * c[3], lambda c: gy * c[3] - c[1]]
+    reject = [lambda c: c[2], lambda c: c[3] - c[2], lambda c: c[0] + c[3], lambda c: c[3] - c[0],
+              lambda c: c[1] + c[3], lambda c: c[3] - c[1]]
+    view = np.array(scene.ubo.view, np.float64).reshape(4, 4).T
+    proj = np.array(scene.ubo.projection, np.float64).reshape(4, 4).T
+    pos = scene.vertices["position"].astype(np.float64)
+    sizes = []
+    for d in scene.draws:
+        m = scene.meshes[d.mesh_index]
+        mvp = proj @ view @ np.array(d.pc.model, np.float64).reshape(4, 4).T
+        first, count, base = int(m["first_index"]), int(m["index_count"]), int(m["base_vertex"])
+        tri = scene.indices[first:first + count - count % 3].reshape(-1, 3).astype(np.int64) + base
+        clip = np.concatenate([pos, np.ones((pos.shape[0], 1))], 1) @ mvp.T
+        for t in tri:
+            c = [clip[i] for i in t]
+            if any(all(f(v) < 0 for v in c) for f in reject):
+                continue
+            if all(f(v) >= 0 for v in c for f in planes):
+                continue
+            poly = c
+            for f in planes:
+                out = []
+                for i in range(len(poly)):
+                    a, b = poly[i], poly[(i + 1) % len(poly)]
+                    da, db = f(a), f(b)
+                    if da >= 0:
+                        out.append(a)
+                    if (da >= 0) != (db >= 0):
+                        out.append(a + da / (da - db) * (b - a))
+                poly = out
+                if not poly:
+                    break
+            sizes.append(len(poly))
+    return np.array(sizes, np.int64)
+
+
+def dense_clip(w=320, h=240, cells=36, size=(3.0, 30.0), pairs=True, guard=True, seed=21, two_behind=True):
+    """Thousands of small triangles cut by the near plane, interleaved on screen with unclipped ones.
+
+    The camera sits at the origin looking down -z (world space is view space), near plane 0.1. Each of cells x cells
+    jittered screen cells gets one triangle of size[0] .. size[1] pixels with one vertex behind the near plane and two
+    in front of it (a 4-vertex polygon, two fan sub-triangles) and, with pairs, an unclipped triangle of like size
+    overlapping it just beyond the plane, so bin rows hold both kinds. About four in five face the camera; with
+    two_behind every fifth clipped one has two vertices behind the plane (a 3-vertex polygon). With guard, two more groups follow:
+    16 slivers that reach beyond an x and a y guard-band plane (near + guard planes: 5-vertex polygons, fan
+    sub-triangles 1..3), and four frame-filling sheets behind everything, cut by the near plane and all four guard
+    planes (8 vertices, sub-triangles 1..6), so every pixel of the frame has a clipped fragment under the small
+    triangles. TRI_MAX_CLIP_POLY = 9 vertices are out of reach of a scene: the sixth plane, w >= 1e-5, adds a vertex
+    only where it cuts off a corner that the guard planes |x|, |y| <= g w leave, and those meet at w = 0, so its edge
+    would be at most 2 g 1e-5 clip units long (and under a perspective projection z >= 0 implies w >= near)."""
+    rng = np.random.default_rng(seed)
+    fov, near, far = 70.0, 0.1, 40.0
+    th = near * np.tan(np.radians(fov) / 2.0)  # half-height of the near rectangle
+    tw = th * w / h
+    px = 2.0 * th / h  # one pixel at the near plane, in world units
+
+    def facing(p):
+        """float [n, 3, 3] triangles: counter-clockwise as the camera sees them with probability 0.8 (the perspective
+        divide keeps the sense of a triangle's part in front of the eye)."""
+        q = p[..., :2] / -p[..., 2:3]
+        ccw = (q[:, 1, 0] - q[:, 0, 0]) * (q[:, 2, 1] - q[:, 0, 1]) - (q[:, 1, 1] - q[:, 0, 1]) * (q[:, 2, 0] - q[:, 0, 0]) > 0
+        flip = ccw != (rng.random(p.shape[0]) < 0.8)
+        p[flip] = p[flip][:, [0, 2, 1]]
+        return p
+
+    n = cells * cells
+    u = rng.random((13, n))
+    jj, ii = np.divmod(np.arange(n), cells)
+    cx = (-1.0 + 2.0 * (ii + 0.2 + 0.6 * u[0]) / cells) * tw
+    cy = (-1.0 + 2.0 * (jj + 0.2 + 0.6 * u[1]) / cells) * th
+    s = (size[0] + (size[1] - size[0]) * u[2]) * px
+    ang = 2 * np.pi * u[3]
+    zb = -(near - (0.002 + 0.008 * u[4])) * np.ones(n)  # behind the near plane
+    behind = np.stack([cx, cy, zb], -1)
+    front = [np.stack([cx + s * np.cos(ang + a), cy + s * np.sin(ang + a), -(near + 0.002 + 0.01 * u[5 + k])], -1)
+             for k, a in enumerate((-0.5, 0.5))]
+    clipped = np.stack([behind, front[0], front[1]], 1)
+    if two_behind:  # every fifth: two vertices behind, one in front (a 3-vertex polygon)
+        k5 = np.arange(n) % 5 == 4
+        clipped[k5] = np.stack([front[0], np.stack([cx - 0.3 * s, cy + 0.2 * s, zb], -1), behind], 1)[k5]
+    groups = [facing(clipped)]
+    if pairs:  # an unclipped triangle of like size over each clipped one, just beyond the plane
+        zz = -(near + 0.004 + 0.016 * u[7])
+        s2 = (size[0] + (size[1] - size[0]) * u[8]) * px * (-zz / near)
+        a2 = 2 * np.pi * u[9]
+        ox, oy = (0.6 * u[10] - 0.3) * s, (0.6 * u[11] - 0.3) * s
+        dz = 0.004 * rng.random((3, n))
+        groups.append(facing(np.stack([np.stack([cx + ox + s2 * np.cos(a2 + a), cy + oy + s2 * np.sin(a2 + a), zz - dz[k]], -1)
+                                       for k, a in enumerate((0.0, 2.1, 4.2))], 1)))
+    tris = list(np.stack(groups, 1).reshape(-1, 3, 3))  # clipped, unclipped, clipped, ... in primitive order
+
+    def facing1(p):
+        return [tuple(q) for q in facing(np.array(p, np.float64)[None])[0]]
+
+    if guard:
+        gx, gy = 2.0 * CLIP_GUARD_PX / w - 1.0, 2.0 * CLIP_GUARD_PX / h - 1.0
+        f = 1.0 / np.tan(np.radians(fov) / 2.0)
+        wb = near + 0.05  # clip w of the far vertices
+
+        def at_ndc(nx, ny, cw):  # the view-space point of clip w cw that projects to (nx, ny)
+            return np.array([nx * cw * (w / h) / f, ny * cw / f, -cw])
+
+        for k in range(16):  # slivers: near + one x and one y guard plane
+            sx, sy = (1, -1)[k & 1], (1, -1)[(k >> 1) & 1]
+            B = at_ndc(sx * 1.2 * gx, sy * 0.9 * gy, wb)
+            C = at_ndc(sx * 0.9 * gx, sy * 1.2 * gy, wb)
+            t = 0.01
+            P = np.array([rng.uniform(-0.7, 0.7) * tw, rng.uniform(-0.7, 0.7) * th, -near])
+            A = (P - t * 0.5 * (B + C)) / (1.0 - t)
+            A[2] = -(near - t / (1.0 - t) * 0.05)
+            tris.append(facing1([A, B, C]))
+        # Four sheets behind everything else, each cut by the near plane and all four guard planes (8 vertices). In
+        # guard-band units the visible part of a sheet projects to the quadrilateral N1 (0, -1.5), B (1.5, 0.3),
+        # C (0.3, 1.5), N2 (-1.5, 0), whose every corner lies outside the guard square while every edge crosses it; N1
+        # and N2 are where the edges from B and C towards A meet the near plane. A lies behind the eye (w < 0) and
+        # projects to A' = (7.5, 7.5) = N1 + 5 (B - N1) = N2 + 5 (C - N2), so with w_B = w_C = 0.3 the near plane is
+        # met at t * w_B = 1.25 * near, (1 - t) * w_A = -0.25 * near. The four are quarter turns of one sheet about
+        # the view axis: the same depth at the frame's centre, tilted four ways, so each shows in a part of the frame;
+        # their vertex order rotates, so the fan's first vertex differs.
+        ws = 0.3
+        t = 1.25 * near / ws
+        wa = -0.25 * near / (1.0 - t)
+        for k in range(4):
+            rot = [lambda x, y: (x, y), lambda x, y: (-y, x), lambda x, y: (-x, -y), lambda x, y: (y, -x)][k]
+            p = [at_ndc(*(np.array(rot(x, y)) * (gx, gy)), cw) for x, y, cw in ((7.5, 7.5, wa), (1.5, 0.3, ws), (0.3, 1.5, ws))]
+            p = [tuple(q) for q in p]
+            tris.append(p[k % 3:] + p[:k % 3])  # counter-clockwise as built: quarter turns keep the sense
+    n = len(tris)
+    v = np.zeros(3 * n, abi.VERTEX_DTYPE)
+    v["position"] = np.asarray(tris, F).reshape(-1, 3)
+    v["normal"] = (0, 0, 1)
+    v["color"] = rng.uniform(0.3, 1.0, size=(3 * n, 3)).astype(F)
+    v["texcoord"] = rng.uniform(0, 2, size=(3 * n, 2)).astype(F)
+    idx = np.arange(3 * n, dtype=np.uint32)
+    cam = (0.0, 0.0, 0.0)
+    view, proj = scenes.editor_camera(cam, (0.0, 0.0, 0.0), fov, (w, h), near, far)
+    lights = [{"type": "directional", "direction": (-0.3, -0.4, -1.0), "intensity": 3.0},
+              {"type": "point", "position": (0.02, 0.03, 0.0), "range": 1.0, "intensity": 4.0}]
+    return scenes.Scene(f"dense_clip_{w}x{h}_{cells}", w, h, v, idx, np.array([(0, idx.size, 0, 0)], abi.MESH_RANGE_DTYPE),
+                        [abi.make_draw(0, np.eye(4, dtype=F), material_index=0)],
+                        scenes.pack_ubo(view, proj, cam, lights), materials=[((0.9, 0.9, 0.9, 1.0), (0.3, 0.5, 1.0, 0.0))])
+
+
+def dense_clip_multi(w=320, h=240, shadow=False, **kw):
+    """dense_clip as three textured draws over thirds of its index range, the second and third under small
+    translations of their own (the clipper reads prim_vs and the draw carried in the record); shadow: with the
+    pre-pass for the scene's sun (the clipper interpolates light-space positions)."""
+    s = dense_clip(w, h, **kw)
+    n = s.indices.size // 3
+    cuts = [0, (n // 3) * 3, (2 * n // 3) * 3, n * 3]
+    s.meshes = np.array([(a, b - a, 0, 0) for a, b in zip(cuts[:-1], cuts[1:])], abi.MESH_RANGE_DTYPE)
+    s.textures = [(1, checker_texture(16, 8, 3)), (2, checker_texture(8, 16, 4))]
+    s.draws = [abi.make_draw(0, np.eye(4, dtype=F), texture_slot=1, material_index=0),
+               abi.make_draw(1, scenes.compose_transform((0.0004, -0.0003, 0.0), (0, 0, 0)), texture_slot=2,
+                             material_index=0, tint=(0.9, 1.0, 0.8, 1.0)),
+               abi.make_draw(2, scenes.compose_transform((-0.0003, 0.0002, 0.0002), (0, 0, 0)), texture_slot=1,
+                             material_index=0)]
+    s.name = f"{s.name}_multi{'_shadow' if shadow else ''}"
+    if shadow:
+        scenes.with_shadow(s, 256)
+    return s
+
+
+def clip_flood(w=320, h=240, cells=185):
+    """cells^2 thin triangles (1-4 px) that each cross the near plane with one vertex behind it (4
+    polygon vertices, 2 clip records): 185^2 = 34225 triangles ask for more clip records than the initial 65536 and
+    more polygon vertices than the initial 131072 (tri_ctx::ovf_rec_cap, ovf_vert_cap)."""
+    s = dense_clip(w, h, cells=cells, size=(1.0, 4.0), pairs=False, guard=False, seed=23, two_behind=False)
+    s.name = f"clip_flood_{cells}"
+    return s
+
+
+CLIP_RECORD_CAP, CLIP_VERTEX_CAP = 1 << 16, 1 << 17  # tri_ctx's initial ovf_rec_cap, ovf_vert_cap
+
+
+def shadow_stack(w=320, h=240, size=256, n=400):
+    """A ground quad under n small horizontal quads stacked along the sun's direction: in the light's view all 2 n
+    caster triangles fall on the same few texels, so one 32 x 32 bin of the size^2 map holds more entries than the
+    map queues' initial capacity (256), while on screen the stack is spread over many bins."""
+    sun = np.array((-0.45, -1.0, -0.35))
+    u = sun / np.linalg.norm(sun)
+    quads = [np.array([(-6, 0, 6), (6, 0, 6), (6, 0, -6), (-6, 0, -6)], np.float64)]
+    for k in range(n):
+        c = np.array((0.5, 0.3, -0.5)) - u * (0.4 + 0.008 * k)
+        r = 0.25 + 0.0003 * k
+        quads.append(c + np.array([(-r, 0, r), (r, 0, r), (r, 0, -r), (-r, 0, -r)]))
+    q = np.asarray(quads)
+    v = np.zeros(4 * len(quads), abi.VERTEX_DTYPE)
+    v["position"] = q.reshape(-1, 3).astype(F)
+    v["normal"] = (0, 1, 0)
+    v["color"] = np.random.default_rng(3).uniform(0.4, 1.0, size=(v.size, 3)).astype(F)
+    v["texcoord"] = np.tile(np.array([(0, 0), (1, 0), (1, 1), (0, 1)], F), (len(quads), 1))
+    base = 4 * np.arange(len(quads), dtype=np.uint32)[:, None]
+    idx = (base + np.array([0, 1, 2, 0, 2, 3], np.uint32)).reshape(-1)
+    cam = (0.0, 4.0, 8.0)
+    view, proj = scenes.editor_camera(cam, (-25.0, 0.0, 0.0), 60.0, (w, h))
+    lights = [{"type": "directional", "direction": tuple(sun), "intensity": 4.0}]
+    s = scenes.Scene("shadow_stack", w, h, v, idx, np.array([(0, idx.size, 0, 0)], abi.MESH_RANGE_DTYPE),
+                     [abi.make_draw(0, np.eye(4, dtype=F), material_index=0)], scenes.pack_ubo(view, proj, cam, lights),
+                     materials=[((0.9, 0.85, 0.8, 1.0), (0.1, 0.6, 1.0, 0.0))], skybox=SOLID_0x808080)
+    return scenes.with_shadow(s, size)
+
+
+def grid_switch_pair(w=320, h=240, sparse_n=24, dense_n=60):
+    """The C3 grid at two tessellations in ONE geometry (mesh 0: 2 (sparse_n - 1)^2 triangles, below 0.05 per pixel;
+    mesh 1: 2 (dense_n - 1)^2, above), so that a draw list alone moves a context between the 16- and the 32-px bin
+    grid. Returns (sparse scene, dense scene): the same buffers and mesh table, one draw each."""
+    a, b = grid_c3(w, h, sparse_n), grid_c3(w, h, dense_n)
+    verts = np.concatenate([a.vertices, b.vertices])
+    idx = np.concatenate([a.indices, b.indices])
+    meshes = np.array([(0, a.indices.size, 0, 0), (a.indices.size, b.indices.size, a.vertices.size, 0)],
+                      abi.MESH_RANGE_DTYPE)
+    out = []
+    for k, s in enumerate((a, b)):
+        s.vertices, s.indices, s.meshes = verts, idx, meshes
+        s.draws = [abi.make_draw(k, np.eye(4, dtype=F), material_index=0)]
+        s.skybox = None
+        s.name = f"switch_{'dense' if k else 'sparse'}"
+        out.append(s)
+    return tuple(out)
+
+
+def textured_two_draws(w=4100, h=4100, n=40):
+    """textured_grid plus a second, tinted draw of the same mesh through another sRGB slot, pushed back and sideways
+    so both show: several draws with a texture LUT and per-draw transforms."""
+    s = textured_grid(w, h, n)
+    s.textures = s.textures + [(5, checker_texture(8, 16, 4))]
+    s.draws = s.draws + [abi.make_draw(0, scenes.compose_transform((1.1, 0.4, 0.35), (0.0, 8.0, 0.0), (1, 1, 1)),
+                                       texture_slot=5, material_index=0, tint=(0.7, 1.0, 0.9, 1.0), tiling=0.5)]
+    s.skybox = None
+    s.name = f"textured_two_{w}x{h}"
+    return s
+
+
+def ai_multi(oracle, w=4100, h=4100, ai_extent=(96, 160), strength=0.35):
+    """primitives_row (three draws) under the AI blend, the AI frame of another extent than the frame and addressed
+    with the frame's own 1 / extent, so it is filtered up to the frame."""
+    s = primitives_row(oracle, w, h)
+    # a fourth draw: the quad primitive as a backdrop that fills the frame, so the blend reaches every bin
+    s.draws = s.draws + [abi.make_draw(2, oracle.compose_transform((0.0, 3.0, -2.0), (0.0, 0.0, 0.0), (40.0, 40.0, 1.0)),
+                                       texture_slot=0, material_index=1, tint=(0.6, 0.7, 0.9, 1.0))]
+    ai =np.random.default_rng(0xA1).integers(0, 256, size=(ai_extent[0], ai_extent[1], 4), dtype=np.uint8)
+    scenes.with_ai_blend(s, strength=strength, ai_frame=ai)
+    s.ubo.ai_blend_config[1] = F(1.0) / F(w)
+    s.ubo.ai_blend_config[2] = F(1.0) / F(h)
+    s.name = f"ai_multi_{w}x{h}"
+    return s

@@ -243,8 +243,10 @@ def test_texture_upload_switches_specialised_raster(oracle, flags):
         assert int(np.abs(col.astype(np.int16) - oc.astype(np.int16)).max()) <= COLOR_TOL, scene.name
 
 
-def test_bin_overflow_grows_and_recovers():
-    """A frame that overflows the bin list reports TRI_E_OVERFLOW, grows, and re-renders correctly."""
+def test_bin_overflow_grows_and_recovers(oracle):
+    """A frame that overflows the bin list reports TRI_E_OVERFLOW, grows, and re-renders correctly: the re-rendered
+    frame (400 frame-sized cubes on 16-px bins, more large triangles per bin than the large-triangle queue holds)
+    meets the parity bar against the oracle."""
     from trident_raster import abi, raster, scenes
 
     s = sc.grid_c3(1280, 720, 300)
@@ -265,7 +267,14 @@ def test_bin_overflow_grows_and_recovers():
             r.synchronize()
         assert ei.value.code == abi.TRI_E_OVERFLOW
         r.render_frame()  # grown buffers: succeeds
+        gc, gd = r.readback()
+        gs = r.frame_stats()
     assert ref[0].shape == (720, 1280, 4)
+    oc, od, os_ = oracle.render(s2)
+    assert gs["bin_size"] == 16
+    assert int((gd != od).sum()) == 0
+    assert int(np.abs(gc.astype(np.int16) - oc.astype(np.int16)).max()) <= COLOR_TOL
+    assert gs["triangles_setup"] == os_["triangles_setup"], (gs, os_)
 
 
 @pytest.mark.parametrize("case", ["grid_turned", "primitives", "invalid", "skinned", "near_clip", "dense",
