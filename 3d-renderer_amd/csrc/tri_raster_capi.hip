@@ -85,6 +85,7 @@ struct tri_geometry {
     bool obj_ok = false;
     bool uni_col = false;  // every vertex has the colour ucol (TriFrameParams::obj_ucol)
     float ucol[3] = {0.0f, 0.0f, 0.0f};
+    float uv_abs[2] = {0.0f, 0.0f};  // max |u|, |v| over the vertices (infinite if any is not finite)
     uint64_t nverts = 0;
     uint32_t* d_idx = nullptr; size_t cap_idx = 0;
     uint64_t nidx = 0;
@@ -159,6 +160,7 @@ struct tri_ctx {
     uint32_t ndraws = 0, nslots = 0, nprims = 0;
     bool any_skin = false;
     TriDrawDev draw0{};  // the resolved draw when there is exactly one (passed by value to the kernels)
+    float uv_texels = 0.0f;    // the active textured draws' largest |uv| in texels (see kUvFastTexels)
     bool draw0_obj = false;    // draw0 may keep object-space varyings (draw_obj_ok)
     bool draw0_xform = false;  // ... and its model matrix is not the identity
     bool draw0_ucol = false;   // ... and every vertex of its geometry has one colour
@@ -285,6 +287,16 @@ bool draw_obj_ok(const tri_geometry& g, const TriDrawDev& d) {
     return std::fabs(dot(0, 0) - s2) <= tol && std::fabs(dot(1, 1) - s2) <= tol && std::fabs(dot(2, 2) - s2) <= tol &&
            std::fabs(dot(0, 1)) <= tol && std::fabs(dot(0, 2)) <= tol && std::fabs(dot(1, 2)) <= tol;
 }
+
+// The fast build interpolates a fragment's varyings with weights that carry an absolute error of a few 2^-24 each
+// (fast_weights) in a contracted sum, the oracle with exactly rounded ones in its own order. On texture coordinates
+// of magnitude M texels the two forms place the bilinear taps about M * 2^-21 texels apart (three weights, the
+// reciprocal of their sum, the sum's order): nothing at the M of ordinary content, 2^-8 texel at M = 2^13, one
+// byte-level of a full-contrast texel pair, and from there on past the 1-LSB bar (an offset of 4096 over a 6 x 10
+// texture: 6 LSB). Float32 coordinates of that size resolve the texture no finer than that themselves, so only the
+// oracle's own operation order defines the frame: beyond this many texels a frame takes the exact instantiation
+// (interp_exact over exact_weights), whatever the context's flags. 4 x a 2048^2 texture (C5) is still within.
+constexpr float kUvFastTexels = 8192.0f;
 
 // Default.frag frame constants hoisted for the fast shading build (Default.frag:131-174).
 void shade_constants(const tri_global_ubo& g, const tri_material_record& m, TriShadeConst& sc) {
@@ -443,6 +455,7 @@ int resolve_draws(tri_ctx* c) {
     std::vector<uint32_t> vb(n + 1), pb(n + 1), cbase(n + 1);
     uint64_t vslots = 0, prims = 0, ncl = 0;
     bool skin = false;
+    float uv_texels = 0.0f;
     for (uint32_t d = 0; d < n; ++d) {
         const tri_draw& src = c->draws[d];
         TriDrawDev& o = dd[d];
@@ -480,7 +493,15 @@ int resolve_draws(tri_ctx* c) {
         prims += mr.index_count / 3;
         ncl += o.ncl;
         skin = skin || (o.bone_count > 0);
+        if (sh.tex.w != 1 || sh.tex.h != 1) {  // a filtered texture: how far from the origin its taps can lie
+            const float ext[2] = {(float)sh.tex.w, (float)sh.tex.h};
+            for (int k = 0; k < 2; ++k) {
+                const float t = (c->geom->uv_abs[k] * std::fabs(o.tex_scale[k] * o.tiling) + std::fabs(o.tex_offset[k])) * ext[k];
+                uv_texels = t <= uv_texels ? uv_texels : (std::isfinite(t) ? t : INFINITY);
+            }
+        }
     }
+    c->uv_texels = uv_texels;
     vb[n] = (uint32_t)vslots;
     pb[n] = (uint32_t)prims;
     cbase[n] = (uint32_t)ncl;
@@ -746,7 +767,12 @@ int geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uin
     std::vector<TriVsIn> vin(nv);
     std::vector<TriVsSkin> skin;
     bool has_skin = false, obj_ok = true;
+    float uv_abs[2] = {0.0f, 0.0f};
     for (uint64_t i = 0; i < nv; ++i) {
+        for (int k = 0; k < 2; ++k) {
+            const float t = std::fabs(v[i].texcoord[k]);
+            uv_abs[k] = t <= uv_abs[k] ? uv_abs[k] : (std::isfinite(t) ? t : INFINITY);
+        }
         const tri_vertex& s = v[i];
         TriVsIn& o = vin[i];
         o.px = s.position[0]; o.py = s.position[1]; o.pz = s.position[2];
@@ -770,6 +796,7 @@ int geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uin
     }
     g->has_skin_data = has_skin;
     g->obj_ok = obj_ok;
+    g->uv_abs[0] = uv_abs[0]; g->uv_abs[1] = uv_abs[1];
     g->uni_col = nv > 0;
     for (uint64_t i = 0; i < nv && g->uni_col; ++i)
         g->uni_col = vin[i].cr == vin[0].cr && vin[i].cg == vin[0].cg && vin[i].cb == vin[0].cb;
@@ -1454,7 +1481,9 @@ int tri_render(tri_ctx* c) {
     fp.bone_count = c->nbones;
     fp.clear_bgra = c->clear_bgra;
     fp.write_depth = (c->cfg.flags & TRI_FLAG_NO_DEPTH_OUTPUT) ? 0u : 1u;
-    fp.exact_shading = (c->cfg.flags & TRI_FLAG_EXACT_SHADING) ? 1u : 0u;
+    // ... and frames whose texture coordinates reach beyond kUvFastTexels texels, in either build
+    fp.exact_shading = ((c->cfg.flags & TRI_FLAG_EXACT_SHADING) || !(c->uv_texels <= kUvFastTexels)) ? 1u : 0u;
+    if (fp.exact_shading) c->last_path |= TRI_PATH_EXACT;
     fp.sky_size = c->sky_size;
     if (c->sky_size) {
         sky_constants(c->ubo, fp.sky_ip, fp.sky_R, fp.sky_pw);

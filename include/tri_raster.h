@@ -169,6 +169,7 @@ typedef struct tri_frame_stats {
 #define TRI_PATH_SHADOW    0x10u  /* the shadow-map pre-pass ran                                            */
 #define TRI_PATH_OBJ48     0x20u  /* object-space varyings outside the single-draw solid instantiation      */
 #define TRI_PATH_IDX_ROUTE 0x40u  /* several draws: vertex slots from the index buffer, no per-primitive record */
+#define TRI_PATH_EXACT     0x80u  /* the exact instantiation shaded it: TRI_FLAG_EXACT_SHADING, or uvs beyond 8192 texels */
 
 /* Shadow-map pre-pass (BASELINE.json config 5). The reference reserves the switch
  * (LightComponent::m_ShadowCaster, Trident/src/ECS/Components/LightComponent.h:33) but renders no shadow

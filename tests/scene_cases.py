@@ -726,3 +726,123 @@ def ai_multi(oracle, w=4100, h=4100, ai_extent=(96, 160), strength=0.35):
     s.ubo.ai_blend_config[2] = F(1.0) / F(h)
     s.name = f"ai_multi_{w}x{h}"
     return s
+
+
+# ---- fragment-stage sweep: materials, light rigs, texture addressing ---------------------------------------------
+# (base RGBA), (metallic, roughness, ambient strength, 0): metallic 0 and 1, the roughness clamp at either end, factors
+# outside [0, 1] (clamped by Default.frag), HDR base colours, alpha above 1 and below
+SWEEP_MATERIALS = [
+    ((0.9, 0.75, 0.6, 1.0), (0.0, 0.0, 1.0, 0.0)),
+    ((0.9, 0.75, 0.6, 1.3), (1.0, 0.045, 0.0, 0.0)),
+    ((1.0, 1.0, 1.0, 0.4), (1.0, 1.0, 2.0, 0.0)),
+    ((0.9, 0.75, 0.6, 1.0), (0.5, 0.3, 1.0, 0.0)),
+    ((0.0, 0.0, 0.0, 1.0), (1.5, 1.7, -1.0, 0.0)),
+    ((2.0, 1.5, 0.2, 1.0), (-0.5, 0.05, 0.5, 0.0)),
+]
+SWEEP_AMBIENT, SWEEP_AMBIENT_INTENSITY = (0.03, 0.05, 0.08), (1.0, 0.0, 3.0)  # the intensity rotates over the materials
+SWEEP_RIGS = ("eight", "eleven", "headon", "back", "touch")
+SWEEP_SUN_RIGS = ("headon", "back")
+SWEEP_VARIANTS = ("one", "one_vcol", "multi", "shadow")
+SWEEP_MULTI_TINT, SWEEP_MULTI_SLOT = (0.7, 1.0, 0.5, 1.2), 2
+TOUCH_RANGE_LIGHT = ((1.0, 1.0, 3.2), 0.8)  # the touch rig's light whose range boundary crosses the visible sphere
+
+
+def sweep_lights(rig):
+    """The light list of a rig (see shading_sphere)."""
+    if rig in ("eight", "eleven"):
+        ranges = (15.0, 6.0, 0.0, 2.0, 30.0, 8.0, 1e-5, 12.0)
+        intens = (6.0, 4.0, 5.0, 1e4, 0.0, 3.0, 5.0, 2.0)
+        colours = ((1.0, 0.98, 0.92), (0.2, 0.9, 0.4), (1.0, 0.1, 0.1), (0.9, 0.9, 1.0), (1.0, 1.0, 1.0),
+                   (0.0, 0.0, 0.0), (0.3, 0.3, 1.0), (1.0, 0.6, 0.1))
+        lights = [{"type": "point", "position": (4.0 * np.cos(0.785 * k), 4.0 * np.sin(0.785 * k), 3.0 + 0.3 * k),
+                   "range": ranges[k], "intensity": intens[k], "color": colours[k]} for k in range(8)]
+        # three more than TRI_MAX_POINT_LIGHTS: bright and close, so a frame that shaded them would show it
+        lights += [{"type": "point", "position": (0.5 * k - 0.5, -0.5, 4.0), "range": 20.0, "intensity": 40.0,
+                    "color": (0.2, 1.0, 0.2)} for k in range(3)]
+        return lights
+    if rig == "headon":  # the GGX peak at the sphere's centre, HDR radiance into the tone curve
+        return [{"type": "directional", "direction": (0.0, 0.0, -1.0), "intensity": 50.0}]
+    if rig == "back":  # N.L <= 0 on almost every visible pixel, L nearly opposite V; a light 1e-3 off the surface
+        return [{"type": "directional", "direction": (0.05, 0.03, 1.0), "intensity": 5.0},
+                {"type": "point", "position": (0.0, 0.0, 3.001), "range": 5.0, "intensity": 8.0}]
+    if rig == "touch":  # dist ~ 0, a range boundary across the visible surface, att reaching exactly 0
+        return [{"type": "point", "position": (0.0, 0.0, 3.0), "range": 4.0, "intensity": 6.0},
+                {"type": "point", "position": (0.0, 0.0, 0.0), "range": 3.5, "intensity": 20.0, "color": (0.4, 1.0, 0.6)},
+                {"type": "point", "position": TOUCH_RANGE_LIGHT[0], "range": TOUCH_RANGE_LIGHT[1], "intensity": 30.0,
+                 "color": (1.0, 0.5, 0.2)}]
+    raise KeyError(rig)
+
+
+def shading_sphere(rig, material, variant, w=320, h=240, rings=40, segments=60):
+    """The C2 sphere (radius 3 at the origin, camera at (0, 0, 9)) under one light rig, one of SWEEP_MATERIALS and one
+    instantiation of the fragment stage.
+
+    Rigs: eight = 8 point lights on a spiral around the view axis (ranges 0 and 1e-5, intensities 0 and 1e4, a black
+    one), three more behind them that the packer drops, no sun; eleven = the same UBO with light_counts[1] = 11 (the
+    shader clamps to 8); headon / back / touch: sweep_lights. Variants: one = a single draw over the default 1x1 slot;
+    one_vcol = with seeded vertex colours in [0, 1.5]; multi = the index range as two draws (a third and two thirds), the
+    second tinted and through a 3x5 texture; shadow = one_vcol under the pre-pass for the rig's sun. Every variant has
+    the same mesh table (mesh 0 the whole sphere, 1 and 2 its parts), so one context can move between them by its draw
+    list alone."""
+    s = scenes.scene_c2_sphere(w, h, rings, segments, skybox="solid")
+    s.skybox = None
+    cam = (0.0, 0.0, 9.0)
+    view, proj = scenes.editor_camera(cam, (0, 0, 0), 60.0, (w, h), 0.1, 1000.0)
+    s.ubo = scenes.pack_ubo(view, proj, cam, sweep_lights(rig), ambient=SWEEP_AMBIENT,
+                            ambient_intensity=SWEEP_AMBIENT_INTENSITY[material % 3])
+    if rig == "eleven":
+        s.ubo.light_counts[1] = 11
+    s.materials = [SWEEP_MATERIALS[material]]
+    cut = (s.indices.size // 9) * 3
+    s.meshes = np.array([(0, s.indices.size, 0, 0), (0, cut, 0, 0), (cut, s.indices.size - cut, 0, 0)],
+                        abi.MESH_RANGE_DTYPE)
+    if variant in ("one_vcol", "shadow"):
+        v = s.vertices.copy()
+        v["color"] = np.random.default_rng(17).uniform(0.0, 1.5, size=(v.shape[0], 3)).astype(F)
+        s.vertices = v
+    if variant == "multi":
+        s.textures = [(SWEEP_MULTI_SLOT, checker_texture(3, 5, 13))]
+        s.draws = [abi.make_draw(1, np.eye(4, dtype=F), material_index=0),
+                   abi.make_draw(2, np.eye(4, dtype=F), texture_slot=SWEEP_MULTI_SLOT, material_index=0,
+                                 tint=SWEEP_MULTI_TINT)]
+    elif variant not in ("one", "one_vcol", "shadow"):
+        raise KeyError(variant)
+    s.name = f"sweep_{rig}_m{material}_{variant}"
+    if variant == "shadow":
+        if rig not in SWEEP_SUN_RIGS:
+            raise ValueError(f"rig {rig} has no sun to cast a shadow")
+        scenes.with_shadow(s, 256)
+    return s
+
+
+# (texture w x h, scale, offset, tiling): non-power-of-two extents, w x 1 and 1 x h, width 2, negative scales and
+# offsets. MODERATE cases stay where float32 uv precision is below an LSB (compared with float64 too); LARGE ones carry
+# uvs in the thousands (|u w|, |v h| < 2^20), where only the oracle's float32 order is the reference.
+SAMPLER_MODERATE = {
+    "3x5": ((3, 5), (1.5, 0.75), (0.1, -0.2), 1.25),
+    "5x3_neg": ((5, 3), (-1.5, 0.75), (-3.3, 100.25), 7.0),
+    "1x7": ((1, 7), (1.0, 1.0), (0.0, 0.0), 1.0),
+    "7x1": ((7, 1), (2.0, -3.0), (0.5, 0.5), 1.0),
+    "2x2": ((2, 2), (1.0, 1.0), (-0.25, -0.25), 1.0),
+    "100x3": ((100, 3), (0.01, 1.0), (-0.005, 0.0), 1.0),
+    "3x5_identity": ((3, 5), (1.0, 1.0), (0.0, 0.0), 1.0),
+}
+SAMPLER_LARGE = {
+    "3x3_tiling1000": ((3, 3), (1.0, 1.0), (0.0, 0.0), 1000.0),
+    "6x10_offset4096": ((6, 10), (1.0, 1.0), (-4096.0, 4096.0), 1.0),
+}
+
+
+def sampler_grid(tex_wh, scale, offset, tiling, w=320, h=180, n=30, seed=7):
+    """textured_grid with a seeded tex_wh texture in slot 3 under the given uv transform (uv * scale * tiling + offset)."""
+    s = textured_grid(w, h, n)
+    s.skybox = None
+    s.textures = [(3, checker_texture(tex_wh[0], tex_wh[1], seed))]
+    s.draws = [abi.make_draw(0, np.eye(4, dtype=F), texture_slot=3, material_index=0, tint=(1.0, 0.9, 0.8, 0.75),
+                             texture_scale=scale, texture_offset=offset, tiling=tiling)]
+    s.name = f"sampler_{tex_wh[0]}x{tex_wh[1]}_s{scale[0]:g},{scale[1]:g}_o{offset[0]:g},{offset[1]:g}_t{tiling:g}"
+    return s
+
+
+def sampler_case(name, **kw):
+    return sampler_grid(*{**SAMPLER_MODERATE, **SAMPLER_LARGE}[name], **kw)
