@@ -201,13 +201,27 @@ __device__ __forceinline__ uint32_t obj_delta(const TriFrameParams& fp, uint32_t
     if (__ballot(d != d0) == 0ull) return fp.vdelta[d0];
     return fp.vdelta[d];
 }
-template <bool ONE = false>
+// Frame kinds (k_raster_kind, include/tri_raster.h TRI_KIND_*): the fast single-draw instantiation with the
+// frame-uniform switches its pixel loop would test as compile-time constants. KIND < 0 is the generic instantiation,
+// which reads them from the frame's arguments; a kind's frames always carry object-space varyings (vary_obj).
+constexpr int kKindGeneric = -1;
+template <int KIND>
+__device__ __forceinline__ bool kind_flag(uint32_t bit, bool runtime) {
+    if constexpr (KIND >= 0) return ((uint32_t)KIND & bit) != 0u;
+    else return runtime;
+}
+template <int KIND>
+__device__ __forceinline__ bool kind_obj(const TriFrameParams& fp) {
+    if constexpr (KIND >= 0) return true;
+    else return obj_mode(fp);
+}
+template <bool ONE = false, int KIND = kKindGeneric>
 __device__ __forceinline__ FetchBufs fetch_bufs(const TriFrameParams& fp, const TriDeviceBuffers& b) {
     FetchBufs f;
     f.snap = rec_buf(b.snap, 16u, fp.nslots);
     f.vary = rec_buf(b.vary, (ONE && TRI_VARY36) ? 36u : 48u, (uint64_t)fp.nslots + fp.ovf_vert_cap);
     f.src = f.vary;
-    if (ONE && obj_mode(fp)) f.src = rec_buf(b.vattr + 9u * fp.vin_base, 36u, fp.nslots);
+    if (ONE && kind_obj<KIND>(fp)) f.src = rec_buf(b.vattr + 9u * fp.vin_base, 36u, fp.nslots);
     // obj48: an unclipped primitive's vertices are its geometry's own 48-B input records (index slot + vdelta)
     if (!ONE && obj48_mode(fp)) f.src = rec_buf(b.vin, 48u, b.vertex_count);
     f.shade = rec_buf(b.draw_shade, (uint32_t)sizeof(TriDrawShade), fp.ndraws);
@@ -1903,8 +1917,8 @@ struct PbrPix {
 };
 
 // One light with unclamped N.L and L.V given (the caller forms them without normalising L first).
-__device__ __forceinline__ void eval_pbr_fast(const TriShadeConst& sc, const PbrPix& px, float NdotLr, float LdotV,
-                                              f3 rad, float scale, f3& c) {
+__device__ __forceinline__ void eval_pbr_fast(float a2m1, float kgo, const PbrPix& px, float NdotLr, float LdotV,
+                                              f3 rad, float scale, f3& c) {  // a2m1, kgo: TriShadeConst's
 #pragma clang fp contract(fast)  // fast build only: FMA contraction is inside the 1-LSB budget
     // N.L <= 0 makes the light's weight 0 and every term finite: c + X * 0 == c exactly, so a wave
     // whose lanes all face away skips the rest (Default.frag evaluates it to the same zero)
@@ -1912,10 +1926,10 @@ __device__ __forceinline__ void eval_pbr_fast(const TriShadeConst& sc, const Pbr
     const float ih = frsq(fmaxf(__builtin_fmaf(2.0f, LdotV, 2.0f), 1e-30f));
     const float NdotH = fmaxf((px.NdotVr + NdotLr) * ih, 0.0f);
     const float NdotL = NdotLr;  // > 0 here: max(N.L, 0) is the identity
-    const float dd = __builtin_fmaf(NdotH * NdotH, sc.a2m1, 1.0f);
+    const float dd = __builtin_fmaf(NdotH * NdotH, a2m1, 1.0f);
     // Default.frag's max(., 1e-4) on G_L's denominator is the identity here: N.L > 0 and k = (r + 1)^2 / 8
     // >= 0.136 for roughness >= 0.045, so N.L (1 - k) + k >= k
-    const float gden = NdotL + sc.kgo;  // G_L's denominator divided through by 1 - k (sc.a2pio carries 1 / (1 - k))
+    const float gden = NdotL + kgo;  // G_L's denominator divided through by 1 - k (sc.a2pio carries 1 / (1 - k))
     // NDF * G_L * G_V / den with NDF = a2 / (pi dd^2), G_L = NdotL / gden
     const float sp = spec_num(px.spA, px.spB, NdotL) * frcp((dd * dd) * gden);
     // 1 - max(H.V, 0), clamped to [0, 1]: one clamped subtract
@@ -1979,8 +1993,15 @@ __device__ __forceinline__ void eval_pbr_fast_p(const TriShadeConst& sc, const P
 #ifndef TRI_ONE_FOLD
 #define TRI_ONE_FOLD 1
 #endif
-template <bool ONE = false>
-__device__ __forceinline__ float4 fs_fast(const TriShadeConst& sc, const Frag& f) {
+// One point light's 32-B record as one scalar load
+typedef float f8v __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f8v ld_light(const TriShadeConst& sc, uint32_t i) {
+    return *reinterpret_cast<const f8v*>(sc.pl[i].pos);
+}
+// KIND (frame kinds): the sun and the point lights are compile-time on or off; each light's record is loaded while
+// the light before it is evaluated.
+template <bool ONE = false, int KIND = kKindGeneric>
+__device__ __forceinline__ float4 fs_fast(const TriShadeConst& sc, const Frag& f, uint32_t npt_k = 0u) {
 #pragma clang fp contract(fast)
 #if TRI_PK_SHADE
     PbrPixP px;
@@ -2059,15 +2080,35 @@ __device__ __forceinline__ float4 fs_fast(const TriShadeConst& sc, const Frag& f
     px.spA = sc.spAk * rgV;                   // 0.25 a2 / pi / (1 - k) / max(G_V's denominator, 1e-4)
     px.spB = sc.spBk * (NdotV * rgV);         // 1e4 a2 / pi * G_V / (1 - k)
     if (kAblate & 64) return make_float4(c.x, c.y, c.z, 1.0f);  // diagnostics: 64 = no lights
-    if (sc.has_sun && f.vis > 0.0f) {  // vis = 0 (fully shadowed): the sun adds exactly nothing
+    // A kind reads the lights' uniform terms where the fragment's other constants are read, ahead of the lanes' skip
+    // tests (behind a skip each would be a scalar load and a wait of its own): the empty asm pins them there.
+    float a2m1 = sc.a2m1, kgo = sc.kgo;
+    f3 srad = mk(sc.sun_rad[0], sc.sun_rad[1], sc.sun_rad[2]);
+    f8v nxt{};  // the next point light's record
+    if constexpr (KIND >= 0) {
+        asm volatile("" : "+s"(a2m1), "+s"(kgo));
+        if constexpr ((KIND & TRI_KIND_SUN) != 0) asm volatile("" : "+s"(srad.x), "+s"(srad.y), "+s"(srad.z));
+        // (the first light's record is not pinned there with them: its eight SGPRs across the sun's evaluation
+        // made the compiler read the other constants a few at a time, each behind a wait of its own)
+        if constexpr ((KIND & TRI_KIND_LIGHTS) != 0) nxt = ld_light(sc, 0);  // (at least one light)
+    }
+    if (kind_flag<KIND>(TRI_KIND_SUN, sc.has_sun) && f.vis > 0.0f) {  // vis = 0 (fully shadowed): the sun adds exactly nothing
         const f3 L = mk(sc.sun_l[0], sc.sun_l[1], sc.sun_l[2]);
-        eval_pbr_fast(sc, px, fdot(px.N, L), fdot(L, px.V), mk(sc.sun_rad[0], sc.sun_rad[1], sc.sun_rad[2]), f.vis, c);
+        eval_pbr_fast(a2m1, kgo, px, fdot(px.N, L), fdot(L, px.V), srad, f.vis, c);
     }
     const f3 wp = fworld(f);
-    for (uint32_t i = 0; i < sc.npt; ++i) {
+    // (a kind's light count is read once per workgroup, ahead of the pixel loop: npt_k)
+    const uint32_t npt = KIND >= 0 ? (kind_flag<KIND>(TRI_KIND_LIGHTS, false) ? npt_k : 0u) : sc.npt;
+    for (uint32_t i = 0; i < npt; ++i) {
         float lp[8];
+        if (KIND >= 0) {  // this light's record was loaded a light ahead; the last light loads itself again (no branch)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { lp[k] = sc.pl[i].pos[k]; lp[4 + k] = sc.pl[i].rad[k]; }
+            for (int k = 0; k < 8; ++k) lp[k] = nxt[k];
+            nxt = ld_light(sc, min(i + 1u, (uint32_t)TRI_MAX_POINT_LIGHTS - 1u));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { lp[k] = sc.pl[i].pos[k]; lp[4 + k] = sc.pl[i].rad[k]; }
+        }
         const f3 to = sub3(mk(lp[0], lp[1], lp[2]), wp);
         const float d2 = fdot(to, to);
         const float inv = frsq(d2);
@@ -2076,7 +2117,7 @@ __device__ __forceinline__ float4 fs_fast(const TriShadeConst& sc, const Frag& f
         // range: (1 - d/r)^2 = 0 adds exactly nothing. One exact skip instead of two.
         if (!(d2 > 1e-8f && att0 > 0.0f)) continue;
         // L = to / |to| is never formed: N.L and L.V are the dot products with `to`, scaled once
-        eval_pbr_fast(sc, px, fdot(px.N, to) * inv, fdot(to, px.V) * inv, mk(lp[4], lp[5], lp[6]), att0 * att0, c);
+        eval_pbr_fast(a2m1, kgo, px, fdot(px.N, to) * inv, fdot(to, px.V) * inv, mk(lp[4], lp[5], lp[6]), att0 * att0, c);
     }
     const f3 t = mk(c.x * frcp(c.x + 1.0f), c.y * frcp(c.y + 1.0f), c.z * frcp(c.z + 1.0f));
     return make_float4(tone_out(t.x), tone_out(t.y), tone_out(t.z), ONE ? sc.sbt[3] : (sc.base[3] * f.tw) * f.sw);
@@ -2275,7 +2316,7 @@ __device__ __forceinline__ ShadeRec load_shade(const FetchBufs& fb, uint32_t d) 
 // XF48: the instantiation may apply obj48's per-draw model and normal matrices (not the shadow instantiation: the
 // host keeps frames with the pre-pass and a non-identity obj48 draw on world-space varyings, so that kernel carries
 // none of this code's registers)
-template <bool EXACT, bool ONE, bool XF48, typename Put>
+template <bool EXACT, bool ONE, bool XF48, int KIND = kKindGeneric, typename Put>
 __device__ __forceinline__ void fetch_attrs(const TriFrameParams& fp, const TriDeviceBuffers& b, const FetchBufs& fb,
                                             const Taps& t, uint32_t d, float w0, float w1, float w2, const float* lut,
                                             Put&& put) {
@@ -2288,7 +2329,7 @@ __device__ __forceinline__ void fetch_attrs(const TriFrameParams& fp, const TriD
     auto row = [](float c0v, float c1v, float c2v, float x, float y, float z, float w) {
         return __builtin_fmaf(c0v, x, __builtin_fmaf(c1v, y, __builtin_fmaf(c2v, z, w)));
     };
-    if (ONE && obj_mode(fp) && fp.obj_xform) {  // object-space position and normal: the model / normal matrices
+    if (ONE && kind_flag<KIND>(TRI_KIND_XFORM, obj_mode(fp) && fp.obj_xform)) {  // object-space position and normal: the model / normal matrices
         const float px = ip(a0.x, b0.x, c0.x), py = ip(a0.y, b0.y, c0.y), pz = ip(a0.z, b0.z, c0.z);
         const float nx = ip(a1.x, b1.x, c1.x), ny = ip(a1.y, b1.y, c1.y), nz = ip(a1.z, b1.z, c1.z);
         const float* m = fp.draw0.model;  // column-major, affine (vary_obj)
@@ -2325,7 +2366,7 @@ __device__ __forceinline__ void fetch_attrs(const TriFrameParams& fp, const TriD
         put(0, ip(a0.x, b0.x, c0.x)); put(1, ip(a0.y, b0.y, c0.y)); put(2, ip(a0.z, b0.z, c0.z));
         put(3, ip(a1.x, b1.x, c1.x)); put(4, ip(a1.y, b1.y, c1.y)); put(5, ip(a1.z, b1.z, c1.z));
     }
-    if (ONE && obj_mode(fp) && fp.obj_ucol) {  // one colour for every vertex (its interpolation is the colour)
+    if (ONE && kind_flag<KIND>(TRI_KIND_UCOL, obj_mode(fp) && fp.obj_ucol)) {  // one colour for every vertex (its interpolation is the colour)
         put(6, fp.ucol[0]); put(7, fp.ucol[1]); put(8, fp.ucol[2]);
     } else {
         put(6, ip(a2.x, b2.x, c2.x)); put(7, ip(a2.y, b2.y, c2.y)); put(8, ip(a2.z, b2.z, c2.z));
@@ -2366,20 +2407,23 @@ __device__ __forceinline__ void fetch_attrs(const TriFrameParams& fp, const TriD
 
 // CLIPM: 0 = the key may name a clipped sub-triangle (tested per pixel), 1 = it never does (the shading loop
 // defers clipped pixels, TRI_CLIP_DEFER), 2 = it always does (the deferred pass).
-template <bool EXACT, bool SHADOW, bool ONE, int CLIPM = 0, typename Put>
+// KIND (frame kinds): `fbk` names the gather descriptors, built once per workgroup; a kind with one vertex colour
+// issues no colour gathers at all (the generic instantiation issues them and never waits for them).
+template <bool EXACT, bool SHADOW, bool ONE, int CLIPM = 0, int KIND = kKindGeneric, typename Put>
 __device__ __forceinline__ void fetch_fragment_to(const TriFrameParams& fp, const TriDeviceBuffers& b, uint64_t key,
                                                   int32_t px, int32_t py, const float* lut, Put&& put,
-                                                  const uint32_t* qtab = nullptr) {
+                                                  const uint32_t* qtab = nullptr, const FetchBufs* fbk = nullptr) {
     constexpr bool kInlineVis = SHADOW;
     const uint32_t low = (uint32_t)key;
     // qtab (TRI_QTAB bins, uniform): the key names the primitive above its queue position (qenc)
     const uint32_t prim = qtab ? kQPrimMax - (low >> 11) : TRI_PRIM_MAX - (low >> 3);
     const uint32_t sub = CLIPM == 1 ? 0u : (qtab ? (low >> 8) & 7u : low & 7u);  // >= 1: sub-triangle of a clipped primitive
-    const FetchBufs fb = fetch_bufs<ONE>(fp, b);
+    const FetchBufs fb = (KIND >= 0 && fbk) ? *fbk : fetch_bufs<ONE, KIND>(fp, b);
     constexpr bool kEarly = !TRI_COLOUR_LATE || (TRI_COLOUR_EARLY_ONE && ONE && !EXACT && !SHADOW);
+    const bool ucol = ONE && TRI_VARY_OBJ && kind_flag<KIND>(TRI_KIND_UCOL, obj_mode(fp) && fp.obj_ucol);
     // (issued early, the colour gathers are unconditional: on a frame with one vertex colour (obj_ucol) they read the
     // records' colours beside their positions, unused; a uniform branch around them cost the instantiation 4 spills)
-    const bool vcol = kEarly || !(ONE && TRI_VARY_OBJ && obj_mode(fp) && fp.obj_ucol);
+    const bool vcol = KIND >= 0 ? !ucol : (kEarly || !ucol);
     uint32_t sl[3] = {0, 0, 0}, d = 0;
     TriSnap a0{}, a1{}, a2{};
     uint32_t v0 = 0, v1 = 0, v2 = 0, dl = 0;
@@ -2436,7 +2480,7 @@ __device__ __forceinline__ void fetch_fragment_to(const TriFrameParams& fp, cons
     }
     if (kAblate & 1024) {  // diagnostics: 1024 = no colour gathers (3 of the fragment's 13 loads; same VALU)
         taps.a2 = V4{w0, w1, w2, 0.0f}; taps.b2 = taps.a2; taps.c2 = taps.a2;
-    } else if (ONE && TRI_VARY_OBJ && obj_mode(fp) && fp.obj_ucol) {
+    } else if (ucol) {
         // one colour for every vertex: fetch_attrs takes it from the frame arguments
     } else if (!kEarly) {
         if (!from_rec) {  // an unclipped primitive's vertices: fb.src (fb.vary unless ONE or obj48; with CLIPM 0 a
@@ -2460,14 +2504,15 @@ __device__ __forceinline__ void fetch_fragment_to(const TriFrameParams& fp, cons
         vis = shadow_vis(fp, b.shadow_map, ix(L0.x, L1.x, L2.x), ix(L0.y, L1.y, L2.y), ix(L0.z, L1.z, L2.z));
     }
     put(19, vis);
-    fetch_attrs<EXACT, ONE, !SHADOW>(fp, b, fb, taps, d, w0, w1, w2, lut, put);
+    fetch_attrs<EXACT, ONE, !SHADOW, KIND>(fp, b, fb, taps, d, w0, w1, w2, lut, put);
 }
 
-template <bool EXACT, bool SHADOW, bool ONE, int CLIPM = 0>
+template <bool EXACT, bool SHADOW, bool ONE, int CLIPM = 0, int KIND = kKindGeneric>
 __device__ __forceinline__ void fetch_fragment(const TriFrameParams& fp, const TriDeviceBuffers& b, uint64_t key,
                                                int32_t px, int32_t py, const float* lut, Frag& f,
-                                               const uint32_t* qtab = nullptr) {
-    fetch_fragment_to<EXACT, SHADOW, ONE, CLIPM>(fp, b, key, px, py, lut, [&](int i, float x) { (&f.wx)[i] = x; }, qtab);
+                                               const uint32_t* qtab = nullptr, const FetchBufs* fbk = nullptr) {
+    fetch_fragment_to<EXACT, SHADOW, ONE, CLIPM, KIND>(fp, b, key, px, py, lut, [&](int i, float x) { (&f.wx)[i] = x; },
+                                                       qtab, fbk);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2739,9 +2784,9 @@ __device__ __forceinline__ float mix_ai(float x, float y, float w) { return x * 
 
 // Default.frag for one fragment at pixel (px, py), stored as B8G8R8A8_UNORM. AI: the instantiation for frames with
 // the AI frame blend (k_raster_ai; the other kernels carry none of its registers)
-template <bool EXACT, bool ONE, bool AI>
+template <bool EXACT, bool ONE, bool AI, int KIND = kKindGeneric>
 __device__ __forceinline__ uint32_t shade_bgra(const TriFrameParams& fp, const TriDeviceBuffers& b, const Frag& f,
-                                               int32_t px, int32_t py) {
+                                               int32_t px, int32_t py, uint32_t npt_k = 0u) {
     if (EXACT) {
         float4 c = fs_exact(fp, f);
         if (AI && fp.ai_on) {  // (an AI frame-generation model is loaded) the blend with the AI frame's sample
@@ -2751,7 +2796,9 @@ __device__ __forceinline__ uint32_t shade_bgra(const TriFrameParams& fp, const T
         }
         return unorm8(c.z) | (unorm8(c.y) << 8) | (unorm8(c.x) << 16) | (unorm8(c.w) << 24);
     }
-    float4 c = fs_fast<ONE>(fp.sc, f);
+    uint32_t a8 = fp.sc.a8;
+    if constexpr (KIND >= 0) asm volatile("" : "+s"(a8));  // (a kind: read ahead of the shading, not in front of the store)
+    float4 c = fs_fast<ONE, KIND>(fp.sc, f, npt_k);
     if (AI && fp.ai_on) {  // the fast build's channels are already scaled by 255 (tone_out): mix there
         const float4 ai = sample_ai(fp, b, px, py);
         const float w = fp.ai_wgt;
@@ -2759,7 +2806,7 @@ __device__ __forceinline__ uint32_t shade_bgra(const TriFrameParams& fp, const T
         return fast_bgra(mix_ai(c.x, 255.0f * ai.x, w), mix_ai(c.y, 255.0f * ai.y, w), mix_ai(c.z, 255.0f * ai.z, w),
                          unorm8(mix_ai(alpha, ai.w, w)));
     }
-    return fast_bgra(c.x, c.y, c.z, ONE ? fp.sc.a8 : unorm8(c.w));  // ONE: the uniform alpha byte, host-folded
+    return fast_bgra(c.x, c.y, c.z, ONE ? a8 : unorm8(c.w));  // ONE: the uniform alpha byte, host-folded
 }
 
 #ifndef TRI_CLIP_DEFER
@@ -2767,7 +2814,9 @@ __device__ __forceinline__ uint32_t shade_bgra(const TriFrameParams& fp, const T
 #endif
 
 // One bin: coverage into the LDS key tile, then shading and stores. Reached by the whole workgroup.
-template <bool EXACT, int BL, bool SHADOW, bool ONE = false, bool AI = false>
+// KIND (frame kinds, k_raster_kind): the shading loops test no frame-uniform switch and read the gather
+// descriptors, the store bases and the light count from values formed once per workgroup.
+template <bool EXACT, int BL, bool SHADOW, bool ONE = false, bool AI = false, int KIND = kKindGeneric>
 __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDeviceBuffers& b, const int bin) {
     constexpr int BIN = 1 << BL;
     __shared__ uint64_t keys[BIN * BIN];
@@ -2982,7 +3031,33 @@ __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDe
     const int lx = tid & (BIN - 1);
     const bool sky_on = fp.sky_size != 0;
     const bool sky_const = sky_on && !EXACT && fp.sky_mode == TRI_SKY_UNIFORM;
-    const bool sky_queue = sky_on && !sky_const;
+    const bool sky_queue = kind_flag<KIND>(TRI_KIND_SKYQ, sky_on && !sky_const);
+    const bool write_depth = kind_flag<KIND>(TRI_KIND_DEPTH, fp.write_depth != 0u);
+    // A kind's per-workgroup values: the gather descriptors, the light count, and the stores' addressing: the colour
+    // and depth bases stay in SGPRs and each lane keeps a 32-bit byte offset that advances by a constant per
+    // iteration (the host gives a kind only frames whose targets stay below 4 GiB: tri_raster_kind).
+    FetchBufs fbk{};
+    uint32_t npt_k = 0u, so = 0u, so_step = 0u;
+    TRI_G char* cbase = nullptr;
+    TRI_G char* dbase = nullptr;
+    if constexpr (KIND >= 0) {
+        fbk = fetch_bufs<ONE, KIND>(fp, b);
+        npt_k = fp.sc.npt;
+        cbase = (TRI_G char*)b.color;
+        dbase = (TRI_G char*)b.depth;
+        so = (uint32_t)((oy - fp.y0 + (tid >> BL)) * fp.W + ox + lx) * 4u;
+        so_step = (uint32_t)((TRI_BLOCK / BIN) * fp.W) * 4u;
+    }
+    // the pixel at band offset `o` (a kind: at byte offset `o32` from the resident bases)
+    auto store_c = [&](size_t o, uint32_t o32, uint32_t colour) {
+        if constexpr (KIND >= 0) *(TRI_G uint32_t*)(cbase + o32) = colour;
+        else b.color[o] = colour;
+    };
+    auto store_z = [&](size_t o, uint32_t o32, float z) {
+        if (!write_depth) return;
+        if constexpr (KIND >= 0) *(TRI_G float*)(dbase + o32) = z;
+        else b.depth[o] = z;
+    };
     // the background colour stays a scalar to its store (its VGPR copy, hoisted out of the loop, was the shadow
     // instantiation's one spilled register)
     const uint32_t bg_sgpr = sky_const ? fp.sky_bgra : fp.clear_bgra;
@@ -3002,7 +3077,13 @@ __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDe
     // carries the other's registers)
     auto shade_loop = [&](auto QT) {
         constexpr bool kq = decltype(QT)::value;
+        // (a kind: the vector-memory counter drained once ahead of the loop (vmcnt(0), the other counters untouched), so
+        // that the loop's header inherits no pending load from the code before it and need not drain the previous
+        // iteration's stores)
+        if constexpr (KIND >= 0) __builtin_amdgcn_s_waitcnt(0x0F70);
+        uint32_t so_it = so - so_step;  // (a kind's store offset of this iteration's pixel)
         for (int ly = tid >> BL; ly < bh; ly += TRI_BLOCK / BIN) {
+            so_it += so_step;
             const bool in = lx < bw;
             const uint64_t key = in ? keys[(ly << BL) + lx] : 0ull;
             const bool bg = in && key == kBgKey;
@@ -3054,9 +3135,9 @@ __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDe
             uint32_t out;
             float z;
             if (bg) {
-                const size_t o = (size_t)(py - fp.y0) * fp.W + px;
-                if (!sky_queue) b.color[o] = bg_bgra();
-                if (fp.write_depth) b.depth[o] = 1.0f;
+                const size_t o = KIND >= 0 ? 0 : (size_t)(py - fp.y0) * fp.W + px;
+                if (!sky_queue) store_c(o, so_it, bg_bgra());
+                store_z(o, so_it, 1.0f);
                 continue;
             } else if (kAblate & 1) {  // diagnostics: coverage only
                 z = __uint_as_float((uint32_t)(key >> 32));
@@ -3068,13 +3149,13 @@ __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDe
                     const float k0 = __uint_as_float(((uint32_t)key & 0x7FFFFFu) | 0x3F000000u);
                     for (int q = 0; q < 20; ++q) (&f.wx)[q] = k0 + 0.01f * q;
                 } else {
-                    fetch_fragment<EXACT, SHADOW, ONE, kDefer ? 1 : 0>(fp, b, key, px, py, lut, f, kq ? qtab : nullptr);
+                    fetch_fragment<EXACT, SHADOW, ONE, kDefer ? 1 : 0, KIND>(fp, b, key, px, py, lut, f, kq ? qtab : nullptr, &fbk);
                 }
-                out = shade_bgra<EXACT, ONE, AI>(fp, b, f, px, py);
+                out = shade_bgra<EXACT, ONE, AI, KIND>(fp, b, f, px, py, npt_k);
             }
-            const size_t o = (size_t)(py - fp.y0) * fp.W + px;
-            b.color[o] = out;
-            if (fp.write_depth) b.depth[o] = z;
+            const size_t o = KIND >= 0 ? 0 : (size_t)(py - fp.y0) * fp.W + px;
+            store_c(o, so_it, out);
+            store_z(o, so_it, z);
         }
     };
     if (kQt && qmode) shade_loop(std::true_type{});
@@ -3087,10 +3168,11 @@ __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDe
             const uint64_t key = keys[li];
             const int32_t px = ox + qx, py = oy + qy;
             Frag f;
-            fetch_fragment<EXACT, SHADOW, ONE, 2>(fp, b, key, px, py, lut, f, (kQt && qmode) ? qtab : nullptr);
+            fetch_fragment<EXACT, SHADOW, ONE, 2, KIND>(fp, b, key, px, py, lut, f, (kQt && qmode) ? qtab : nullptr, &fbk);
             const size_t o = (size_t)(py - fp.y0) * fp.W + px;
-            b.color[o] = shade_bgra<EXACT, ONE, AI>(fp, b, f, px, py);
-            if (fp.write_depth) b.depth[o] = __uint_as_float((uint32_t)(key >> 32));
+            const uint32_t o32 = KIND >= 0 ? (uint32_t)((py - fp.y0) * fp.W + px) * 4u : 0u;
+            store_c(o, o32, shade_bgra<EXACT, ONE, AI, KIND>(fp, b, f, px, py, npt_k));
+            store_z(o, o32, __uint_as_float((uint32_t)(key >> 32)));
         }
     }
 #ifdef TRI_PHASE_TIMING
@@ -3160,6 +3242,46 @@ __global__ __launch_bounds__(TRI_BLOCK) __attribute__((amdgpu_waves_per_eu(8))) 
     TRI_BIND_ARGS;
     raster_bin<false, 5, false, true>(fp, b, xcd_bin(blockIdx.x, fp.nbins));
 }
+#endif
+// Frame kinds: the fast single-draw instantiation compiled once per combination of the frame-uniform switches its
+// pixel loop tests (TRI_KIND_*), for the combinations the benchmark's frames and the common scenes take; every other
+// frame keeps k_raster_plain<false, BL, true>. TRI_FRAME_KINDS = 0 builds none. Plain functions, not a template: the
+// register attributes take no template-dependent value.
+#ifndef TRI_FRAME_KINDS
+#define TRI_FRAME_KINDS 1
+#endif
+// occupancy and VGPR cap of the 32x32-bin kinds (as TRI_RASTER_WAVES_PLAIN_ONE / TRI_RASTER_ONE_VGPRS above: the
+// attribute's value is doubled on gfx950, 0 = no cap). Round 10, same box, two interleaved rounds: at the
+// generic instantiation's 56 VGPRs the values held across the loop cost spilled VGPRs (24 B of scratch, a reload per
+// pixel) and the constants are read a few at a time (C3 10.49k frames/s, below the parent's 10.85-10.97k); at 64 VGPRs (59 used, no
+// scratch) every constant is read in one batch behind the gathers (11.27-11.31k); 7 waves/SIMD with 96 SGPRs and no
+// cap 11.17-11.19k.
+#ifndef TRI_KIND_WAVES
+#define TRI_KIND_WAVES 8
+#endif
+#ifndef TRI_KIND_VGPRS
+#define TRI_KIND_VGPRS 32
+#endif
+#if TRI_KIND_VGPRS
+#define TRI_KIND_VGPR_ATTR __attribute__((amdgpu_num_vgpr(TRI_KIND_VGPRS)))
+#else
+#define TRI_KIND_VGPR_ATTR
+#endif
+#if TRI_FRAME_KINDS && defined(TRI_RASTER_PLAIN_TU)
+#define TRI_KIND_KERNEL(NAME, BL, ATTR, KIND)                                                                      \
+    __global__ __launch_bounds__(TRI_BLOCK) ATTR void NAME(TRI_KARGS) {                                            \
+        TRI_BIND_ARGS;                                                                                             \
+        raster_bin<false, BL, false, true, false, (int)(KIND)>(fp, b, xcd_bin(blockIdx.x, fp.nbins));              \
+    }
+#define TRI_KIND_ATTR5 __attribute__((amdgpu_waves_per_eu(TRI_KIND_WAVES))) TRI_KIND_VGPR_ATTR
+#define TRI_KIND_ATTR4 __attribute__((amdgpu_waves_per_eu(TRI_RASTER_WAVES_PLAIN_ONE)))
+constexpr uint32_t kKindLit = TRI_KIND_SUN | TRI_KIND_LIGHTS | TRI_KIND_DEPTH;  // a sun, point lights, a depth target
+// 32x32 bins: vertex colours under a sun and point lights, with a sampled or a uniform sky, plain or under a TRS draw
+TRI_KIND_KERNEL(k_raster_kind5_lit_sky, 5, TRI_KIND_ATTR5, kKindLit | TRI_KIND_SKYQ)
+TRI_KIND_KERNEL(k_raster_kind5_lit_sky_xf, 5, TRI_KIND_ATTR5, kKindLit | TRI_KIND_SKYQ | TRI_KIND_XFORM)
+TRI_KIND_KERNEL(k_raster_kind5_lit, 5, TRI_KIND_ATTR5, kKindLit)
+// 16x16 bins: one vertex colour under point lights alone, a sampled sky
+TRI_KIND_KERNEL(k_raster_kind4_ucol_pl_sky, 4, TRI_KIND_ATTR4, TRI_KIND_UCOL | TRI_KIND_LIGHTS | TRI_KIND_DEPTH | TRI_KIND_SKYQ)
 #endif
 // Frames with Default.frag's AI frame blend (AiBlendConfig.w > 0, an uploaded AI frame; never with the shadow
 // pre-pass, which the reference does not have): the general instantiation plus the blend
@@ -3440,12 +3562,39 @@ const void* tri_vertex_stage_kernel(TriFrontKernel k) {
 #endif
 
 #ifdef TRI_RASTER_PLAIN_TU
+// The frame-kind kernel for the frame's switches at its bin size, or null (no such kind is built)
+static const void* kind_kernel(int bl, uint32_t kind) {
+#if TRI_FRAME_KINDS
+    auto f = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
+    if (bl == 5) {
+        if (kind == (kKindLit | TRI_KIND_SKYQ)) return f(k_raster_kind5_lit_sky);
+        if (kind == (kKindLit | TRI_KIND_SKYQ | TRI_KIND_XFORM)) return f(k_raster_kind5_lit_sky_xf);
+        if (kind == kKindLit) return f(k_raster_kind5_lit);
+    }
+    if (bl == 4 && kind == (TRI_KIND_UCOL | TRI_KIND_LIGHTS | TRI_KIND_DEPTH | TRI_KIND_SKYQ)) return f(k_raster_kind4_ucol_pl_sky);
+#endif
+    return nullptr;
+}
+int tri_raster_kind(const TriFrameParams& fp) {
+    // the fast single-draw solid instantiation's frames with object-space varyings, outside the shadow pre-pass and
+    // the AI blend, whose colour and depth targets a 32-bit byte offset spans
+    if (!(fp.one_draw && fp.shade_solid && fp.vary_obj) || fp.exact_shading || fp.ai_on || fp.shadow_on) return -1;
+    if ((uint64_t)fp.W * (uint64_t)(fp.y1 - fp.y0) * 4ull >= (1ull << 32)) return -1;
+    const bool sky_on = fp.sky_size != 0;
+    const uint32_t kind = (fp.obj_xform ? TRI_KIND_XFORM : 0u) | (fp.obj_ucol ? TRI_KIND_UCOL : 0u) |
+                          (fp.sc.has_sun ? TRI_KIND_SUN : 0u) | (fp.write_depth ? TRI_KIND_DEPTH : 0u) |
+                          (sky_on && fp.sky_mode != TRI_SKY_UNIFORM ? TRI_KIND_SKYQ : 0u) |
+                          (fp.sc.npt ? TRI_KIND_LIGHTS : 0u);
+    return kind_kernel(fp.bin_log2, kind) ? (int)kind : -1;
+}
 const void* tri_raster_plain_kernel(const TriFrameParams& fp) {
     // ONE: a single draw over a 1x1 texture slot (the common untextured mesh), the specialised instantiation
     const bool one = fp.one_draw && fp.shade_solid;
     const int bl = fp.bin_log2 == 5 ? 5 : fp.bin_log2 == 4 ? 4 : 6;
     const int sel = (fp.exact_shading ? 1 : 0) | (one ? 2 : 0);
     auto f = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
+    const int kind = tri_raster_kind(fp);
+    if (kind >= 0) return kind_kernel(bl, (uint32_t)kind);
     if (fp.ai_on) {  // (the host keeps such frames off the ONE instantiation's 36-B varyings)
         if (bl == 5) return fp.exact_shading ? f(k_raster_ai<true, 5>) : f(k_raster_ai<false, 5>);
         if (bl == 4) return fp.exact_shading ? f(k_raster_ai<true, 4>) : f(k_raster_ai<false, 4>);

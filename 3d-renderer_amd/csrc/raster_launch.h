@@ -132,6 +132,9 @@ void tri_diag_front_plan(TriFramePlan& plan);  // diagnostics build only (raster
 #endif
 // k_raster_plain's instantiation for a frame without the shadow pre-pass (raster_plain.hip)
 const void* tri_raster_plain_kernel(const TriFrameParams& fp);
+// The frame kind that instantiation takes: the frame's TRI_KIND_* switches (include/tri_raster.h) when a kernel with
+// them as compile-time constants is built for its bin size, -1 for the generic instantiation (raster_plain.hip)
+int tri_raster_kind(const TriFrameParams& fp);
 // The frame's first kernel (vertex_stage.hip): k_vertex, k_vertex_band (row bands with cluster culling) or k_reset
 // (a frame without vertex work)
 enum TriFrontKernel { kFrontVertex = 0, kFrontBand, kFrontReset };

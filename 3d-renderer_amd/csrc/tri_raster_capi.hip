@@ -1588,6 +1588,8 @@ int tri_render(tri_ctx* c) {
     ts.shadow = fp.shadow_on != 0;
     TriFramePlan plan;
     tri_plan_frame(fp, plan);
+    if (const int kind = tri_raster_kind(fp); kind >= 0)  // the frame-kind kernel the plan took
+        c->last_path |= TRI_PATH_KIND | ((uint32_t)kind << TRI_PATH_KIND_SHIFT);
 #ifdef TRI_DIAG_FRONT
     if (c->diag_frames++ > 0) tri_diag_front_plan(plan);
 #endif

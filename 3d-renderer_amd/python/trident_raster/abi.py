@@ -152,6 +152,10 @@ TRI_PATH_ONE_DRAW, TRI_PATH_VARY_OBJ, TRI_PATH_OBJ_XFORM, TRI_PATH_OBJ_UCOL, TRI
 TRI_PATH_OBJ48 = 0x20
 TRI_PATH_IDX_ROUTE = 0x40
 TRI_PATH_EXACT = 0x80
+# a frame-kind instantiation shaded the frame; its TRI_KIND_* switches at (path >> TRI_PATH_KIND_SHIFT) & TRI_KIND_MASK
+TRI_PATH_KIND, TRI_PATH_KIND_SHIFT = 0x100, 16
+TRI_KIND_XFORM, TRI_KIND_UCOL, TRI_KIND_SUN, TRI_KIND_DEPTH, TRI_KIND_SKYQ, TRI_KIND_LIGHTS = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+TRI_KIND_MASK = 0x3F
 
 # the delta bit-plane band format (include/tri_raster.h)
 TRI_DBP_SLOT_PIXELS, TRI_DBP_MIN_SLOT, TRI_DBP_MAX_SLOT, TRI_DBP_MAX_BANDS = 4096, 176, 12448, 16

@@ -170,6 +170,18 @@ typedef struct tri_frame_stats {
 #define TRI_PATH_OBJ48     0x20u  /* object-space varyings outside the single-draw solid instantiation      */
 #define TRI_PATH_IDX_ROUTE 0x40u  /* several draws: vertex slots from the index buffer, no per-primitive record */
 #define TRI_PATH_EXACT     0x80u  /* the exact instantiation shaded it: TRI_FLAG_EXACT_SHADING, or uvs beyond 8192 texels */
+#define TRI_PATH_KIND     0x100u  /* a frame-kind instantiation shaded it: the frame-uniform switches below are      *
+                                   * compile-time constants of its kernel, which is named by                         *
+                                   * (path >> TRI_PATH_KIND_SHIFT) & TRI_KIND_MASK; clear: the generic instantiation */
+#define TRI_PATH_KIND_SHIFT 16
+/* the switches of a frame kind (single-draw solid frames with object-space varyings only) */
+#define TRI_KIND_XFORM   0x1u  /* TRI_PATH_OBJ_XFORM                                              */
+#define TRI_KIND_UCOL    0x2u  /* TRI_PATH_OBJ_UCOL: no colour gathers                            */
+#define TRI_KIND_SUN     0x4u  /* a directional light                                             */
+#define TRI_KIND_DEPTH   0x8u  /* the frame has a depth target (no TRI_FLAG_NO_DEPTH_OUTPUT)      */
+#define TRI_KIND_SKYQ   0x10u  /* background pixels queue for the skybox pass (a non-uniform sky) */
+#define TRI_KIND_LIGHTS 0x20u  /* at least one point light                                        */
+#define TRI_KIND_MASK   0x3Fu
 
 /* Shadow-map pre-pass (BASELINE.json config 5). The reference reserves the switch
  * (LightComponent::m_ShadowCaster, Trident/src/ECS/Components/LightComponent.h:33) but renders no shadow
