@@ -49,10 +49,6 @@ static_assert(TRI_MAX_CLIP_POLY <= TRI_MAX_CLIP_VERTS, "clip polygon buffers");
 #endif
 #define TRI_OBJ48_DRAWS 16  // draws a frame may hold for object-space varyings outside the ONE instantiation
 
-#ifndef TRI_SNAP_F
-#define TRI_SNAP_F 1
-#endif
-
 #define TRI_SKY_RAY 0u
 #define TRI_SKY_PERSP 1u
 #define TRI_SKY_UNIFORM 2u
@@ -75,8 +71,8 @@ struct __attribute__((aligned(16))) TriVsSkin {
 };
 
 // Per-vertex window-space record written by k_vertex (the perspective divide + viewport transform
-// + 8-bit snap are done once per vertex): X (signed 24 bits) | outcode << 24, Y, 1/w, z_ndc. With TRI_SNAP_F
-// (the main pass; the shadow map's lsnap keeps the packed form) X and Y are stored as floats — they are
+// + 8-bit snap are done once per vertex): X (signed 24 bits) | outcode << 24, Y, 1/w, z_ndc. In the main pass
+// (the shadow map's lsnap keeps the packed form) X and Y are stored as floats — they are
 // integers below 2^22 in magnitude, so exactly — and the outcode goes to its own byte per slot: the fragment
 // stage's weights then start from float differences (no per-pixel sign extension and conversions).
 struct __attribute__((aligned(16))) TriSnap {

@@ -1,21 +1,12 @@
-// raster_launch.h — host-side launchers for the gfx950 kernels (implemented in raster_kernels.hip).
+// raster_launch.h — host-side launchers for the gfx950 kernels (the frame plan: raster_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "raster_common.h"
 
+// Tunables (numeric; -D overrides them for A/B builds), read by the kernels and by the host's launch geometry.
 // k_setup occupancy target (waves per SIMD); with 4 waves per workgroup, also its workgroups per CU
-// TRI_IDX_ROUTE: frames of a few draws over concatenated meshes reach a primitive's vertex slots through the index
-// buffer (TriFrameParams::idx_route) instead of a per-primitive prim_vs record; 0 keeps the records
-#ifndef TRI_IDX_ROUTE
-#define TRI_IDX_ROUTE 1
-#endif
-// TRI_IDX_ROUTE_SHADOW: the route on frames with the shadow pre-pass too (its fragments read their slots and draw from
-// the queue-position table, so only the coverage pass, the map raster and the table's fallback search the draws)
-#ifndef TRI_IDX_ROUTE_SHADOW
-#define TRI_IDX_ROUTE_SHADOW 0
-#endif
 #ifndef TRI_SETUP_WAVES
 #define TRI_SETUP_WAVES 6
 #endif
@@ -29,13 +20,13 @@
 // C3 under a TRS draw +1 %, C2 unchanged: its set-up is one primitive per lane either way). The shadow set-up bins
 // every primitive twice and keeps the resident round (C5 4.90k -> 4.75k with 2). Round 6: with the single-draw set-up
 // within 64 VGPRs and the raster's C3 instantiation within 56 (raster_kernels.hip: TRI_SETUP_WAVES_ONE,
-// TRI_RASTER_ONE_VGPRS) a set-up wave displaces at most one raster wave, and 3 per CU beat 2 (same-box A/B).
+// raster_plain.hip: TRI_RASTER_ONE_VGPRS) a set-up wave displaces at most one raster wave, and 3 per CU beat 2 (same-box A/B).
+#ifndef TRI_SETUP_WGS_PER_CU_OVERLAP
+#define TRI_SETUP_WGS_PER_CU_OVERLAP 3
+#endif
 // k_setup's chunk target for bands (cluster culling): most chunks are culled and exit at once
 #ifndef TRI_SETUP_BAND_CHUNKS
 #define TRI_SETUP_BAND_CHUNKS 4096
-#endif
-#ifndef TRI_SETUP_WGS_PER_CU_OVERLAP
-#define TRI_SETUP_WGS_PER_CU_OVERLAP 3
 #endif
 
 // Device pointers in the global address space (device compilation only; the host sees plain pointers of the same
@@ -49,16 +40,6 @@
 #define TRI_G __attribute__((address_space(1)))
 #else
 #define TRI_G
-#endif
-
-// TRI_UCOL: vary_obj frames over a geometry whose vertices share one colour take it from the frame arguments
-// (TriFrameParams::obj_ucol)
-#ifndef TRI_UCOL
-#define TRI_UCOL 1
-#endif
-// TRI_OBJ48: object-space varyings outside the ONE instantiation (TriFrameParams::obj48); 0 keeps world-space varyings
-#ifndef TRI_OBJ48
-#define TRI_OBJ48 1
 #endif
 
 struct TriDeviceBuffers {
@@ -76,8 +57,8 @@ struct TriDeviceBuffers {
     TRI_G const uint32_t* sky;         // 6 * sky_size^2 RGBA8 sRGB texels (+X,-X,+Y,-Y,+Z,-Z)
     TRI_G const float* srgb_lut;       // 256 sRGB -> linear (host, double) + 256 alpha b/255
     TRI_G float4* clip;                // nslots (read only when a primitive is clipped)
-    TRI_G TriSnap* snap;               // nslots (TRI_SNAP_F: {X, Y as exact floats, 1/w, z})
-    TRI_G uint8_t* oc;                 // nslots outcodes (TRI_SNAP_F; otherwise they ride in snap's X word)
+    TRI_G TriSnap* snap;               // nslots: {X, Y as exact floats, 1/w, z}
+    TRI_G uint8_t* oc;                 // nslots outcodes
     TRI_G float4* vary;                // 3 * (nslots + ovf_vert_cap)
     TRI_G TriRec* recs;                // ovf_rec_cap clipped sub-triangles
     TRI_G uint32_t* clip_slot;         // nprims: first sub-triangle record of a clipped primitive
@@ -143,8 +124,6 @@ const void* tri_vertex_stage_kernel(TriFrontKernel k);
 // Event stamps of one frame, in launch order: vertex, setup (+ clip, + the shadow map binning), shadow-map
 // raster (only with the pre-pass), raster, end.
 enum TriStage { kStageVertex = 0, kStageShadow, kStageSetup, kStageRaster, kStageCount };
-
-hipError_t tri_kernels_init();
 
 // One frame = 3 dependent launches on `stream` (k_vertex, k_setup with in-wave clipping, k_raster), 4 with the
 // shadow pre-pass (k_shadow_raster after k_setup<shadow>); `events` (may be null) gets kStageCount + 1 stamps

@@ -55,13 +55,13 @@ struct TextArgs {
     int32_t aw, ah;     // atlas extent
 };
 
-__device__ __forceinline__ uint32_t unorm8(float c) {  // as raster_kernels.hip's
+__device__ __forceinline__ uint32_t unorm8(float c) {  // as raster_device.h's
     const float cc = fminf(fmaxf(c, 0.0f), 1.0f);
     return (uint32_t)(int)(cc * 255.0f + 0.5f);
 }
 
 // The atlas at (u, v): A8 UNORM (byte / 255), LINEAR, CLAMP_TO_EDGE, level 0 — sample_ai's arithmetic
-// (raster_kernels.hip) on one channel.
+// (raster_bin.h) on one channel.
 __device__ __forceinline__ float sample_atlas(const TextArgs& a, const float* unorm, float u, float v) {
     const float x = u * (float)a.aw - 0.5f, y = v * (float)a.ah - 0.5f;
     const float fx = floorf(x), fy = floorf(y);

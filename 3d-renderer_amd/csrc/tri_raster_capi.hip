@@ -959,7 +959,6 @@ int tri_create(const tri_config* cfg, tri_ctx** out) {
     auto bail = [&](int rc) { tri_destroy(c); return rc; };
     int rc = make_current(c);
     if (rc) return bail(rc);
-    if (tri_kernels_init() != hipSuccess) return bail(fail(TRI_E_HIP, "tri_create: kernel attribute setup failed"));
     if (hipDeviceGetAttribute(&c->cu_count, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess ||
         c->cu_count <= 0)
         c->cu_count = 256;
@@ -1457,14 +1456,14 @@ int tri_render(tri_ctx* c) {
     fp.vary_obj = fp.vary36 && c->draw0_obj ? 1u : 0u;
     fp.obj_xform = fp.vary_obj && c->draw0_xform ? 1u : 0u;
     fp.vin_base = fp.vary_obj ? (uint32_t)((int64_t)c->draw0.base_vertex + (int64_t)c->draw0.min_index) : 0u;
-    fp.obj_ucol = TRI_UCOL && fp.vary_obj && c->draw0_ucol ? 1u : 0u;
+    fp.obj_ucol = fp.vary_obj && c->draw0_ucol ? 1u : 0u;
     if (fp.obj_ucol) std::memcpy(fp.ucol, c->geom->ucol, sizeof fp.ucol);
     // object-space varyings for the other instantiations (the ONE frames keep vary_obj's 36-B records)
     // (not with the pre-pass over a transformed draw: the shadow instantiation carries no per-draw transform)
-    fp.obj48 = (TRI_OBJ48 && !fp.vary36 && c->obj48 && !(c->shadow.size && c->obj48_xform)) ? 1u : 0u;
+    fp.obj48 = (!fp.vary36 && c->obj48 && !(c->shadow.size && c->obj48_xform)) ? 1u : 0u;
     fp.obj48_xform = fp.obj48 && c->obj48_xform ? 1u : 0u;
-    // (with the pre-pass only under TRI_IDX_ROUTE_SHADOW: the shadow kernels carry the draw search only then)
-    fp.idx_route = (TRI_IDX_ROUTE && c->idx_route && (!c->shadow.size || TRI_IDX_ROUTE_SHADOW)) ? 1u : 0u;
+    // (not with the pre-pass: the shadow kernels carry no draw search)
+    fp.idx_route = (c->idx_route && !c->shadow.size) ? 1u : 0u;
     if (fp.idx_route) {
         fp.idx_k = c->idx_k;
         std::memcpy(fp.pbase, c->pbase, sizeof fp.pbase);

@@ -1,5 +1,5 @@
 """The fragment stage on the device over its parameter space: every algebraic form of Default.frag in
-raster_kernels.hip (fs_exact; fs_fast scalar, packed-pair and host-folded ONE) under the materials, light rigs and
+raster_bin.h (fs_exact; fs_fast scalar, packed-pair and host-folded ONE) under the materials, light rigs and
 texture addressing of scene_cases.shading_sphere / sampler_grid, against the oracle (depth bit-exact, colour within
 COLOR_TOL) and against the float64 frames of tests/test_fragment_sweep.py (2 LSB, as
 test_parity_gpu.test_gpu_against_float64_pipeline states and justifies). Each test asserts the instantiation that shaded

@@ -24,7 +24,7 @@ CLUSTER_PRIMS = 512  # raster_common.h TRI_CLUSTER_PRIMS
 
 
 def cluster_visible(scene, draw, lo, hi, y0, y1):
-    """Restatement of k_vertex's cluster_visible (raster_kernels.hip): the object-space box through
+    """Restatement of k_vertex's cluster_visible (vertex_stage.hip): the object-space box through
     (P V) M; a box wholly in front of the eye whose image misses rows [y0, y1) or the frame's columns (2 px
     margin), or lies before z = 0 or beyond z = w, has no fragment in the band."""
     if (lo > hi).any():

@@ -283,7 +283,7 @@ def test_cluster_cull_is_exact(oracle, case):
     """TRI_FLAG_CLUSTER_CULL on a whole frame (row bands always cull): frames bit-identical to the
     unculled path and to the oracle, with geometry partly off screen, several draws, invalid vertices,
     skinned draws (never culled), clipped primitives, and clusters cut by both the near and the far plane
-    (the cull's depth margin, raster_kernels.hip cluster_visible)."""
+    (the cull's depth margin, vertex_stage.hip cluster_visible)."""
     from trident_raster import abi, scenes
 
     if case == "near_far_planes":  # the displaced grid spans z in [-5.9, -4.1]: both planes cut its clusters

@@ -13,7 +13,7 @@
 //   k_cal_dense16 / k_cal_dense12    packed 16-B / 12-B records, each read once in scrambled order (the
 //                                    snap / varying gathers of k_raster over random triangle order):
 //                                    footprint is the lower bound; the excess is re-fetch after eviction.
-// Loads are raw buffer loads exactly as k_raster issues them (raster_kernels.hip ld128 / b96 snap reads).
+// Loads are raw buffer loads exactly as k_raster issues them (raster_device.h ld128 / b96 snap reads).
 // The kernels only read; one store happens only for an impossible checksum, so writes are ~0.
 #include <hip/hip_runtime.h>
 
