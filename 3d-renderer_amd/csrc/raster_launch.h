@@ -192,6 +192,25 @@ void tri_text_build(const tri_text_quad* quads, uint32_t count, int32_t W, int32
 hipError_t tri_launch_text(uint32_t* color, int32_t W, int32_t y0, int32_t y1, const TriTextPlan& plan,
                            const uint8_t* d_blob, const uint8_t* atlas, uint32_t aw, uint32_t ah, hipStream_t stream);
 
+// Device pose evaluation (pose_eval.hip; include/tri_raster.h "skeletal poses evaluated on the device").
+int tri_internal_animset_device(const tri_animset* set);
+// The host-side check of a tri_pose_palette call against a palette whose uploaded prefix holds `prefix` matrices:
+// TRI_OK with the end of the posed suffix (*extent, in matrices; `prefix` for no instances), or TRI_E_INVALID with the
+// message recorded. scratch is the caller's to keep between calls (no allocation per frame once it has grown); on
+// success scratch.bones[i] is instance i's bone count.
+struct TriPoseScratch {
+    std::vector<std::pair<uint32_t, uint32_t>> spans;  // {first matrix, matrices}, sorted for the overlap test
+    std::vector<uint32_t> bones;
+};
+int tri_pose_check(const tri_animset* set, const tri_pose_instance* instances, uint32_t count, uint32_t prefix,
+                   uint32_t* extent, TriPoseScratch& scratch);
+// d_instances: checked records on the set's device, none of a skeleton with more than lds_bones bones (the workgroups'
+// LDS is sized by it); palette: at least *extent matrices.
+hipError_t tri_launch_pose(const tri_animset* set, const tri_pose_instance* d_instances, uint32_t count,
+                           uint32_t lds_bones, float* palette, hipStream_t stream);
+// The matrices of a context's uploaded palette prefix.
+uint32_t tri_internal_pose_prefix(tri_ctx* ctx);
+
 // Internal accessors for the group layer (tri_group.hip): a context's stream and device.
 hipStream_t tri_internal_stream(tri_ctx* ctx);
 int tri_internal_device(tri_ctx* ctx);

@@ -346,6 +346,31 @@ int tri_group_set_text(tri_group* g, tri_font* const* fonts, const tri_text_quad
     return TRI_OK;
 }
 
+int tri_group_pose_palette(tri_group* g, tri_animset* const* sets, const tri_pose_instance* inst, uint32_t n) {
+    if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_pose_palette: null group");
+    if (!n) return each(g, [&](tri_ctx* c) { return tri_pose_palette(c, nullptr, nullptr, 0); });
+    if (!sets || !inst) return tri_internal_fail(TRI_E_INVALID, "tri_group_pose_palette: null argument");
+    // sets: one per distinct device, in any order; every band's set is resolved and its instances checked against its
+    // own palette before the first band enqueues anything, so a refusal enqueues nothing
+    std::vector<tri_animset*> use(g->n, nullptr);
+    for (uint32_t r = 0; r < g->n; ++r) {
+        for (size_t i = 0; i < g->udev.size() && !use[r]; ++i)
+            if (sets[i] && tri_internal_animset_device(sets[i]) == g->dev[r]) use[r] = sets[i];
+        if (!use[r]) return tri_internal_fail(TRI_E_INVALID, "tri_group_pose_palette: no set on a band's device");
+    }
+    TriPoseScratch scratch;
+    for (uint32_t r = 0; r < g->n; ++r) {
+        uint32_t extent = 0;
+        const int rc = tri_pose_check(use[r], inst, n, tri_internal_pose_prefix(g->ctx[r]), &extent, scratch);
+        if (rc) return rc;
+    }
+    for (uint32_t r = 0; r < g->n; ++r) {
+        const int rc = tri_pose_palette(g->ctx[r], use[r], inst, n);
+        if (rc) return rc;
+    }
+    return TRI_OK;
+}
+
 int tri_group_render(tri_group* g) {
     if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_render: null group");
     const int32_t ddev = g->dev[g->display];

@@ -135,7 +135,20 @@ struct tri_ctx {
     uint32_t sky_size = 0;
     bool sky_uniform = false;  // every texel of the cubemap equal (e.g. the solid fallback)
     uint32_t sky_uniform_bgra = 0;
-    uint32_t nbones = 0;
+    uint32_t nbones = 0;         // the palette's extent: the uploaded prefix and the posed suffix behind it
+    uint32_t nbones_prefix = 0;  // what tri_upload_bone_palette put there
+    // tri_pose_palette's instance records: a ring of pinned buffers with their device copies, each fenced by an event
+    // recorded behind the k_pose that read it
+    struct PoseStage {
+        tri_pose_instance* h = nullptr;
+        tri_pose_instance* d = nullptr;
+        size_t cap = 0;
+        hipEvent_t done = nullptr;
+        bool busy = false;
+    };
+    PoseStage pose_stage[4];
+    uint32_t pose_next = 0;
+    TriPoseScratch pose_scratch;  // tri_pose_check's, kept between calls
 
     // per frame
     tri_global_ubo ubo{};
@@ -924,6 +937,7 @@ bool tri_internal_whole_frame(tri_ctx* c) { return c->y0 == 0 && c->y1 == c->H; 
 int tri_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
 int tri_internal_geometry_device(const tri_geometry* g) { return g->device; }
 int tri_internal_font_device(const tri_font* f) { return f->device; }
+uint32_t tri_internal_pose_prefix(tri_ctx* c) { return c->nbones_prefix; }
 const float* tri_internal_unorm_lut(tri_ctx* c) { return c->d_lut + 256; }
 
 extern "C" {
@@ -1009,6 +1023,11 @@ int tri_destroy(tri_ctx* c) {
     f(c->d_color_own); f(c->d_depth_own); f(c->d_present);
     f(c->d_lpos); f(c->d_lsnap); f(c->d_sbin_count); f(c->d_sbin_list); f(c->d_shadow);
     f(c->d_text);
+    for (auto& ps : c->pose_stage) {
+        f(ps.d);
+        if (ps.h) (void)hipHostFree(ps.h);
+        if (ps.done) (void)hipEventDestroy(ps.done);
+    }
     if (c->h_text) (void)hipHostFree(c->h_text);
     if (c->text_free) (void)hipEventDestroy(c->text_free);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -1141,6 +1160,84 @@ int tri_upload_bone_palette(tri_ctx* c, const float* m, uint32_t n) {
     if (n) HIP_TRY(hipMemcpy(c->d_bones, m, 64ull * n, hipMemcpyHostToDevice));
     HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->nbones = n;
+    c->nbones_prefix = n;  // the posed suffix, if any, is dropped
+    return TRI_OK;
+}
+
+int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst, uint32_t n) {
+    if (!c) return fail(TRI_E_INVALID, "tri_pose_palette: null context");
+    if (!n) {
+        c->nbones = c->nbones_prefix;
+        return TRI_OK;
+    }
+    if (!set || !inst) return fail(TRI_E_INVALID, "tri_pose_palette: null argument");
+    if (tri_internal_animset_device(set) != c->device) return fail(TRI_E_INVALID, "tri_pose_palette: the set is on another device");
+    uint32_t extent = 0;
+    int rc = tri_pose_check(set, inst, n, c->nbones_prefix, &extent, c->pose_scratch);
+    if (rc) return rc;
+    if ((rc = make_current(c))) return rc;
+    if (16ull * extent > c->cap_bones || !c->d_bones) {
+        // grow, keeping the prefix: frames in flight read the old palette
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        float* grown = nullptr;
+        const size_t cap = std::max<size_t>(16ull * extent, 2 * c->cap_bones);
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(float)));
+        hipError_t e = hipMemset(grown, 0, cap * sizeof(float));
+        if (e == hipSuccess && c->nbones_prefix)
+            e = hipMemcpy(grown, c->d_bones, 64ull * c->nbones_prefix, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess) e = hipDeviceSynchronize();  // null-stream work: complete before the context's stream reads it
+        if (e != hipSuccess) {
+            (void)hipFree(grown);
+            return fail(TRI_E_HIP, "tri_pose_palette: growing the palette: %s", hipGetErrorString(e));
+        }
+        if (c->d_bones) HIP_TRY(hipFree(c->d_bones));
+        c->d_bones = grown;
+        c->cap_bones = cap;
+    }
+    tri_ctx::PoseStage& ps = c->pose_stage[c->pose_next];
+    if (ps.busy) HIP_TRY(hipEventSynchronize(ps.done));  // four calls back: long complete unless the device is that far behind
+    ps.busy = false;
+    if (n > ps.cap) {
+        if (ps.h) HIP_TRY(hipHostFree(ps.h));
+        ps.h = nullptr;
+        if (ps.d) HIP_TRY(hipFree(ps.d));
+        ps.d = nullptr;
+        ps.cap = 0;
+        const size_t cap = std::max<size_t>(n, 256);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ps.h), cap * sizeof(tri_pose_instance), hipHostMallocDefault));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ps.d), cap * sizeof(tri_pose_instance)));
+        ps.cap = cap;
+    }
+    if (!ps.done) HIP_TRY(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
+    // the records grouped by skeleton size, one launch per group: a workgroup's LDS is sized by its launch's largest
+    // skeleton, and a 256-bone instance should not make every 20-bone one reserve 40 KiB
+    static const uint32_t kBucket[3] = {32, 128, TRI_POSE_MAX_BONES};
+    const std::vector<uint32_t>& bones = c->pose_scratch.bones;
+    uint32_t first[4] = {0, 0, 0, 0};
+    for (uint32_t i = 0; i < n; ++i) ++first[(bones[i] <= kBucket[0] ? 0 : bones[i] <= kBucket[1] ? 1 : 2) + 1];
+    first[2] += first[1];
+    first[3] += first[2];
+    uint32_t at[3] = {0, first[1], first[2]};
+    for (uint32_t i = 0; i < n; ++i) ps.h[at[bones[i] <= kBucket[0] ? 0 : bones[i] <= kBucket[1] ? 1 : 2]++] = inst[i];
+    HIP_TRY(hipMemcpyAsync(ps.d, ps.h, (size_t)n * sizeof(tri_pose_instance), hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < 3; ++b)
+        HIP_TRY(tri_launch_pose(set, ps.d + first[b], first[b + 1] - first[b], kBucket[b], c->d_bones, c->stream));
+    HIP_TRY(hipEventRecord(ps.done, c->stream));
+    ps.busy = true;
+    c->pose_next = (c->pose_next + 1) % 4;
+    c->nbones = extent;
+    return TRI_OK;
+}
+
+int tri_read_bone_palette(tri_ctx* c, float* out, uint32_t n) {
+    if (!c) return fail(TRI_E_INVALID, "tri_read_bone_palette: null context");
+    if (n > c->nbones) return fail(TRI_E_INVALID, "tri_read_bone_palette: %u matrices of a palette of %u", n, c->nbones);
+    if (!n) return TRI_OK;
+    if (!out) return fail(TRI_E_INVALID, "tri_read_bone_palette: null destination");
+    int rc = make_current(c);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(out, c->d_bones, 64ull * n, hipMemcpyDeviceToHost));
     return TRI_OK;
 }
 

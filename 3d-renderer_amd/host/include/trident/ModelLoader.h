@@ -11,9 +11,28 @@
 //     them, Default.frag:126-130), missing vertex colours = white (ModelLoader.cpp:436-443);
 //   - material mapping: base colour (glTF baseColorFactor, MTL Kd + d), metallic / roughness (glTF
 //     factors, MTL Pm / Pr; defaults 1 / 1 as ModelLoader.cpp:375-378), base-colour texture path;
-//   - glTF node hierarchy baked into MeshInstance matrices (ModelLoader.cpp:505-540).
+//   - glTF node hierarchy baked into MeshInstance matrices (ModelLoader.cpp:505-540);
+//   - glTF skins and animations -> ModelData::m_Skeleton / m_AnimationClips and the vertices' bone influences, by the
+//     reference loader's rules (ModelLoader.cpp:87-183, :263-302, :545-628) applied to glTF's own structures:
+//       bones: the first skin's joints in order, then the unseen joints of further skins, then animated nodes that
+//         are no joint (identity inverse bind); m_SourceName = the node's name ("Node<i>" without one), m_Name =
+//         trimmed with a leading "mixamorig:" removed; m_LocalBindTransform = the node's local matrix;
+//         m_InverseBindMatrix from the first skin that lists the joint (identity without an accessor);
+//       hierarchy: the parent is the nearest ancestor node that is a bone (transforms of nodes in between are
+//         dropped, as in the reference); the root is the first parentless bone, bone 0 when there is none;
+//       influences: JOINTS_0 (u8 / u16) / WEIGHTS_0 (float, or u8 / u16 taken as normalised) through the skin of
+//         the node that instantiates the mesh, assigned as AssignBoneWeight does (free slot, else replace the
+//         smallest when larger) and normalised as NormaliseBoneWeights does; a joint index beyond the skin refuses
+//         the file;
+//       clips: one per animation ("Clip<i>" without a name), key times in seconds, duration = the largest input
+//         time, m_TicksPerSecond = 1000; one TransformChannel per target node with its T / R / S keys (a path the
+//         node's channel already has keys for starts another channel for that node); LINEAR and STEP keys as they
+//         are, CUBICSPLINE keys by their value element, all played linearly (one log line per file that loses
+//         information this way); morph-target "weights" channels are skipped; an output accessor whose count
+//         disagrees with its input refuses the file.
+//     OBJ carries neither.
 // Not restated: aiProcess_ImproveCacheLocality / OptimizeMeshes (they only reorder triangles or merge
-// meshes; the rendered image differs at most at exact depth ties), skeletons and animation clips.
+// meshes; the rendered image differs at most at exact depth ties).
 // Images: PNG (ImageDecoder.h: stb_image's PNG semantics on zlib) and binary PPM (P6) / PAM (P7, RGB /
 // RGBA) decode to forced RGBA8 with stb's vertical flip for 2D textures (stbi_set_flip_vertically_on_load,
 // TextureLoader.cpp:290-304) and without it for cube faces (:773); JPEG / TGA / BMP / HDR need stb and
@@ -25,6 +44,7 @@
 #include <string>
 #include <vector>
 
+#include "Animation.h"
 #include "Scene.h"
 
 namespace Trident {
@@ -41,6 +61,8 @@ struct ModelData {
     std::vector<Geometry::Material> m_Materials;
     std::vector<std::string> m_Textures;  // normalised paths referenced by materials
     std::vector<MeshInstance> m_MeshInstances;
+    Animation::Skeleton m_Skeleton;
+    std::vector<Animation::AnimationClip> m_AnimationClips;
 };
 
 class ModelLoader {

@@ -72,6 +72,9 @@ public:
     static bool SubmitAiOutput(const float* data, size_t count, const int64_t* shape, size_t rank) {
         return GetRenderer().SubmitAiOutput(data, count, shape, rank);
     }
+    // Poses evaluated on the device (opt-in; Renderer::SetDevicePoseEnabled)
+    static void SetDevicePoseEnabled(bool enabled) { GetRenderer().SetDevicePoseEnabled(enabled); }
+    static bool IsDevicePoseEnabled() { return GetRenderer().IsDevicePoseEnabled(); }
     static size_t GetOrCreatePrimitiveMeshIndex(MeshComponent::PrimitiveType primitiveType) {
         return GetRenderer().GetOrCreatePrimitiveMeshIndex(primitiveType);
     }

@@ -230,6 +230,18 @@ public:
     // false (and changes nothing) for an invalid device list.
     bool SetDeviceCount(uint32_t count, const std::vector<int32_t>& devices = {});
     uint32_t GetDeviceCount() const { return (uint32_t)std::max<size_t>(m_Devices.size(), 1); }
+    // Device poses (default off): the one switch. When on, a draw whose AnimationComponent has a valid skeleton handle,
+    // and whose asset the device path takes (Animation::DevicePoseCompatible), is posed by tri_pose_palette at the
+    // component's clip and time (no valid clip: the bind pose) behind the uploaded palette; its m_BoneMatrices are not
+    // read, and an ECS::AnimationSystem made with this renderer only advances its time. Every other animated draw goes
+    // through the uploaded prefix as before. Assets reach a device once, at their first use there; after any
+    // registration with the asset service (AnimationAssetService::GetGeneration) they are looked at and sent again.
+    void SetDevicePoseEnabled(bool enabled) { m_DevicePose = enabled; }
+    // Whether this renderer poses the component's draw on the device (false while device poses are off).
+    bool PosesOnDevice(const AnimationComponent& component) const;
+    bool IsDevicePoseEnabled() const { return m_DevicePose; }
+    // Host uploads of a bone palette (tri_upload_bone_palette calls) since Init.
+    uint64_t GetBonePaletteUploadCount() const { return m_BonePaletteUploads; }
     bool IsShutdown() const { return m_Shutdown; }
     // The concatenated buffers UploadMeshFromCache builds (the device copy of these is what
     // tri_upload_geometry receives).
@@ -267,6 +279,7 @@ private:
         uint64_t m_GeometryGeneration = 0, m_TextureGeneration = 0, m_MaterialGeneration = 0, m_SkyboxGeneration = 0;
         uint64_t m_AiGeneration = 0;
         std::vector<float> m_BonePalette;  // the palette last uploaded to this viewport's context
+        bool m_HasPosedSuffix = false;     // the last tri_pose_palette on this context had instances
         tri_shadow_config m_Shadow{};      // the pre-pass configuration last set on this context
         tri_image m_Image{};               // GetViewportTexture's handle (after the first frame)
         bool m_HasImage = false;
@@ -307,6 +320,31 @@ private:
     MeshDrawInfo m_SpriteDrawInfo{};
     static constexpr uint32_t s_MaxBonesPerSkeleton = 128;  // Renderer.h:291
     std::vector<float> m_BonePalette;  // PrepareBonePaletteBuffer's scratch: per-draw palettes, back to back
+    // device poses: this frame's posed draws (PrepareBonePaletteBuffer), and per device the set with what it holds
+    struct PoseDraw {
+        size_t m_Skeleton, m_Animation, m_Clip;  // asset handles and the clip index
+        float m_Time;
+        uint32_t m_Offset;
+    };
+    struct PoseAssetOnDevice {
+        uint32_t m_Skeleton = 0;
+        std::vector<uint32_t> m_Clips;
+    };
+    struct PoseDeviceSet {
+        tri_animset* m_Set = nullptr;
+        std::map<std::pair<size_t, size_t>, PoseAssetOnDevice> m_Assets;  // by (skeleton handle, animation handle)
+    };
+    bool m_DevicePose = false;
+    uint64_t m_BonePaletteUploads = 0;
+    std::vector<PoseDraw> m_PoseDraws;
+    mutable std::map<std::pair<size_t, size_t>, bool> m_PoseCompatible;  // DevicePoseCompatible per (skeleton, animation)
+    mutable uint64_t m_PoseCompatibleGeneration = 0;  // the asset service's generation the cache was filled under
+    uint64_t m_PoseSetsGeneration = 0;                // ... and the one the devices' sets were filled under
+    std::map<int32_t, PoseDeviceSet> m_PoseSets;
+    std::vector<tri_pose_instance> m_PoseInstances;
+    bool SubmitPoses(ViewportContext& context);
+    const PoseAssetOnDevice* PoseAssetOn(int32_t device, size_t skeleton, size_t animation);
+    void DropPoseSets();
     size_t m_PrimitiveMeshIndices[3] = {SIZE_MAX, SIZE_MAX, SIZE_MAX};
     bool m_IsUploadingMeshes = false;
     tri_geometry* m_SharedGeometry = nullptr;  // the device copy every viewport context binds

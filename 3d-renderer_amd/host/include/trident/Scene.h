@@ -133,11 +133,31 @@ struct SpriteComponent {
     float m_SortOffset{0.0f};
 };
 
-// AnimationComponent (ECS/Components/AnimationComponent.h:29-73), the part the renderer reads: the
-// skinning palette the CPU animation system writes each frame (m_BoneMatrices, column-major mat4s).
-// Clip/skeleton bookkeeping stays with the animation system, which is outside the hot path.
+// AnimationComponent (ECS/Components/AnimationComponent.h:29-73): the playback state ECS::AnimationSystem advances
+// (AnimationSystem.h), the cached asset handles, and the skinning palette the renderer reads (m_BoneMatrices,
+// column-major mat4s: written by the CPU animation system each frame, or by any other code). The reference's
+// m_StateMachine does not exist here (the state machine and blend tree are not restated).
 struct AnimationComponent {
+    std::string m_SkeletonAssetId{};
+    std::string m_AnimationAssetId{};
+    std::string m_CurrentClip{};
+    float m_CurrentTime{0.0f};
+    float m_PlaybackSpeed{1.0f};
+    bool m_IsLooping{true};
+    bool m_IsPlaying{true};
     std::vector<glm::mat4> m_BoneMatrices{};
+
+    size_t m_SkeletonAssetHandle{std::numeric_limits<size_t>::max()};
+    size_t m_AnimationAssetHandle{std::numeric_limits<size_t>::max()};
+    size_t m_CurrentClipIndex{std::numeric_limits<size_t>::max()};
+    size_t m_SkeletonAssetHash{0};
+    size_t m_AnimationAssetHash{0};
+    size_t m_CurrentClipHash{0};
+
+    void InvalidateCachedAssets() {
+        m_SkeletonAssetHandle = m_AnimationAssetHandle = m_CurrentClipIndex = std::numeric_limits<size_t>::max();
+        m_SkeletonAssetHash = m_AnimationAssetHash = m_CurrentClipHash = 0;
+    }
 };
 
 struct TagComponent {

@@ -52,6 +52,9 @@ int trident_app_set_entity_visible(trident_app* app, uint32_t entity, int visibl
 /* AnimationComponent::m_BoneMatrices of an entity (count column-major mat4s; 0 clears the palette):
  * the draw skins with them (PrepareBonePaletteBuffer, Renderer.cpp:3168-3245). */
 int trident_app_set_entity_bones(trident_app* app, uint32_t entity, const float* matrices, uint32_t count);
+/* The same for entity_count entities in one call: entity i takes matrices[i * matrices_per_entity ...]. */
+int trident_app_set_entities_bones(trident_app* app, const uint32_t* entities, uint32_t entity_count,
+                                   const float* matrices, uint32_t matrices_per_entity);
 int trident_app_add_light(trident_app* app, int type, const float position[3], const float direction[3],
                           const float color[3], float intensity, float range, int enabled, uint32_t* entity);
 
@@ -210,6 +213,66 @@ int trident_font_glyph(trident_font* font, uint32_t codepoint, float out[9]);
 int trident_font_metrics(trident_font* font, float out[3]);
 int trident_font_layout(trident_font* font, const float position[2], const float color[4], const char* text,
                         uint32_t bytes, tri_text_quad* out, uint32_t capacity, uint32_t* count);
+
+/* ---- skeletal animation on the CPU (host/include/trident/Animation.h): no app, no GPU ----------------------
+ * The asset service (Animation::AnimationAssetService::Get()) and the float32 player, over flat arrays. Matrices are
+ * column-major, quaternions w, x, y, z. */
+/* Animation::DecomposeBindTransform: out = translation[3], rotation[4], scale[3] — the defaults a tri_pose_bone takes. */
+int trident_anim_decompose(const float local_bind[16], float out[10]);
+/* RegisterRuntimeAsset with a skeleton and no clips (an id registered before keeps its handle and is replaced).
+ * parents: negative = none; source_names: nullable, and a NULL entry names bone i "Bone<i>"; root_index is
+ * m_RootBoneIndex as given (negative: unset). bone_count 0 registers an empty skeleton. */
+int trident_anim_register(const char* asset_id, uint32_t bone_count, const int32_t* parents, const float* local_binds,
+                          const float* inverse_binds, const char* const* source_names, int32_t root_index,
+                          uint64_t* handle);
+/* Append a clip to the asset. channels[i].bone and the key ranges are tri_pose_channel's; stored_bones (nullable)
+ * overrides the stored index per channel (it may be stale or negative); source_names (nullable, entries nullable) are
+ * the channels' m_SourceBoneName. *clip_index receives the clip's index. */
+int trident_anim_add_clip(uint64_t handle, const char* name, float duration, const tri_pose_channel* channels,
+                          const int32_t* stored_bones, const char* const* source_names, uint32_t channel_count,
+                          const float* vec_times, const float* vec_values, uint32_t vec_count, const float* quat_times,
+                          const float* quat_values, uint32_t quat_count, uint32_t* clip_index);
+/* AnimationAssetService::AcquireSkeleton(path): the asset of a model file (.gltf / .glb), loaded once per path;
+ * TRI_E_INVALID when the file yields neither bones nor clips. */
+int trident_anim_load(const char* path, uint64_t* handle);
+/* The asset as JSON text, for tests: {"root", "bones": [{"name", "source", "parent", "children", "local", "inverse"}],
+ * "clips": [{"name", "duration", "ticks", "channels": [{"bone", "source", "t", "r", "s"}]}]} with keys as
+ * [time, x, y, z] / [time, w, x, y, z] and floats printed with 9 significant digits. *needed gets the byte count
+ * (with the terminator); out is written when capacity allows. */
+int trident_anim_describe(uint64_t handle, char* out, uint64_t capacity, uint64_t* needed);
+/* ResolveClipIndex: TRI_E_INVALID when the asset has no clip of that name. */
+int trident_anim_clip_index(uint64_t handle, const char* name, uint32_t* clip_index);
+/* ResolveChannelBoneIndex of every channel of a clip (-1: skipped), as the player applies them. */
+int trident_anim_resolve_channels(uint64_t handle, uint32_t clip_index, int32_t* bones, uint32_t capacity,
+                                  uint32_t* count);
+/* A fresh AnimationPlayer on (handle, handle, clip_index) evaluated at `time` (EvaluateAt + CopyPoseTo): *count
+ * matrices, written to out when capacity allows. clip_index UINT32_MAX = no clip (the bind pose); an unknown handle
+ * gives the fallback pose, one identity. */
+int trident_anim_evaluate(uint64_t handle, uint32_t clip_index, float time, float* out, uint32_t capacity,
+                          uint32_t* count);
+/* AnimationPlayer::Update on a player set to (time, speed, looping, playing): the time and play state after dt. */
+int trident_anim_advance(uint64_t handle, uint32_t clip_index, float time, float speed, int looping, int playing,
+                         float dt, float* out_time, int* out_playing);
+
+/* ---- animated entities (ECS::AnimationSystem, host/include/trident/AnimationSystem.h) ---- */
+/* The playback fields of an entity's AnimationComponent (added when absent): asset ids as registered with
+ * trident_anim_register (NULL = empty), the clip name, time, speed, looping, playing. */
+int trident_app_set_entity_animation(trident_app* app, uint32_t entity, const char* skeleton_asset_id,
+                                     const char* animation_asset_id, const char* clip, float time, float speed,
+                                     int looping, int playing);
+/* AnimationSystem::Update(registry, dt): poses into m_BoneMatrices, or time only in device mode. */
+int trident_app_update_animation(trident_app* app, float dt);
+/* AnimationSystem::InitialisePose of the entity's component. */
+int trident_app_initialise_pose(trident_app* app, uint32_t entity);
+/* The entity's pose: its m_BoneMatrices; for a component the device poses, evaluated on the CPU at its current time on demand.
+ * *count matrices, written to out when capacity allows. */
+int trident_app_entity_pose(trident_app* app, uint32_t entity, float* out, uint32_t capacity, uint32_t* count);
+/* m_CurrentTime, m_IsPlaying and the cached {skeleton handle, animation handle, clip index} (UINT64_MAX: invalid). */
+int trident_app_entity_animation_state(trident_app* app, uint32_t entity, float* time, int* playing, uint64_t handles[3]);
+/* Renderer::SetDevicePoseEnabled (the app's animation system follows its renderer). */
+int trident_app_set_device_pose(trident_app* app, int enabled);
+/* Renderer::GetBonePaletteUploadCount. */
+int trident_app_bone_palette_uploads(trident_app* app, uint64_t* count);
 
 /* Renderer::GetViewportTexture: copies the viewport's image handle (TRI_E_STATE before its first frame). */
 int trident_app_viewport_texture(trident_app* app, uint32_t viewport_id, tri_image* out);

@@ -69,6 +69,9 @@ struct Corner {  // one triangle corner before aiProcess_JoinIdenticalVertices
     glm::vec3 p, n, c;
     glm::vec2 uv;
     bool hasNormal;
+    bool skinned;  // bi / bw are the vertex's bone influences
+    glm::ivec4 bi;
+    glm::vec4 bw;
 };
 
 // aiProcess_GenSmoothNormals (only when the mesh has no normals): each face's normalised normal is
@@ -118,6 +121,11 @@ Geometry::Mesh BuildMesh(std::vector<Corner>& corners, bool hasNormals, int mate
         v.TexCoord = c.uv;
         std::string key(reinterpret_cast<const char*>(&v), offsetof(Vertex, Tangent));
         key.append(reinterpret_cast<const char*>(&v.Color), sizeof(glm::vec3) + sizeof(glm::vec2));
+        if (c.skinned) {  // (skinless meshes weld exactly as before)
+            v.m_BoneIndices = c.bi;
+            v.m_BoneWeights = c.bw;
+            key.append(reinterpret_cast<const char*>(&v.m_BoneIndices), sizeof(glm::ivec4) + sizeof(glm::vec4));
+        }
         auto it = weld.find(key);
         if (it != weld.end()) {
             mesh.Indices.push_back(it->second);
@@ -436,12 +444,13 @@ bool Base64Decode(const std::string& in, std::string& out) {
         return -1;
     };
     out.clear();
-    int buf = 0, bits = 0;
+    uint32_t buf = 0;  // (only its low bits are ever read: unsigned, so the shifted-out ones just go)
+    int bits = 0;
     for (char c : in) {
         if (c == '=') break;
         const int v = val(c);
         if (v < 0) continue;
-        buf = (buf << 6) | v;
+        buf = (buf << 6) | (uint32_t)v;
         bits += 6;
         if (bits >= 8) {
             bits -= 8;
@@ -521,12 +530,14 @@ ModelData LoadGltf(const fs::path& path) {
     const std::vector<Json>& views = arrOf("bufferViews");
     const std::vector<Json>& accessors = arrOf("accessors");
     // accessor -> float components (normalised integer formats are converted) or indices
-    auto readAccessor = [&](int index, int comps, std::vector<float>& out) -> bool {
+    auto readAccessor = [&](int index, int comps, std::vector<float>& out, bool forceNorm = false) -> bool {
         if (index < 0 || (size_t)index >= accessors.size()) return false;
         const Json& a = accessors[index];
-        const size_t count = (size_t)a.numOr("count", 0);
+        const double countD = a.numOr("count", 0);
+        if (!(countD >= 0.0) || countD > 1.0e8) return false;
+        const size_t count = (size_t)countD;
         const int ctype = (int)a.numOr("componentType", 5126);
-        const bool norm = a.get("normalized") && a.get("normalized")->b;
+        const bool norm = forceNorm || (a.get("normalized") && a.get("normalized")->b);
         out.assign(count * comps, 0.0f);
         const Json* bvj = a.get("bufferView");
         if (!bvj) return true;  // all zeros (sparse accessors are not supported)
@@ -538,7 +549,9 @@ ModelData LoadGltf(const fs::path& path) {
         const std::string& buf = buffers[bi];
         const size_t csize = ctype == 5126 || ctype == 5125 ? 4 : (ctype == 5123 || ctype == 5122 ? 2 : 1);
         const size_t stride = bv.get("byteStride") ? (size_t)bv.numOr("byteStride", 0) : csize * comps;
-        const size_t base = (size_t)bv.numOr("byteOffset", 0) + (size_t)a.numOr("byteOffset", 0);
+        const double baseD = bv.numOr("byteOffset", 0) + a.numOr("byteOffset", 0);
+        if (!(baseD >= 0.0) || baseD > 1.0e12 || stride == 0 || stride > (1u << 20)) return false;
+        const size_t base = (size_t)baseD;
         for (size_t i = 0; i < count; ++i)
             for (int c = 0; c < comps; ++c) {
                 const size_t o = base + i * stride + c * csize;
@@ -586,6 +599,131 @@ ModelData LoadGltf(const fs::path& path) {
         }
         data.m_Materials.push_back(out);
     }
+    // skins and animations -> the skeleton (rules: ModelLoader.h)
+    const std::vector<Json>& gnodes = arrOf("nodes");
+    const std::vector<Json>& skins = arrOf("skins");
+    const std::vector<Json>& animations = arrOf("animations");
+    std::vector<int> nodeParent(gnodes.size(), -1), nodeBone(gnodes.size(), -1);
+    for (size_t n = 0; n < gnodes.size(); ++n)
+        if (const Json* ch = gnodes[n].get("children"))
+            for (const Json& c : ch->arr)
+                if (c.type == Json::Number && c.num >= 0 && c.num < (double)gnodes.size() && nodeParent[(size_t)c.num] < 0)
+                    nodeParent[(size_t)c.num] = (int)n;
+    auto nodeIndex = [&](const Json* j) -> int {
+        return j && j->type == Json::Number && j->num >= 0 && j->num < (double)gnodes.size() ? (int)j->num : -1;
+    };
+    Animation::Skeleton& skeleton = data.m_Skeleton;
+    auto ensureBone = [&](int node) -> int {
+        if (nodeBone[(size_t)node] >= 0) return nodeBone[(size_t)node];
+        Animation::Bone bone;
+        const Json* name = gnodes[(size_t)node].get("name");
+        bone.m_SourceName = name && name->type == Json::String && !name->str.empty() ? name->str : "Node" + std::to_string(node);
+        bone.m_Name = Animation::NormaliseBoneName(bone.m_SourceName);
+        bone.m_LocalBindTransform = NodeMatrix(gnodes[(size_t)node]);
+        const int index = (int)skeleton.m_Bones.size();
+        skeleton.m_NameToIndex.emplace(bone.m_Name, index);  // (the first bone of a name keeps it)
+        skeleton.m_SourceNameToIndex.emplace(bone.m_SourceName, index);
+        skeleton.m_Bones.push_back(std::move(bone));
+        return nodeBone[(size_t)node] = index;
+    };
+    std::vector<std::vector<int>> skinJoints(skins.size());  // per skin: joint slot -> bone
+    for (size_t si = 0; si < skins.size(); ++si) {
+        const Json* joints = skins[si].get("joints");
+        std::vector<float> ibm;
+        const bool hasIbm = skins[si].get("inverseBindMatrices") != nullptr;
+        if (hasIbm && (!readAccessor((int)skins[si].numOr("inverseBindMatrices", -1), 16, ibm) ||
+                       ibm.size() < 16 * (joints ? joints->arr.size() : 0))) {
+            LogError("glTF skin: the inverse bind accessor is unreadable or shorter than the joints", path.string());
+            return ModelData{};
+        }
+        for (size_t j = 0; joints && j < joints->arr.size(); ++j) {
+            const int node = nodeIndex(&joints->arr[j]);
+            if (node < 0) {
+                LogError("glTF skin: a joint is no node", path.string());
+                return ModelData{};
+            }
+            const bool fresh = nodeBone[(size_t)node] < 0;
+            const int bone = ensureBone(node);
+            if (fresh && hasIbm)
+                for (int k = 0; k < 16; ++k) skeleton.m_Bones[(size_t)bone].m_InverseBindMatrix[k / 4][k % 4] = ibm[16 * j + k];
+            skinJoints[si].push_back(bone);
+        }
+    }
+    bool lossy = false;
+    for (size_t ai = 0; ai < animations.size(); ++ai) {
+        Animation::AnimationClip clip;
+        const Json* name = animations[ai].get("name");
+        clip.m_Name = name && name->type == Json::String && !name->str.empty() ? name->str : "Clip" + std::to_string(ai);
+        clip.m_TicksPerSecond = 1000.0f;
+        const Json* samplers = animations[ai].get("samplers");
+        const Json* channels = animations[ai].get("channels");
+        std::unordered_map<int, size_t> current;  // node -> its open TransformChannel in clip.m_Channels
+        for (const Json& ch : channels ? channels->arr : kEmpty.arr) {
+            const Json* target = ch.get("target");
+            const Json* pathJ = target ? target->get("path") : nullptr;
+            const int node = target ? nodeIndex(target->get("node")) : -1;
+            if (!pathJ || node < 0 || pathJ->str == "weights") continue;
+            const int track = pathJ->str == "translation" ? 0 : pathJ->str == "rotation" ? 1 : pathJ->str == "scale" ? 2 : -1;
+            const double sd = ch.numOr("sampler", -1);
+            if (track < 0 || !samplers || !(sd >= 0) || sd >= (double)samplers->arr.size()) continue;
+            const Json& sampler = samplers->arr[(size_t)sd];
+            const Json* interp = sampler.get("interpolation");
+            const bool cubic = interp && interp->str == "CUBICSPLINE";
+            lossy = lossy || cubic || (interp && interp->str == "STEP");
+            const int comps = track == 1 ? 4 : 3;
+            std::vector<float> times, values;
+            if (!readAccessor((int)sampler.numOr("input", -1), 1, times) || !readAccessor((int)sampler.numOr("output", -1), comps, values) ||
+                values.size() != times.size() * comps * (cubic ? 3 : 1)) {
+                LogError("glTF animation: a sampler's accessors are unreadable or their counts disagree", path.string());
+                return ModelData{};
+            }
+            const int bone = ensureBone(node);
+            auto open = current.find(node);
+            auto hasKeys = [&](const Animation::TransformChannel& c) {
+                return track == 0 ? !c.m_TranslationKeys.empty() : track == 1 ? !c.m_RotationKeys.empty() : !c.m_ScaleKeys.empty();
+            };
+            if (open == current.end() || hasKeys(clip.m_Channels[open->second])) {
+                Animation::TransformChannel fresh;
+                fresh.m_BoneIndex = bone;
+                fresh.m_SourceBoneName = skeleton.m_Bones[(size_t)bone].m_SourceName;
+                clip.m_Channels.push_back(std::move(fresh));
+                current[node] = clip.m_Channels.size() - 1;
+                open = current.find(node);
+            }
+            Animation::TransformChannel& out = clip.m_Channels[open->second];
+            for (size_t k = 0; k < times.size(); ++k) {
+                const float* v = values.data() + (cubic ? 3 * k + 1 : k) * comps;
+                if (track == 1) out.m_RotationKeys.push_back({times[k], glm::quat(v[3], v[0], v[1], v[2])});
+                else (track == 0 ? out.m_TranslationKeys : out.m_ScaleKeys).push_back({times[k], glm::vec3(v[0], v[1], v[2])});
+                if (times[k] > clip.m_DurationSeconds) clip.m_DurationSeconds = times[k];
+            }
+        }
+        data.m_AnimationClips.push_back(std::move(clip));
+    }
+    if (lossy) LogError("glTF animation: STEP / CUBICSPLINE samplers are played linearly", path.string());
+    {  // parents: the nearest ancestor node that is a bone; the root: the first bone without one
+        std::vector<int> boneNode(skeleton.m_Bones.size(), -1);
+        for (size_t n = 0; n < gnodes.size(); ++n)
+            if (nodeBone[n] >= 0) boneNode[(size_t)nodeBone[n]] = (int)n;
+        for (size_t b = 0; b < skeleton.m_Bones.size(); ++b) {
+            int up = nodeParent[(size_t)boneNode[b]], parent = -1;
+            for (size_t steps = 0; up >= 0 && steps < gnodes.size(); ++steps, up = nodeParent[(size_t)up])
+                if (nodeBone[(size_t)up] >= 0 && nodeBone[(size_t)up] != (int)b) {
+                    parent = nodeBone[(size_t)up];
+                    break;
+                }
+            skeleton.m_Bones[b].m_ParentIndex = parent;
+            if (parent >= 0) skeleton.m_Bones[(size_t)parent].m_Children.push_back((int)b);
+            else if (skeleton.m_RootBoneIndex < 0) skeleton.m_RootBoneIndex = (int)b;
+        }
+        if (skeleton.m_RootBoneIndex < 0 && !skeleton.m_Bones.empty()) skeleton.m_RootBoneIndex = 0;
+    }
+    std::vector<int> meshSkin(arrOf("meshes").size(), -1);  // the skin of the first node that instantiates the mesh with one
+    for (const Json& node : gnodes) {
+        const double mi = node.numOr("mesh", -1), si = node.numOr("skin", -1);
+        if (mi >= 0 && mi < (double)meshSkin.size() && si >= 0 && si < (double)skins.size() && meshSkin[(size_t)mi] < 0)
+            meshSkin[(size_t)mi] = (int)si;
+    }
     // meshes: one Geometry::Mesh per triangle primitive (Assimp splits primitives into meshes)
     std::vector<std::vector<size_t>> meshPrims;
     for (const Json& m : arrOf("meshes")) {
@@ -601,14 +739,62 @@ ModelData LoadGltf(const fs::path& path) {
                 return ModelData{};
             }
             const size_t nv = P.size() / 3;
-            const bool hasN = attrs->get("NORMAL") && readAccessor((int)attrs->get("NORMAL")->num, 3, N);
-            const bool hasT = attrs->get("TEXCOORD_0") && readAccessor((int)attrs->get("TEXCOORD_0")->num, 2, T);
+            // (an attribute whose accessor does not hold one element per vertex is treated as absent)
+            const bool hasN = attrs->get("NORMAL") && readAccessor((int)attrs->get("NORMAL")->num, 3, N) && N.size() == 3 * nv;
+            const bool hasT = attrs->get("TEXCOORD_0") && readAccessor((int)attrs->get("TEXCOORD_0")->num, 2, T) && T.size() == 2 * nv;
             int ccomps = 0;
             if (const Json* cj = attrs->get("COLOR_0")) {
                 const int ai = (int)cj->num;
                 ccomps = (ai >= 0 && (size_t)ai < accessors.size() && accessors[ai].get("type") &&
                           accessors[ai].get("type")->str == "VEC4") ? 4 : 3;
-                if (!readAccessor(ai, ccomps, C)) ccomps = 0;
+                if (!readAccessor(ai, ccomps, C) || C.size() != (size_t)ccomps * nv) ccomps = 0;
+            }
+            std::vector<glm::ivec4> BI;
+            std::vector<glm::vec4> BW;
+            const int skinOf = meshSkin[meshPrims.size()];
+            if (skinOf >= 0 && attrs->get("JOINTS_0") && attrs->get("WEIGHTS_0")) {
+                std::vector<float> J, Wt;
+                const int wa = (int)attrs->get("WEIGHTS_0")->num;
+                const bool intWeights = wa >= 0 && (size_t)wa < accessors.size() && (int)accessors[wa].numOr("componentType", 5126) != 5126;
+                if (!readAccessor((int)attrs->get("JOINTS_0")->num, 4, J) || !readAccessor(wa, 4, Wt, intWeights) ||
+                    J.size() != 4 * nv || Wt.size() != 4 * nv) {
+                    LogError("glTF skin: JOINTS_0 / WEIGHTS_0 unreadable or not one per vertex", path.string());
+                    return ModelData{};
+                }
+                BI.assign(nv, glm::ivec4(0));
+                BW.assign(nv, glm::vec4(0.0f));
+                const std::vector<int>& joints = skinJoints[(size_t)skinOf];
+                for (size_t v = 0; v < nv; ++v) {
+                    int* bi = &BI[v].x;
+                    float* bw = &BW[v].x;
+                    for (int k = 0; k < 4; ++k) {
+                        const float w = Wt[4 * v + k], j = J[4 * v + k];
+                        if (!(w > 0.0f)) continue;  // AssignBoneWeight ignores weightless influences
+                        if (!(j >= 0.0f) || j >= (float)joints.size()) {
+                            LogError("glTF skin: a joint index beyond the skin", path.string());
+                            return ModelData{};
+                        }
+                        const int bone = joints[(size_t)j];
+                        int slot = -1;
+                        for (int e = 0; e < 4 && slot < 0; ++e)
+                            if (bw[e] <= 0.0f) slot = e;
+                        if (slot < 0) {  // full: replace the smallest when this one is larger
+                            int least = 0;
+                            for (int e = 1; e < 4; ++e)
+                                if (bw[e] < bw[least]) least = e;
+                            if (w > bw[least]) slot = least;
+                        }
+                        if (slot >= 0) {
+                            bi[slot] = bone;
+                            bw[slot] = w;
+                        }
+                    }
+                    const float total = bw[0] + bw[1] + bw[2] + bw[3];
+                    if (total > 0.0f) {
+                        const float inv = 1.0f / total;
+                        for (int e = 0; e < 4; ++e) bw[e] *= inv;
+                    }
+                }
             }
             if (const Json* ij = pr.get("indices")) {
                 if (!readAccessor((int)ij->num, 1, I)) {
@@ -634,6 +820,11 @@ ModelData LoadGltf(const fs::path& path) {
                     if (hasT) c.uv = glm::vec2(T[2 * v], T[2 * v + 1]);
                     c.c = ccomps ? glm::vec3(C[ccomps * v], C[ccomps * v + 1], C[ccomps * v + 2]) : glm::vec3(1.0f);
                     c.hasNormal = hasN;
+                    if (!BI.empty()) {
+                        c.skinned = true;
+                        c.bi = BI[v];
+                        c.bw = BW[v];
+                    }
                     corners.push_back(c);
                 }
             const int mat = (int)pr.numOr("material", -1);
@@ -643,7 +834,7 @@ ModelData LoadGltf(const fs::path& path) {
         meshPrims.push_back(std::move(ids));
     }
     // scene graph -> MeshInstance (parent * local, ModelLoader.cpp:505-540)
-    const std::vector<Json>& nodes = arrOf("nodes");
+    const std::vector<Json>& nodes = gnodes;
     std::function<void(int, const glm::mat4&, int)> visit = [&](int n, const glm::mat4& parent, int depth) {
         if (n < 0 || (size_t)n >= nodes.size() || depth > 64) return;
         const Json& node = nodes[n];

@@ -7,6 +7,7 @@
 // and frame timing (:6286-6343). Vulkan command recording is replaced by tri_set_frame /
 // tri_set_draws / tri_render on one tri_ctx per viewport.
 #include "trident/Renderer.h"
+#include "trident/Animation.h"
 #include "trident/ModelLoader.h"
 
 #include <algorithm>
@@ -188,6 +189,9 @@ struct Target {
     int Bones(const float* m, uint32_t n) const {
         return g ? tri_group_upload_bone_palette(g, m, n) : tri_upload_bone_palette(c, m, n);
     }
+    int Pose(tri_animset* const* sets, const tri_pose_instance* i, uint32_t n) const {
+        return g ? tri_group_pose_palette(g, sets, i, n) : tri_pose_palette(c, n ? sets[0] : nullptr, i, n);
+    }
     int Frame(const tri_global_ubo* u, const float* clear) const {
         return g ? tri_group_set_frame(g, u, clear) : tri_set_frame(c, u, clear);
     }
@@ -267,6 +271,7 @@ void Renderer::DestroyViewportTargets() {
     m_DeviceGeometry.clear();
     m_DeviceGeometryGeneration.clear();
     DropFonts();
+    DropPoseSets();
 }
 
 void Renderer::DropFonts() {  // only while no context that was given one can still render with it
@@ -752,12 +757,20 @@ void Renderer::GatherDraws() {
 
 // Renderer.cpp:3168-3245: each animated draw gets a slice [offset, offset + count) of one palette
 // (count clamped to s_MaxBonesPerSkeleton); draws without a palette keep offset 0 / count 0.
+// With device poses on, the draws the device poses (SetDevicePoseEnabled) take slices behind that palette instead:
+// m_PoseDraws, submitted by SubmitPoses.
 void Renderer::PrepareBonePaletteBuffer() {
     m_BonePalette.clear();
+    m_PoseDraws.clear();
+    std::vector<MeshDrawCommand*> posed;
     uint32_t total = 0;
     for (MeshDrawCommand& cmd : m_MeshDrawCommands) {
         cmd.m_BoneOffset = 0;
         cmd.m_BoneCount = 0;
+        if (cmd.m_AnimationComponent && PosesOnDevice(*cmd.m_AnimationComponent)) {
+            posed.push_back(&cmd);
+            continue;
+        }
         if (!cmd.m_AnimationComponent || cmd.m_AnimationComponent->m_BoneMatrices.empty()) continue;
         const auto& src = cmd.m_AnimationComponent->m_BoneMatrices;
         const uint32_t n = (uint32_t)std::min<size_t>(src.size(), s_MaxBonesPerSkeleton);
@@ -770,6 +783,134 @@ void Renderer::PrepareBonePaletteBuffer() {
             m_BonePalette.insert(m_BonePalette.end(), m, m + 16);
         }
     }
+    for (MeshDrawCommand* cmd : posed) {  // behind the uploaded prefix, back to back
+        const AnimationComponent& a = *cmd->m_AnimationComponent;
+        const size_t bones = Animation::AnimationAssetService::Get().GetSkeleton(a.m_SkeletonAssetHandle)->m_Bones.size();
+        cmd->m_BoneOffset = total;
+        cmd->m_BoneCount = (uint32_t)std::min<size_t>(bones, s_MaxBonesPerSkeleton);
+        m_PoseDraws.push_back({a.m_SkeletonAssetHandle, a.m_AnimationAssetHandle, a.m_CurrentClipIndex, a.m_CurrentTime, total});
+        total += cmd->m_BoneCount;
+    }
+}
+
+bool Renderer::PosesOnDevice(const AnimationComponent& a) const {
+    if (!m_DevicePose || a.m_SkeletonAssetHandle == Animation::AnimationAssetService::s_InvalidHandle) return false;
+    const auto& service = Animation::AnimationAssetService::Get();
+    if (m_PoseCompatibleGeneration != service.GetGeneration()) {  // something was registered: look again
+        m_PoseCompatible.clear();
+        m_PoseCompatibleGeneration = service.GetGeneration();
+    }
+    const auto key = std::make_pair(a.m_SkeletonAssetHandle, a.m_AnimationAssetHandle);
+    auto known = m_PoseCompatible.find(key);
+    if (known == m_PoseCompatible.end()) {
+        const Animation::Skeleton* sk = service.GetSkeleton(key.first);
+        known = m_PoseCompatible.emplace(key, sk && Animation::DevicePoseCompatible(*sk, service.GetAnimationClips(key.second))).first;
+    }
+    return known->second;
+}
+
+void Renderer::DropPoseSets() {  // only while no context can still pose from them
+    for (auto& it : m_PoseSets) tri_animset_destroy(it.second.m_Set);
+    m_PoseSets.clear();
+}
+
+// The (skeleton asset, animation asset) pair on a device, added to that device's set at its first use: the decomposed
+// defaults, and every clip with its channels resolved against the skeleton (a channel without a bone is left out).
+const Renderer::PoseAssetOnDevice* Renderer::PoseAssetOn(int32_t device, size_t skeleton, size_t animation) {
+    if (m_PoseSets.empty()) m_PoseSetsGeneration = Animation::AnimationAssetService::Get().GetGeneration();
+    PoseDeviceSet& ds = m_PoseSets[device];
+    if (!ds.m_Set && tri_animset_create(device, &ds.m_Set) != TRI_OK) return nullptr;
+    const auto key = std::make_pair(skeleton, animation);
+    auto have = ds.m_Assets.find(key);
+    if (have != ds.m_Assets.end()) return &have->second;
+    const auto& service = Animation::AnimationAssetService::Get();
+    const Animation::Skeleton* sk = service.GetSkeleton(skeleton);
+    if (!sk) return nullptr;
+    std::vector<tri_pose_bone> bones(sk->m_Bones.size());
+    for (size_t b = 0; b < bones.size(); ++b) {
+        const Animation::Bone& src = sk->m_Bones[b];
+        const Animation::TransformDecomposition d = Animation::DecomposeBindTransform(src.m_LocalBindTransform);
+        tri_pose_bone& o = bones[b];
+        std::memset(&o, 0, sizeof o);
+        o.parent = src.m_ParentIndex;
+        o.translation[0] = d.m_Translation.x; o.translation[1] = d.m_Translation.y; o.translation[2] = d.m_Translation.z;
+        o.rotation[0] = d.m_Rotation.w; o.rotation[1] = d.m_Rotation.x; o.rotation[2] = d.m_Rotation.y; o.rotation[3] = d.m_Rotation.z;
+        o.scale[0] = d.m_Scale.x; o.scale[1] = d.m_Scale.y; o.scale[2] = d.m_Scale.z;
+        CopyMat(src.m_InverseBindMatrix, o.inverse_bind);
+    }
+    PoseAssetOnDevice out;
+    if (tri_animset_add_skeleton(ds.m_Set, bones.data(), (uint32_t)bones.size(), sk->m_RootBoneIndex, &out.m_Skeleton) != TRI_OK)
+        return nullptr;
+    if (const std::vector<Animation::AnimationClip>* clips = service.GetAnimationClips(animation)) {
+        for (const Animation::AnimationClip& clip : *clips) {
+            std::vector<tri_pose_channel> channels;
+            std::vector<float> vt, vv, qt, qv;
+            auto vec = [&](const std::vector<Animation::VectorKeyframe>& keys, uint32_t& first, uint32_t& count) {
+                first = (uint32_t)vt.size();
+                count = (uint32_t)keys.size();
+                for (const auto& k : keys) {
+                    vt.push_back(k.m_TimeSeconds);
+                    vv.insert(vv.end(), {k.m_Value.x, k.m_Value.y, k.m_Value.z});
+                }
+            };
+            for (const Animation::TransformChannel& ch : clip.m_Channels) {
+                const int bone = Animation::ResolveChannelBoneIndex(ch, *sk, clip.m_Name);
+                if (bone < 0 || (size_t)bone >= bones.size()) continue;
+                tri_pose_channel o{};
+                o.bone = (uint32_t)bone;
+                vec(ch.m_TranslationKeys, o.translation_first, o.translation_count);
+                vec(ch.m_ScaleKeys, o.scale_first, o.scale_count);
+                o.rotation_first = (uint32_t)qt.size();
+                o.rotation_count = (uint32_t)ch.m_RotationKeys.size();
+                for (const auto& k : ch.m_RotationKeys) {
+                    qt.push_back(k.m_TimeSeconds);
+                    qv.insert(qv.end(), {k.m_Value.w, k.m_Value.x, k.m_Value.y, k.m_Value.z});
+                }
+                channels.push_back(o);
+            }
+            uint32_t index = 0;
+            if (tri_animset_add_clip(ds.m_Set, out.m_Skeleton, channels.data(), (uint32_t)channels.size(), vt.data(), vv.data(),
+                                     (uint32_t)vt.size(), qt.data(), qv.data(), (uint32_t)qt.size(), clip.m_DurationSeconds,
+                                     &index) != TRI_OK)
+                return nullptr;
+            out.m_Clips.push_back(index);
+        }
+    }
+    return &ds.m_Assets.emplace(key, std::move(out)).first->second;
+}
+
+// This frame's posed draws onto a target: one tri_pose_palette (every band of a group) behind the uploaded prefix.
+bool Renderer::SubmitPoses(ViewportContext& vc) {
+    const Target t{vc.m_Ctx, vc.m_Group};
+    std::vector<int32_t> devices;
+    if (vc.m_Group) {
+        for (int32_t d : m_Devices)
+            if (std::find(devices.begin(), devices.end(), d) == devices.end()) devices.push_back(d);
+    } else {
+        tri_image img{};
+        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK) return false;
+        devices.push_back(img.device);
+    }
+    std::vector<tri_animset*> sets;
+    m_PoseInstances.clear();
+    for (size_t di = 0; di < devices.size(); ++di) {
+        for (size_t i = 0; i < m_PoseDraws.size(); ++i) {
+            const PoseDraw& p = m_PoseDraws[i];
+            const PoseAssetOnDevice* on = PoseAssetOn(devices[di], p.m_Skeleton, p.m_Animation);
+            if (!on) return false;
+            const uint32_t clip = p.m_Clip < on->m_Clips.size() ? on->m_Clips[p.m_Clip] : TRI_POSE_BIND;
+            const tri_pose_instance inst{on->m_Skeleton, clip, p.m_Time, p.m_Offset};
+            if (di == 0) m_PoseInstances.push_back(inst);
+            else if (std::memcmp(&m_PoseInstances[i], &inst, sizeof inst) != 0) {  // the sets were filled in one order
+                LogError("device poses", "the devices' sets disagree");
+                return false;
+            }
+        }
+        if (!m_PoseDraws.empty()) sets.push_back(m_PoseSets[devices[di]].m_Set);
+    }
+    if (t.Pose(sets.data(), m_PoseInstances.data(), (uint32_t)m_PoseInstances.size()) != TRI_OK) return false;
+    vc.m_HasPosedSuffix = !m_PoseInstances.empty();
+    return true;
 }
 
 void Renderer::BuildDrawList(std::vector<tri_draw>& out) const {  // Renderer.cpp:5110-5151
@@ -1039,6 +1180,7 @@ bool Renderer::PrepareViewport(ViewportContext& vc) {
         vc.m_AiGeneration = 0;
         vc.m_Shadow = tri_shadow_config{};  // a fresh context starts without the pre-pass and bones
         vc.m_BonePalette.clear();
+        vc.m_HasPosedSuffix = false;
     }
     const Target t{vc.m_Ctx, vc.m_Group};
     if (vc.m_GeometryGeneration != m_GeometryGeneration && multi) {
@@ -1138,6 +1280,12 @@ bool Renderer::SubmitTarget(ViewportContext& vc, const tri_global_ubo& ubo, cons
             return false;
         }
         vc.m_BonePalette = m_BonePalette;
+        vc.m_HasPosedSuffix = false;  // (an upload drops the posed suffix)
+        ++m_BonePaletteUploads;
+    }
+    if ((!m_PoseDraws.empty() || vc.m_HasPosedSuffix) && !SubmitPoses(vc)) {
+        LogError("device poses", tri_last_error());
+        return false;
     }
     const float clear[4] = {m_ClearColor.x, m_ClearColor.y, m_ClearColor.z, m_ClearColor.w};
     if (t.Frame(&ubo, clear) != TRI_OK || t.Draws(draws.data(), (uint32_t)draws.size()) != TRI_OK ||
@@ -1160,6 +1308,10 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     // the device tensor handed out by GetFrameReadbackDeviceTensor was valid until here: its slot serves again (an
     // unconsumed pending tensor moves from the slot's pinned buffer into host memory first)
     ReleaseHeldReadbackSlot(true);
+    if (!m_PoseSets.empty() && m_PoseSetsGeneration != Animation::AnimationAssetService::Get().GetGeneration()) {
+        FinishFrame();   // an asset was registered or replaced since the devices' sets were filled: no frame in flight
+        DropPoseSets();  // may still pose from them, and they are filled again from what the service holds now
+    }
     GatherDraws();
     PrepareBonePaletteBuffer();
     std::vector<tri_draw> draws;

@@ -3,6 +3,8 @@
 // MeshComponent (ApplicationLayer.cpp:677-718), lights as LightComponent entities.
 #include "trident_app.h"
 
+#include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <exception>
 #include <string>
@@ -11,6 +13,8 @@
 #include "trident/Renderer.h"
 #include "trident/SceneFile.h"
 #include "trident/ModelLoader.h"
+#include "trident/Animation.h"
+#include "trident/AnimationSystem.h"
 
 #include <algorithm>
 #include <array>
@@ -22,6 +26,7 @@ struct trident_app {
     ECS::Registry registry;
     EditorCamera editor;
     RuntimeCamera runtime;
+    ECS::AnimationSystem animation{&renderer};
 };
 
 namespace {
@@ -327,6 +332,18 @@ int trident_app_set_entity_bones(trident_app* app, uint32_t entity, const float*
         for (uint32_t b = 0; b < count; ++b)
             for (int c = 0; c < 4; ++c)
                 for (int r = 0; r < 4; ++r) a.m_BoneMatrices[b][c][r] = matrices[16 * b + 4 * c + r];
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_entities_bones(trident_app* app, const uint32_t* entities, uint32_t entity_count,
+                                   const float* matrices, uint32_t matrices_per_entity) {
+    return Guard(app, [&] {
+        if (entity_count && (!entities || (matrices_per_entity && !matrices))) return TRI_E_INVALID;
+        for (uint32_t i = 0; i < entity_count; ++i) {
+            const int rc = trident_app_set_entity_bones(app, entities[i], matrices + 16ull * matrices_per_entity * i, matrices_per_entity);
+            if (rc != TRI_OK) return rc;
+        }
         return TRI_OK;
     });
 }
@@ -950,6 +967,354 @@ int trident_app_frame_timing(trident_app* app, double out[7]) {
         out[4] = s.MaximumFPS;
         out[5] = s.AverageFPS;
         out[6] = (double)app->renderer.GetFrameTimingHistoryCount();
+        return TRI_OK;
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+glm::mat4 Mat4From(const float* m) {
+    glm::mat4 r(1.0f);
+    for (int c = 0; c < 4; ++c)
+        for (int k = 0; k < 4; ++k) r[c][k] = m[4 * c + k];
+    return r;
+}
+
+size_t AnimHandle(uint64_t handle) {
+    return handle == UINT64_MAX ? Animation::AnimationAssetService::s_InvalidHandle : (size_t)handle;
+}
+
+size_t AnimClip(uint32_t clip) { return clip == UINT32_MAX ? Animation::AnimationAssetService::s_InvalidHandle : (size_t)clip; }
+
+template <typename F>
+int GuardAnim(F&& f) {
+    try {
+        return f();
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int trident_app_set_entity_animation(trident_app* app, uint32_t entity, const char* skeleton_asset_id,
+                                     const char* animation_asset_id, const char* clip, float time, float speed,
+                                     int looping, int playing) {
+    return Guard(app, [&] {
+        AnimationComponent& a = app->registry.HasComponent<AnimationComponent>(entity)
+                                    ? app->registry.GetComponent<AnimationComponent>(entity)
+                                    : app->registry.AddComponent<AnimationComponent>(entity);
+        a.m_SkeletonAssetId = skeleton_asset_id ? skeleton_asset_id : "";
+        a.m_AnimationAssetId = animation_asset_id ? animation_asset_id : "";
+        a.m_CurrentClip = clip ? clip : "";
+        a.m_CurrentTime = time;
+        a.m_PlaybackSpeed = speed;
+        a.m_IsLooping = looping != 0;
+        a.m_IsPlaying = playing != 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_update_animation(trident_app* app, float dt) {
+    return Guard(app, [&] {
+        app->animation.Update(app->registry, dt);
+        return TRI_OK;
+    });
+}
+
+int trident_app_initialise_pose(trident_app* app, uint32_t entity) {
+    return Guard(app, [&] {
+        if (!app->registry.HasComponent<AnimationComponent>(entity)) return TRI_E_INVALID;
+        ECS::AnimationSystem::InitialisePose(app->registry.GetComponent<AnimationComponent>(entity));
+        return TRI_OK;
+    });
+}
+
+int trident_app_entity_pose(trident_app* app, uint32_t entity, float* out, uint32_t capacity, uint32_t* count) {
+    return Guard(app, [&] {
+        if (!count || !app->registry.HasComponent<AnimationComponent>(entity)) return TRI_E_INVALID;
+        AnimationComponent& a = app->registry.GetComponent<AnimationComponent>(entity);
+        if (app->renderer.PosesOnDevice(a)) ECS::AnimationSystem::EvaluatePose(a);
+        *count = (uint32_t)a.m_BoneMatrices.size();
+        if (!out) return TRI_OK;
+        if (capacity < *count) return TRI_E_INVALID;
+        for (size_t b = 0; b < a.m_BoneMatrices.size(); ++b)
+            for (int c = 0; c < 4; ++c)
+                for (int k = 0; k < 4; ++k) out[16 * b + 4 * c + k] = a.m_BoneMatrices[b][c][k];
+        return TRI_OK;
+    });
+}
+
+int trident_app_entity_animation_state(trident_app* app, uint32_t entity, float* time, int* playing, uint64_t handles[3]) {
+    return Guard(app, [&] {
+        if (!time || !playing || !handles || !app->registry.HasComponent<AnimationComponent>(entity)) return TRI_E_INVALID;
+        const AnimationComponent& a = app->registry.GetComponent<AnimationComponent>(entity);
+        *time = a.m_CurrentTime;
+        *playing = a.m_IsPlaying ? 1 : 0;
+        const size_t h[3] = {a.m_SkeletonAssetHandle, a.m_AnimationAssetHandle, a.m_CurrentClipIndex};
+        for (int i = 0; i < 3; ++i) handles[i] = h[i] == Animation::AnimationAssetService::s_InvalidHandle ? UINT64_MAX : (uint64_t)h[i];
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_device_pose(trident_app* app, int enabled) {
+    return Guard(app, [&] {
+        app->renderer.SetDevicePoseEnabled(enabled != 0);
+        return TRI_OK;
+    });
+}
+
+int trident_app_bone_palette_uploads(trident_app* app, uint64_t* count) {
+    return Guard(app, [&] {
+        if (!count) return TRI_E_INVALID;
+        *count = app->renderer.GetBonePaletteUploadCount();
+        return TRI_OK;
+    });
+}
+
+int trident_anim_decompose(const float local_bind[16], float out[10]) {
+    if (!local_bind || !out) return TRI_E_INVALID;
+    const Animation::TransformDecomposition d = Animation::DecomposeBindTransform(Mat4From(local_bind));
+    const float v[10] = {d.m_Translation.x, d.m_Translation.y, d.m_Translation.z, d.m_Rotation.w, d.m_Rotation.x,
+                         d.m_Rotation.y, d.m_Rotation.z, d.m_Scale.x, d.m_Scale.y, d.m_Scale.z};
+    std::memcpy(out, v, sizeof v);
+    return TRI_OK;
+}
+
+int trident_anim_register(const char* asset_id, uint32_t bone_count, const int32_t* parents, const float* local_binds,
+                          const float* inverse_binds, const char* const* source_names, int32_t root_index,
+                          uint64_t* handle) {
+    if (!asset_id || !handle || (bone_count && (!parents || !local_binds || !inverse_binds))) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::Skeleton sk;
+        sk.m_Bones.resize(bone_count);
+        for (uint32_t b = 0; b < bone_count; ++b) {
+            Animation::Bone& bone = sk.m_Bones[b];
+            bone.m_SourceName = source_names && source_names[b] ? source_names[b] : "Bone" + std::to_string(b);
+            bone.m_ParentIndex = parents[b];
+            bone.m_LocalBindTransform = Mat4From(local_binds + 16 * (size_t)b);
+            bone.m_InverseBindMatrix = Mat4From(inverse_binds + 16 * (size_t)b);
+        }
+        sk.m_RootBoneIndex = root_index;
+        Animation::FinaliseSkeleton(sk);
+        const size_t h = Animation::AnimationAssetService::Get().RegisterRuntimeAsset(asset_id, std::move(sk), {});
+        if (h == Animation::AnimationAssetService::s_InvalidHandle) return TRI_E_INVALID;
+        *handle = (uint64_t)h;
+        return TRI_OK;
+    });
+}
+
+int trident_anim_add_clip(uint64_t handle, const char* name, float duration, const tri_pose_channel* channels,
+                          const int32_t* stored_bones, const char* const* source_names, uint32_t channel_count,
+                          const float* vec_times, const float* vec_values, uint32_t vec_count, const float* quat_times,
+                          const float* quat_values, uint32_t quat_count, uint32_t* clip_index) {
+    if (!name || !clip_index || (channel_count && !channels) || (vec_count && (!vec_times || !vec_values)) ||
+        (quat_count && (!quat_times || !quat_values)))
+        return TRI_E_INVALID;
+    return GuardAnim([&] {
+        auto& service = Animation::AnimationAssetService::Get();
+        const Animation::Skeleton* sk = service.GetSkeleton(AnimHandle(handle));
+        const std::vector<Animation::AnimationClip>* have = service.GetAnimationClips(AnimHandle(handle));
+        if (!sk || !have) return TRI_E_INVALID;
+        Animation::AnimationClip clip;
+        clip.m_Name = name;
+        clip.m_DurationSeconds = duration;
+        clip.m_TicksPerSecond = 1000.0f;
+        auto vec_keys = [&](uint32_t first, uint32_t count, std::vector<Animation::VectorKeyframe>& out) {
+            if ((uint64_t)first + count > vec_count) return false;
+            for (uint32_t i = first; i < first + count; ++i)
+                out.push_back({vec_times[i], glm::vec3(vec_values[3 * (size_t)i], vec_values[3 * (size_t)i + 1], vec_values[3 * (size_t)i + 2])});
+            return true;
+        };
+        for (uint32_t c = 0; c < channel_count; ++c) {
+            Animation::TransformChannel ch;
+            ch.m_BoneIndex = stored_bones ? stored_bones[c] : (int)channels[c].bone;
+            if (source_names && source_names[c]) ch.m_SourceBoneName = source_names[c];
+            if (!vec_keys(channels[c].translation_first, channels[c].translation_count, ch.m_TranslationKeys) ||
+                !vec_keys(channels[c].scale_first, channels[c].scale_count, ch.m_ScaleKeys) ||
+                (uint64_t)channels[c].rotation_first + channels[c].rotation_count > quat_count)
+                return TRI_E_INVALID;
+            for (uint32_t i = channels[c].rotation_first; i < channels[c].rotation_first + channels[c].rotation_count; ++i)
+                ch.m_RotationKeys.push_back({quat_times[i], glm::quat(quat_values[4 * (size_t)i], quat_values[4 * (size_t)i + 1],
+                                                                      quat_values[4 * (size_t)i + 2], quat_values[4 * (size_t)i + 3])});
+            clip.m_Channels.push_back(std::move(ch));
+        }
+        // re-register the asset under its id with the clip appended (the handle stays)
+        std::string id;
+        Animation::Skeleton skeleton = *sk;
+        std::vector<Animation::AnimationClip> clips = *have;
+        clips.push_back(std::move(clip));
+        *clip_index = (uint32_t)clips.size() - 1;
+        if (!service.AssetId(AnimHandle(handle), id)) return TRI_E_INVALID;
+        return service.RegisterRuntimeAsset(id, std::move(skeleton), std::move(clips)) == AnimHandle(handle) ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_anim_load(const char* path, uint64_t* handle) {
+    if (!path || !handle) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        const size_t h = Animation::AnimationAssetService::Get().AcquireSkeleton(path);
+        if (h == Animation::AnimationAssetService::s_InvalidHandle) return TRI_E_INVALID;
+        *handle = (uint64_t)h;
+        return TRI_OK;
+    });
+}
+
+int trident_anim_describe(uint64_t handle, char* out, uint64_t capacity, uint64_t* needed) {
+    if (!needed) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        auto& service = Animation::AnimationAssetService::Get();
+        const Animation::Skeleton* sk = service.GetSkeleton(AnimHandle(handle));
+        const std::vector<Animation::AnimationClip>* clips = service.GetAnimationClips(AnimHandle(handle));
+        if (!sk || !clips) return TRI_E_INVALID;
+        std::string j;
+        auto num = [&](float v) {
+            char buf[40];
+            if (std::isfinite(v)) std::snprintf(buf, sizeof buf, "%.9g", (double)v);
+            else std::snprintf(buf, sizeof buf, "null");
+            j += buf;
+        };
+        auto str = [&](const std::string& v) {
+            j += '"';
+            for (char c : v) {
+                if (c == '"' || c == '\\') j += '\\';
+                j += (unsigned char)c < 0x20 ? '?' : c;
+            }
+            j += '"';
+        };
+        auto mat = [&](const glm::mat4& m) {
+            j += '[';
+            for (int k = 0; k < 16; ++k) {
+                if (k) j += ',';
+                num(m[k / 4][k % 4]);
+            }
+            j += ']';
+        };
+        j += "{\"root\":" + std::to_string(sk->m_RootBoneIndex) + ",\"bones\":[";
+        for (size_t b = 0; b < sk->m_Bones.size(); ++b) {
+            const Animation::Bone& bone = sk->m_Bones[b];
+            j += b ? ",{\"name\":" : "{\"name\":";
+            str(bone.m_Name);
+            j += ",\"source\":";
+            str(bone.m_SourceName);
+            j += ",\"parent\":" + std::to_string(bone.m_ParentIndex) + ",\"children\":[";
+            for (size_t c = 0; c < bone.m_Children.size(); ++c) j += (c ? "," : "") + std::to_string(bone.m_Children[c]);
+            j += "],\"local\":";
+            mat(bone.m_LocalBindTransform);
+            j += ",\"inverse\":";
+            mat(bone.m_InverseBindMatrix);
+            j += '}';
+        }
+        j += "],\"clips\":[";
+        for (size_t c = 0; c < clips->size(); ++c) {
+            const Animation::AnimationClip& clip = (*clips)[c];
+            j += c ? ",{\"name\":" : "{\"name\":";
+            str(clip.m_Name);
+            j += ",\"duration\":";
+            num(clip.m_DurationSeconds);
+            j += ",\"ticks\":";
+            num(clip.m_TicksPerSecond);
+            j += ",\"channels\":[";
+            for (size_t h = 0; h < clip.m_Channels.size(); ++h) {
+                const Animation::TransformChannel& ch = clip.m_Channels[h];
+                j += h ? ",{\"bone\":" : "{\"bone\":";
+                j += std::to_string(ch.m_BoneIndex) + ",\"source\":";
+                str(ch.m_SourceBoneName);
+                auto vec = [&](const char* key, const std::vector<Animation::VectorKeyframe>& keys) {
+                    j += std::string(",\"") + key + "\":[";
+                    for (size_t k = 0; k < keys.size(); ++k) {
+                        j += k ? ",[" : "[";
+                        num(keys[k].m_TimeSeconds); j += ','; num(keys[k].m_Value.x); j += ','; num(keys[k].m_Value.y); j += ',';
+                        num(keys[k].m_Value.z); j += ']';
+                    }
+                    j += ']';
+                };
+                vec("t", ch.m_TranslationKeys);
+                j += ",\"r\":[";
+                for (size_t k = 0; k < ch.m_RotationKeys.size(); ++k) {
+                    const Animation::QuaternionKeyframe& q = ch.m_RotationKeys[k];
+                    j += k ? ",[" : "[";
+                    num(q.m_TimeSeconds); j += ','; num(q.m_Value.w); j += ','; num(q.m_Value.x); j += ','; num(q.m_Value.y); j += ',';
+                    num(q.m_Value.z); j += ']';
+                }
+                j += ']';
+                vec("s", ch.m_ScaleKeys);
+                j += '}';
+            }
+            j += "]}";
+        }
+        j += "]}";
+        *needed = j.size() + 1;
+        if (!out) return TRI_OK;
+        if (capacity < j.size() + 1) return TRI_E_INVALID;
+        std::memcpy(out, j.c_str(), j.size() + 1);
+        return TRI_OK;
+    });
+}
+
+int trident_anim_clip_index(uint64_t handle, const char* name, uint32_t* clip_index) {
+    if (!name || !clip_index) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        const size_t i = Animation::AnimationAssetService::Get().ResolveClipIndex(AnimHandle(handle), name);
+        if (i == Animation::AnimationAssetService::s_InvalidHandle) return TRI_E_INVALID;
+        *clip_index = (uint32_t)i;
+        return TRI_OK;
+    });
+}
+
+int trident_anim_resolve_channels(uint64_t handle, uint32_t clip_index, int32_t* bones, uint32_t capacity, uint32_t* count) {
+    if (!count) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        auto& service = Animation::AnimationAssetService::Get();
+        const Animation::Skeleton* sk = service.GetSkeleton(AnimHandle(handle));
+        const Animation::AnimationClip* clip = service.GetClip(AnimHandle(handle), AnimClip(clip_index));
+        if (!sk || !clip) return TRI_E_INVALID;
+        *count = (uint32_t)clip->m_Channels.size();
+        if (!bones || capacity < *count) return bones ? TRI_E_INVALID : TRI_OK;
+        for (uint32_t c = 0; c < *count; ++c) bones[c] = Animation::ResolveChannelBoneIndex(clip->m_Channels[c], *sk, clip->m_Name);
+        return TRI_OK;
+    });
+}
+
+int trident_anim_evaluate(uint64_t handle, uint32_t clip_index, float time, float* out, uint32_t capacity, uint32_t* count) {
+    if (!count) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationPlayer player(Animation::AnimationAssetService::Get());
+        player.SetSkeletonHandle(AnimHandle(handle));
+        player.SetAnimationHandle(AnimHandle(handle));
+        player.SetClipIndex(AnimClip(clip_index));
+        player.EvaluateAt(time);
+        std::vector<glm::mat4> pose;
+        player.CopyPoseTo(pose);
+        *count = (uint32_t)pose.size();
+        if (!out) return TRI_OK;
+        if (capacity < pose.size()) return TRI_E_INVALID;
+        for (size_t b = 0; b < pose.size(); ++b)
+            for (int c = 0; c < 4; ++c)
+                for (int k = 0; k < 4; ++k) out[16 * b + 4 * c + k] = pose[b][c][k];
+        return TRI_OK;
+    });
+}
+
+int trident_anim_advance(uint64_t handle, uint32_t clip_index, float time, float speed, int looping, int playing, float dt,
+                         float* out_time, int* out_playing) {
+    if (!out_time || !out_playing) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationPlayer player(Animation::AnimationAssetService::Get());
+        player.SetSkeletonHandle(AnimHandle(handle));
+        player.SetAnimationHandle(AnimHandle(handle));
+        player.SetClipIndex(AnimClip(clip_index));
+        player.SetCurrentTime(time);
+        player.SetPlaybackSpeed(speed);
+        player.SetLooping(looping != 0);
+        player.SetIsPlaying(playing != 0);
+        player.Update(dt);
+        *out_time = player.GetCurrentTime();
+        *out_playing = player.IsPlaying() ? 1 : 0;
         return TRI_OK;
     });
 }

@@ -229,6 +229,38 @@ TEXT_QUAD_DTYPE = np.dtype(("<f4", 12))
 assert C.sizeof(TriTextQuad) == 48 and TEXT_QUAD_DTYPE.itemsize == 48
 
 
+# skeletal poses evaluated on the device (include/tri_raster.h)
+TRI_POSE_MAX_BONES, TRI_POSE_PALETTE_BONES, TRI_POSE_BIND = 256, 128, 0xFFFFFFFF
+TRI_POSE_MAX_INSTANCES, TRI_POSE_MAX_PALETTE = 65536, 1 << 24
+
+
+class TriPoseBone(C.Structure):
+    _fields_ = [("parent", C.c_int32), ("reserved", C.c_uint32 * 3), ("translation", C.c_float * 4),
+                ("rotation", C.c_float * 4), ("scale", C.c_float * 4), ("inverse_bind", C.c_float * 16)]
+
+
+class TriPoseChannel(C.Structure):
+    _fields_ = [("bone", C.c_uint32), ("translation_first", C.c_uint32), ("translation_count", C.c_uint32),
+                ("rotation_first", C.c_uint32), ("rotation_count", C.c_uint32), ("scale_first", C.c_uint32),
+                ("scale_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TriPoseInstance(C.Structure):
+    _fields_ = [("skeleton", C.c_uint32), ("clip", C.c_uint32), ("time", C.c_float), ("palette_offset", C.c_uint32)]
+
+
+# the same records as numpy rows (rotation is w, x, y, z)
+POSE_BONE_DTYPE = np.dtype([("parent", "<i4"), ("reserved", "<u4", 3), ("translation", "<f4", 4), ("rotation", "<f4", 4),
+                            ("scale", "<f4", 4), ("inverse_bind", "<f4", 16)])
+POSE_CHANNEL_DTYPE = np.dtype([("bone", "<u4"), ("translation_first", "<u4"), ("translation_count", "<u4"),
+                               ("rotation_first", "<u4"), ("rotation_count", "<u4"), ("scale_first", "<u4"),
+                               ("scale_count", "<u4"), ("reserved", "<u4")])
+POSE_INSTANCE_DTYPE = np.dtype([("skeleton", "<u4"), ("clip", "<u4"), ("time", "<f4"), ("palette_offset", "<u4")])
+assert C.sizeof(TriPoseBone) == POSE_BONE_DTYPE.itemsize == 128
+assert C.sizeof(TriPoseChannel) == POSE_CHANNEL_DTYPE.itemsize == 32
+assert C.sizeof(TriPoseInstance) == POSE_INSTANCE_DTYPE.itemsize == 16
+
+
 class TriXferConfig(C.Structure):
     _fields_ = [("width", C.c_uint32), ("band_y", C.POINTER(C.c_uint32)), ("display", C.c_uint32),
                 ("format", C.c_uint32), ("slot_bytes", C.c_uint32), ("alpha", C.c_uint32), ("nbuf", C.c_uint32)]
@@ -300,6 +332,14 @@ CABI_FUNCTIONS = [
     ("tri_font_destroy", C.c_int, [C.c_void_p]),
     ("tri_set_text", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("tri_group_set_text", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32]),
+    ("tri_animset_create", C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
+    ("tri_animset_destroy", C.c_int, [C.c_void_p]),
+    ("tri_animset_add_skeleton", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]),
+    ("tri_animset_add_clip", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint32)]),
+    ("tri_pose_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("tri_read_bone_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("tri_group_pose_palette", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32]),
     ("tri_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("tri_get_timing", C.c_int, [C.c_void_p, C.POINTER(TriTiming)]),
     ("tri_get_frame_stats", C.c_int, [C.c_void_p, C.POINTER(TriFrameStats)]),

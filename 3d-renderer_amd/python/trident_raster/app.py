@@ -29,6 +29,7 @@ _APP_FUNCTIONS = [
     ("trident_app_set_entity_transform", C.c_int, [C.c_void_p, C.c_uint32, _f3, _f3, _f3]),
     ("trident_app_set_entity_visible", C.c_int, [C.c_void_p, C.c_uint32, C.c_int]),
     ("trident_app_set_entity_bones", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    ("trident_app_set_entities_bones", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     ("trident_app_set_assets_dir", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]),
     ("trident_app_viewport_texture", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage)]),
     ("trident_app_set_light_shadow_caster", C.c_int, [C.c_void_p, C.c_uint32, C.c_int]),
@@ -118,6 +119,28 @@ _APP_FUNCTIONS = [
     ("trident_font_metrics", C.c_int, [C.c_void_p, C.POINTER(C.c_float * 3)]),
     ("trident_font_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4), C.c_char_p,
                                       C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_app_set_entity_animation", C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_float,
+                                                   C.c_float, C.c_int, C.c_int]),
+    ("trident_app_update_animation", C.c_int, [C.c_void_p, C.c_float]),
+    ("trident_app_initialise_pose", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("trident_app_entity_pose", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_app_entity_animation_state", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                                     C.POINTER(C.c_uint64 * 3)]),
+    ("trident_app_set_device_pose", C.c_int, [C.c_void_p, C.c_int]),
+    ("trident_app_bone_palette_uploads", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    ("trident_anim_decompose", C.c_int, [C.c_void_p, C.POINTER(C.c_float * 10)]),
+    ("trident_anim_register", C.c_int, [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p),
+                                        C.c_int32, C.POINTER(C.c_uint64)]),
+    ("trident_anim_add_clip", C.c_int, [C.c_uint64, C.c_char_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p),
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.POINTER(C.c_uint32)]),
+    ("trident_anim_load", C.c_int, [C.c_char_p, C.POINTER(C.c_uint64)]),
+    ("trident_anim_describe", C.c_int, [C.c_uint64, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("trident_anim_clip_index", C.c_int, [C.c_uint64, C.c_char_p, C.POINTER(C.c_uint32)]),
+    ("trident_anim_resolve_channels", C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_anim_evaluate", C.c_int, [C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_anim_advance", C.c_int, [C.c_uint64, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
+                                       C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 ]
 
 _lib = None
@@ -258,6 +281,52 @@ class TridentApp:
         m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 16)
         _check(self._lib.trident_app_set_entity_bones(self._h, entity, m.ctypes.data if m.size else None,
                                                       m.shape[0]), "set_entity_bones")
+
+    def set_entities_bones(self, entities, matrices):
+        """set_entity_bones for many entities in one call: matrices float32 [entities, n, 16]."""
+        e = np.ascontiguousarray(entities, np.uint32)
+        m = np.ascontiguousarray(matrices, np.float32).reshape(e.size, -1, 16)
+        _check(self._lib.trident_app_set_entities_bones(self._h, e.ctypes.data if e.size else None, e.size,
+                                                        m.ctypes.data if m.size else None, m.shape[1]), "set_entities_bones")
+
+    def set_entity_animation(self, entity, skeleton=None, animation=None, clip=None, time=0.0, speed=1.0, looping=True,
+                             playing=True):
+        """The playback fields of the entity's AnimationComponent (asset ids as given to anim_register)."""
+        enc = lambda s: None if s is None else s.encode()  # noqa: E731
+        _check(self._lib.trident_app_set_entity_animation(self._h, entity, enc(skeleton), enc(animation), enc(clip), time,
+                                                          speed, int(looping), int(playing)), "set_entity_animation")
+
+    def update_animation(self, dt):
+        """ECS::AnimationSystem::Update."""
+        _check(self._lib.trident_app_update_animation(self._h, dt), "update_animation")
+
+    def initialise_pose(self, entity):
+        _check(self._lib.trident_app_initialise_pose(self._h, entity), "initialise_pose")
+
+    def entity_pose(self, entity):
+        """The entity's bone matrices, float32 [n, 16] (device mode: evaluated on the CPU on demand)."""
+        n = C.c_uint32()
+        _check(self._lib.trident_app_entity_pose(self._h, entity, None, 0, C.byref(n)), "entity_pose")
+        out = np.empty((n.value, 16), np.float32)
+        _check(self._lib.trident_app_entity_pose(self._h, entity, out.ctypes.data if n.value else None, n.value,
+                                                 C.byref(n)), "entity_pose")
+        return out
+
+    def entity_animation_state(self, entity):
+        """(time, playing, skeleton handle, animation handle, clip index); an invalid handle or index is None."""
+        t, p, h = C.c_float(), C.c_int(), (C.c_uint64 * 3)()
+        _check(self._lib.trident_app_entity_animation_state(self._h, entity, C.byref(t), C.byref(p), C.byref(h)),
+               "entity_animation_state")
+        return (t.value, bool(p.value)) + tuple(None if v == ANIM_NO_HANDLE else v for v in h)
+
+    def set_device_pose(self, enabled):
+        """Renderer::SetDevicePoseEnabled; the animation system then only advances time."""
+        _check(self._lib.trident_app_set_device_pose(self._h, int(enabled)), "set_device_pose")
+
+    def bone_palette_uploads(self):
+        n = C.c_uint64()
+        _check(self._lib.trident_app_bone_palette_uploads(self._h, C.byref(n)), "bone_palette_uploads")
+        return n.value
 
     def add_light(self, type, position=(0, 0, 0), direction=(-0.5, -1.0, -0.3), color=(1.0, 0.98, 0.92),
                   intensity=5.0, range=10.0, enabled=True):
@@ -712,3 +781,117 @@ def load_default_skybox(assets_dir):
     _check(lib.trident_load_default_skybox(os.fsencode(assets_dir), faces.ctypes.data, faces.nbytes, C.byref(n), src, 64),
            "load_default_skybox")
     return faces, src.value.decode()
+
+
+# ---- skeletal animation on the CPU (trident_anim_*): the asset service and the float32 player, no GPU ----
+ANIM_NO_HANDLE = 0xFFFFFFFFFFFFFFFF
+ANIM_NO_CLIP = 0xFFFFFFFF
+
+
+def _names(names, n):
+    if names is None:
+        return None
+    arr = (C.c_char_p * max(n, 1))()
+    for i, s in enumerate(names):
+        arr[i] = None if s is None else s.encode()
+    return arr
+
+
+def anim_decompose(local_bind):
+    """Animation::DecomposeBindTransform: (translation [3], rotation [4] w x y z, scale [3]) as float32."""
+    lib = load_library()
+    m = np.ascontiguousarray(local_bind, np.float32).reshape(16)
+    out = (C.c_float * 10)()
+    _check(lib.trident_anim_decompose(m.ctypes.data, C.byref(out)), "anim_decompose")
+    v = np.array(out[:], np.float32)
+    return v[0:3], v[3:7], v[7:10]
+
+
+def anim_register(asset_id, parents, local_binds, inverse_binds, source_names=None, root_index=-1):
+    """RegisterRuntimeAsset of a skeleton (matrices [n, 16] column-major); returns the handle."""
+    lib = load_library()
+    p = np.ascontiguousarray(parents, np.int32).reshape(-1)
+    lb = np.ascontiguousarray(local_binds, np.float32).reshape(-1, 16)
+    ib = np.ascontiguousarray(inverse_binds, np.float32).reshape(-1, 16)
+    assert lb.shape[0] == p.size == ib.shape[0]
+    h = C.c_uint64()
+    opt = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    _check(lib.trident_anim_register(asset_id.encode(), p.size, opt(p), opt(lb), opt(ib), _names(source_names, p.size),
+                                     root_index, C.byref(h)), "anim_register")
+    return h.value
+
+
+def anim_add_clip(handle, name, duration, channels, vec_times, vec_values, quat_times, quat_values, stored_bones=None,
+                  source_names=None):
+    """Append a clip: channels are abi.POSE_CHANNEL_DTYPE rows over the vector / quaternion key arrays."""
+    lib = load_library()
+    ch = np.ascontiguousarray(channels, abi.POSE_CHANNEL_DTYPE)
+    vt = np.ascontiguousarray(vec_times, np.float32).reshape(-1)
+    vv = np.ascontiguousarray(vec_values, np.float32).reshape(-1, 3)
+    qt = np.ascontiguousarray(quat_times, np.float32).reshape(-1)
+    qv = np.ascontiguousarray(quat_values, np.float32).reshape(-1, 4)
+    sb = None if stored_bones is None else np.ascontiguousarray(stored_bones, np.int32)
+    opt = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    out = C.c_uint32()
+    _check(lib.trident_anim_add_clip(handle, name.encode(), duration, opt(ch), opt(sb), _names(source_names, ch.size),
+                                     ch.size, opt(vt), opt(vv), vt.size, opt(qt), opt(qv), qt.size, C.byref(out)),
+           "anim_add_clip")
+    return out.value
+
+
+def anim_load(path):
+    """AnimationAssetService::AcquireSkeleton of a model file: the handle, or None when it yields no bones or clips."""
+    lib = load_library()
+    h = C.c_uint64()
+    rc = lib.trident_anim_load(os.fsencode(path), C.byref(h))
+    return h.value if rc == abi.TRI_OK else None
+
+
+def anim_describe(handle):
+    """The asset as a dict (trident_anim_describe's JSON)."""
+    import json
+
+    lib = load_library()
+    n = C.c_uint64()
+    _check(lib.trident_anim_describe(handle, None, 0, C.byref(n)), "anim_describe")
+    buf = C.create_string_buffer(n.value)
+    _check(lib.trident_anim_describe(handle, buf, n.value, C.byref(n)), "anim_describe")
+    return json.loads(buf.value.decode())
+
+
+def anim_clip_index(handle, name):
+    """ResolveClipIndex, or None."""
+    lib = load_library()
+    out = C.c_uint32()
+    rc = lib.trident_anim_clip_index(handle, name.encode(), C.byref(out))
+    return out.value if rc == abi.TRI_OK else None
+
+
+def anim_resolve_channels(handle, clip_index):
+    lib = load_library()
+    n = C.c_uint32()
+    _check(lib.trident_anim_resolve_channels(handle, clip_index, None, 0, C.byref(n)), "anim_resolve_channels")
+    out = np.empty(n.value, np.int32)
+    _check(lib.trident_anim_resolve_channels(handle, clip_index, out.ctypes.data if n.value else None, n.value,
+                                             C.byref(n)), "anim_resolve_channels")
+    return out
+
+
+def anim_evaluate(handle, clip_index, time):
+    """The CPU player's pose at `time`: float32 [bones, 16] (clip_index None: the bind pose)."""
+    lib = load_library()
+    clip = ANIM_NO_CLIP if clip_index is None else clip_index
+    n = C.c_uint32()
+    _check(lib.trident_anim_evaluate(handle, clip, time, None, 0, C.byref(n)), "anim_evaluate")
+    out = np.empty((n.value, 16), np.float32)
+    _check(lib.trident_anim_evaluate(handle, clip, time, out.ctypes.data, n.value, C.byref(n)), "anim_evaluate")
+    return out
+
+
+def anim_advance(handle, clip_index, time, dt, speed=1.0, looping=True, playing=True):
+    """AnimationPlayer::Update from the given state: (time, playing) afterwards."""
+    lib = load_library()
+    t, p = C.c_float(), C.c_int()
+    _check(lib.trident_anim_advance(handle, ANIM_NO_CLIP if clip_index is None else clip_index, time, speed,
+                                    int(looping), int(playing), dt, C.byref(t), C.byref(p)), "anim_advance")
+    return t.value, bool(p.value)

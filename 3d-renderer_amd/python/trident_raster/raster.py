@@ -127,6 +127,19 @@ class TriRaster:
         m = np.ascontiguousarray(mats, dtype=np.float32).reshape(-1, 16)
         _check(_lib.tri_upload_bone_palette(self._ctx, _ptr(m), m.shape[0]))
 
+    def pose_palette(self, animset, instances):
+        """tri_pose_palette: instances = rows of (skeleton, clip or abi.TRI_POSE_BIND, time, palette_offset), or a
+        POSE_INSTANCE_DTYPE array; empty drops the posed suffix."""
+        p = _pose_instances(instances)
+        _check(_lib.tri_pose_palette(self._ctx, animset._s if animset is not None else None, _ptr(p) if p.size else None,
+                                     p.size))
+
+    def read_bone_palette(self, count):
+        """tri_read_bone_palette: float32 [count, 16], column-major matrices."""
+        out = np.empty((count, 16), dtype=np.float32)
+        _check(_lib.tri_read_bone_palette(self._ctx, _ptr(out) if count else None, count))
+        return out
+
     def upload_ai_frame(self, rgba):
         """rgba: uint8 [h, w, 4] R8G8B8A8_UNORM AI frame (Default.frag's blend), or None to remove it."""
         if rgba is None:
@@ -270,6 +283,57 @@ class TriFont:
         if self._f:
             _lib.tri_font_destroy(self._f)
             self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _pose_instances(instances):
+    if isinstance(instances, np.ndarray) and instances.dtype == abi.POSE_INSTANCE_DTYPE:
+        return np.ascontiguousarray(instances)
+    p = np.zeros(len(instances), dtype=abi.POSE_INSTANCE_DTYPE)
+    for i, (skeleton, clip, time, offset) in enumerate(instances):
+        p[i] = (skeleton, clip, time, offset)
+    return p
+
+
+class TriAnimSet:
+    """tri_animset: skeletons and clips on one device, posed by tri_pose_palette."""
+
+    def __init__(self, device=-1):
+        lib = load_library()
+        s = C.c_void_p()
+        _check(lib.tri_animset_create(device, C.byref(s)))
+        self._s = s
+
+    def add_skeleton(self, bones, root_index=-1):
+        """bones: POSE_BONE_DTYPE rows (decomposed defaults, rotation w, x, y, z); returns the skeleton index."""
+        b = np.ascontiguousarray(bones, dtype=abi.POSE_BONE_DTYPE)
+        out = C.c_uint32()
+        _check(_lib.tri_animset_add_skeleton(self._s, _ptr(b), b.size, root_index, C.byref(out)))
+        return out.value
+
+    def add_clip(self, skeleton, channels, vec_times, vec_values, quat_times, quat_values, duration):
+        """channels: POSE_CHANNEL_DTYPE rows; vec_values [n, 3]; quat_values [n, 4] (w, x, y, z); returns the clip index."""
+        ch = np.ascontiguousarray(channels, dtype=abi.POSE_CHANNEL_DTYPE)
+        vt = np.ascontiguousarray(vec_times, dtype=np.float32).reshape(-1)
+        vv = np.ascontiguousarray(vec_values, dtype=np.float32).reshape(-1, 3)
+        qt = np.ascontiguousarray(quat_times, dtype=np.float32).reshape(-1)
+        qv = np.ascontiguousarray(quat_values, dtype=np.float32).reshape(-1, 4)
+        assert vt.size == vv.shape[0] and qt.size == qv.shape[0]
+        out = C.c_uint32()
+        opt = lambda a: _ptr(a) if a.size else None  # noqa: E731
+        _check(_lib.tri_animset_add_clip(self._s, skeleton, opt(ch), ch.size, opt(vt), opt(vv), vt.size, opt(qt), opt(qv),
+                                         qt.size, duration, C.byref(out)))
+        return out.value
+
+    def close(self):
+        if self._s:
+            _lib.tri_animset_destroy(self._s)
+            self._s = None
 
     def __enter__(self):
         return self

@@ -249,6 +249,121 @@ int tri_upload_texture(tri_ctx* ctx, uint32_t slot, const uint8_t* rgba8_srgb, u
 /* Bone palette SSBO (binding 4, PrepareBonePaletteBuffer Renderer.cpp:3168-3245):
  * column-major mat4s. */
 int tri_upload_bone_palette(tri_ctx* ctx, const float* matrices, uint32_t matrix_count);
+
+/* ---- skeletal poses evaluated on the device ------------------------------------------------------
+ * The pose rules (Animation::AnimationPlayer::EvaluatePose, AnimationPlayer.cpp:141-341), stated once. The device
+ * kernel (csrc/pose_eval.hip), the shim's CPU player (host/src/Animation.cpp) and the float64 restatement of the tests
+ * (tests/anim_ref.py) each implement exactly this; the two float32 ones use the same IEEE operations in the same
+ * order (no contraction), so they agree bit for bit wherever no library call (sin, acos) is evaluated.
+ *
+ * Quaternions are {w, x, y, z}; matrices are column-major glm::mat4. eps = FLT_EPSILON.
+ *   dot(a, b)       = (a.w*b.w + a.x*b.x) + (a.y*b.y + a.z*b.z)
+ *   normalize(q)    = len = sqrt(dot(q, q)); {1,0,0,0} when len <= 0, else q * (1 / len)
+ *   clamp(x, 0, 1)  = min(max(x, 0), 1) with max(a,b) = a < b ? b : a and min(a,b) = b < a ? b : a
+ *   mix(a, b, T)    = a*(1 - T) + b*T, per component
+ *   slerp(a, b, T)  = c = dot(a, b); when c < 0: b = -b, c = -c; when c > 1 - eps: mix(a, b, T) per component;
+ *                     otherwise A = acos(c) and (sin((1 - T)*A)*a + sin(T*A)*b) / sin(A) per component
+ *   toMat4(q)       = glm::mat4_cast: column 0 = {1 - 2(yy + zz), 2(xy + wz), 2(xz - wy)}, column 1 =
+ *                     {2(xy - wz), 1 - 2(xx + zz), 2(yz + wx)}, column 2 = {2(xz + wy), 2(yz - wx), 1 - 2(xx + yy)}
+ *   A * B           = column j of the product is ((A0*B[j].x + A1*B[j].y) + A2*B[j].z) + A3*B[j].w
+ *
+ * Per-bone defaults: the decomposition of the bone's local bind transform (DecomposeBindTransform, :343-390):
+ * translation = column 3; scale = the lengths of columns 0..2 (length(v) = sqrt((x*x + y*y) + z*z)); rotation =
+ * normalize(quat_cast(columns / scale)), a column left undivided when its length is <= eps. The host computes this
+ * once per skeleton: the library takes the decomposed defaults (tri_pose_bone), never the matrix.
+ *
+ * Channels: a clip's channels apply in order, and each track (translation, rotation, scale) of a channel that has at
+ * least one key replaces the bone's current value, so per (bone, track) the last channel with keys wins;
+ * tri_animset_add_clip resolves that. The caller resolves channel -> bone (ResolveChannelBoneIndex) and leaves out
+ * the channels it cannot map.
+ *
+ * Sampling a track at time t (:287-341): no keys: the default. One key, or t <= time[0]: key 0. Otherwise the first i
+ * with t < time[i+1]: d = time[i+1] - time[i], T = clamp(d > eps ? (t - time[i]) / d : 0, 0, 1), and the value is
+ * mix(key[i], key[i+1], T) for vectors, normalize(slerp(key[i], key[i+1], T)) for quaternions. Otherwise the last
+ * key. A quaternion taken from a single key or an end point is normalize(key). Key times are non-decreasing (for
+ * those the reference's linear scan is an upper-bound search, which is what the kernel does); a track with
+ * decreasing or non-finite times is refused.
+ *
+ * Local matrix: translate * toMat4(normalize(q)) * scale, evaluated as: column j (j < 3) = column j of
+ * toMat4(normalize(q)) times scale[j] with w = 0, column 3 = {translation, 1}. For finite inputs glm's two products
+ * give the same floats (every other term is an exact zero); only the sign of a zero entry can differ.
+ *
+ * Hierarchy (:209-277): the traversal starts at the root index when it is a bone, otherwise at every bone without
+ * a parent, otherwise at bone 0; a start bone's global is identity * local (through the product above); a child's is
+ * parent_global * local. A bone the traversal does not reach takes global = local (the reference leaves it at its
+ * previous evaluation's value, which is local only on the first one: here it is always the fresh local). A reached
+ * bone whose global equals the identity in all 16 entries takes local too (:270-273).
+ * The traversal follows the parents (a bone's children are the bones that name it as their parent; the shim rebuilds
+ * Bone::m_Children from the parents when an asset is registered, where the reference walks the child lists as given).
+ * pose = global * inverse_bind. A parent graph with a cycle reachable from the start set, which the reference would
+ * walk for ever, is refused when the skeleton is added.
+ *
+ * Time advance (AnimationPlayer::Update, :57-102) is the caller's: an instance carries the final sample time. */
+#define TRI_POSE_MAX_BONES 256      /* bones of one skeleton (ancestors beyond the palette slice still count)      */
+#define TRI_POSE_PALETTE_BONES 128  /* an instance writes its first min(bones, 128) matrices                      *
+                                     * (PrepareBonePaletteBuffer's clamp, Renderer.cpp:3168-3245)                 */
+#define TRI_POSE_BIND 0xFFFFFFFFu   /* tri_pose_instance.clip: no clip, every bone at its defaults                */
+#define TRI_POSE_MAX_INSTANCES 65536u
+#define TRI_POSE_MAX_PALETTE (1u << 24) /* matrices a palette may hold                                            */
+
+/* One bone: its parent (negative: none), the decomposed defaults and the inverse bind matrix. */
+typedef struct tri_pose_bone {
+    int32_t parent;
+    uint32_t reserved[3];
+    float translation[4]; /* xyz; w ignored */
+    float rotation[4];    /* w, x, y, z     */
+    float scale[4];       /* xyz; w ignored */
+    float inverse_bind[16];
+} tri_pose_bone;
+
+/* One TransformChannel with its bone resolved: key ranges {first, count} into the clip's vector keys (translation,
+ * scale) and quaternion keys (rotation). */
+typedef struct tri_pose_channel {
+    uint32_t bone;
+    uint32_t translation_first, translation_count;
+    uint32_t rotation_first, rotation_count;
+    uint32_t scale_first, scale_count;
+    uint32_t reserved;
+} tri_pose_channel;
+
+typedef struct tri_pose_instance {
+    uint32_t skeleton;       /* from tri_animset_add_skeleton                                  */
+    uint32_t clip;           /* from tri_animset_add_clip for that skeleton, or TRI_POSE_BIND  */
+    float time;              /* sample time in seconds                                         */
+    uint32_t palette_offset; /* first matrix of the instance's slice in the context's palette  */
+} tri_pose_instance;
+
+/* A device-resident, append-only store of skeletons and clips on one device (-1: the current one). Adding validates
+ * on the host, derives the traversal's level order and completes its upload before it returns; a destroy only after
+ * every context that posed from the set is synchronised. Without a HIP device tri_animset_create is TRI_E_HIP. */
+typedef struct tri_animset tri_animset;
+int tri_animset_create(int32_t device, tri_animset** out);
+int tri_animset_destroy(tri_animset* set);
+/* TRI_E_INVALID: bone_count outside 1..TRI_POSE_MAX_BONES, a parent >= bone_count, a cycle reachable from the
+ * traversal's start set. root_index outside 0..bone_count-1 means "no root". */
+int tri_animset_add_skeleton(tri_animset* set, const tri_pose_bone* bones, uint32_t bone_count, int32_t root_index,
+                             uint32_t* out_skeleton);
+/* vector keys: vec_times[i], vec_values[3*i..]; quaternion keys: quat_times[i], quat_values[4*i..] = w, x, y, z.
+ * TRI_E_INVALID: an unknown skeleton, a channel bone >= its bone count, a key range outside the arrays, key times
+ * of a range not finite or decreasing, a duration that is not finite. */
+int tri_animset_add_clip(tri_animset* set, uint32_t skeleton, const tri_pose_channel* channels, uint32_t channel_count,
+                         const float* vec_times, const float* vec_values, uint32_t vec_count,
+                         const float* quat_times, const float* quat_values, uint32_t quat_count, float duration,
+                         uint32_t* out_clip);
+
+/* Evaluate `count` instances on the context's stream (k_pose), each writing its min(bones, TRI_POSE_PALETTE_BONES)
+ * matrices at palette_offset of the context's bone palette. The palette is then the uploaded prefix (what the last
+ * tri_upload_bone_palette put there; that call drops any posed suffix) followed by the posed suffix, which every
+ * tri_pose_palette replaces; count 0 drops it. Matrices of the suffix that no instance covers are unspecified.
+ * Stream-ordered like tri_render: no host synchronisation while the palette's capacity suffices (the records travel
+ * through a pinned ring and may be overwritten when the call returns); growing the palette synchronises and keeps
+ * the prefix. TRI_E_INVALID, before anything is enqueued: an instance below the prefix or beyond
+ * TRI_POSE_MAX_PALETTE, two instances that overlap, an unknown skeleton or clip, a clip of another skeleton, a set
+ * on another device, count above TRI_POSE_MAX_INSTANCES. */
+int tri_pose_palette(tri_ctx* ctx, tri_animset* set, const tri_pose_instance* instances, uint32_t count);
+/* Blocking read of the palette's first matrix_count matrices (at most its current extent), for tests and tools. */
+int tri_read_bone_palette(tri_ctx* ctx, float* out_matrices, uint32_t matrix_count);
+
 /* Skybox cubemap (CreateSkyboxCubemap, Renderer.cpp:3818-4110; LoadFromFaces TextureLoader.cpp:
  * 334-830): 6 faces in Vulkan layer order +X,-X,+Y,-Y,+Z,-Z, each size x size RGBA8 sRGB texels, rows
  * top to bottom, one mip. The skybox pass (Skybox.cpp:13-79, Skybox.vert/.frag, cull FRONT, depth
@@ -615,6 +730,12 @@ int tri_group_set_draws(tri_group* group, const tri_draw* draws, uint32_t draw_c
  * device; TRI_E_INVALID — no band changed — if a band's device has none). fonts == NULL or count == 0 removes the
  * overlay. */
 int tri_group_set_text(tri_group* group, tri_font* const* fonts, const tri_text_quad* quads, uint32_t count);
+/* tri_pose_palette on every band with the same instances. sets: one tri_animset per distinct device of the group, in
+ * any order, each holding the same skeletons and clips under the same indices (TRI_E_INVALID — nothing enqueued — if
+ * a band's device has none, or any band refuses the instances; a HIP failure on a later band leaves the earlier ones
+ * posed). count == 0 drops every band's posed suffix. */
+int tri_group_pose_palette(tri_group* group, tri_animset* const* sets, const tri_pose_instance* instances,
+                           uint32_t count);
 /* Enqueue every band, then the assembly onto the display device (asynchronous). */
 int tri_group_render(tri_group* group);
 /* Wait for every band and the assembly; TRI_E_OVERFLOW as tri_synchronize (re-render the frame). */
@@ -664,6 +785,9 @@ static_assert(sizeof(tri_shadow_config) == 80, "tri_shadow_config layout");
 static_assert(sizeof(tri_group_config) == 32, "tri_group_config layout");
 static_assert(sizeof(tri_image) == 32, "tri_image layout");
 static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
+static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
+static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
+static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
 #endif
 
 #endif /* TRI_RASTER_H */
