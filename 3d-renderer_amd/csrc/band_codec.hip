@@ -11,6 +11,7 @@
 //                   the transfer stayed lossless; tri_alpha_uniform makes it unreachable)
 //   k_unpack_bgr24  4 pixels per lane: one 12-B load, one 16-B store
 // Both are HBM-streaming kernels: 7 B moved per pixel (4 read + 3 written, or the reverse).
+#include "capi_util.h"
 #include "raster_launch.h"
 
 #include <hip/hip_runtime.h>
@@ -426,10 +427,10 @@ int tri_dbp_pack(const void* bgra, uint64_t pixels, uint32_t alpha, void* stream
         return tri_internal_fail(TRI_E_INVALID, "tri_dbp_pack: bad argument");
     if (((uintptr_t)bgra & 3u) || ((uintptr_t)stream_out & 15u))
         return tri_internal_fail(TRI_E_INVALID, "tri_dbp_pack: misaligned buffer");
-    const hipError_t e = tri_launch_dbp_pack(static_cast<const uint32_t*>(bgra), pixels, alpha,
-                                             static_cast<uint8_t*>(stream_out), slot_bytes, flags,
-                                             static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TRI_OK : tri_internal_fail(TRI_E_HIP, hipGetErrorString(e));
+    TRI_HIP_TRY(tri_launch_dbp_pack(static_cast<const uint32_t*>(bgra), pixels, alpha,
+                                    static_cast<uint8_t*>(stream_out), slot_bytes, flags,
+                                    static_cast<hipStream_t>(stream)));
+    return TRI_OK;
 }
 
 int tri_dbp_unpack(const void* stream_in, uint64_t pixels, uint32_t alpha, uint32_t slot_bytes, void* bgra, void* stream) {
@@ -437,9 +438,9 @@ int tri_dbp_unpack(const void* stream_in, uint64_t pixels, uint32_t alpha, uint3
         return tri_internal_fail(TRI_E_INVALID, "tri_dbp_unpack: bad argument");
     if (((uintptr_t)bgra & 3u) || ((uintptr_t)stream_in & 15u))
         return tri_internal_fail(TRI_E_INVALID, "tri_dbp_unpack: misaligned buffer");
-    const hipError_t e = tri_launch_dbp_unpack(static_cast<const uint8_t*>(stream_in), pixels, alpha, slot_bytes,
-                                               static_cast<uint32_t*>(bgra), static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TRI_OK : tri_internal_fail(TRI_E_HIP, hipGetErrorString(e));
+    TRI_HIP_TRY(tri_launch_dbp_unpack(static_cast<const uint8_t*>(stream_in), pixels, alpha, slot_bytes,
+                                      static_cast<uint32_t*>(bgra), static_cast<hipStream_t>(stream)));
+    return TRI_OK;
 }
 
 uint64_t tri_dbp_bytes(uint64_t pixels, uint32_t slot_bytes) { return tri_dbp_stream_bytes(pixels, slot_bytes); }
@@ -459,25 +460,24 @@ int tri_dbp_unpack_bands(const void* const* streams, void* const* bgra, const ui
         src[k] = static_cast<const uint8_t*>(streams[k]);
         dst[k] = static_cast<uint32_t*>(bgra[k]);
     }
-    const hipError_t e = tri_launch_dbp_unpack_bands(src, dst, pixels, count, alpha, slot_bytes,
-                                                     static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TRI_OK : tri_internal_fail(TRI_E_HIP, hipGetErrorString(e));
+    TRI_HIP_TRY(tri_launch_dbp_unpack_bands(src, dst, pixels, count, alpha, slot_bytes, static_cast<hipStream_t>(stream)));
+    return TRI_OK;
 }
 
 int tri_pack_bgr24(const void* bgra, void* bgr, uint64_t pixels, uint32_t alpha, uint32_t* flag, void* stream) {
     if ((pixels && (!bgra || !bgr)) || alpha > 255u) return tri_internal_fail(TRI_E_INVALID, "tri_pack_bgr24: bad argument");
     if ((uintptr_t)bgra & 3u) return tri_internal_fail(TRI_E_INVALID, "tri_pack_bgr24: source must be 4-B aligned");
-    const hipError_t e = tri_launch_pack_bgr24(static_cast<const uint32_t*>(bgra), static_cast<uint8_t*>(bgr), pixels,
-                                               alpha, flag, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TRI_OK : tri_internal_fail(TRI_E_HIP, hipGetErrorString(e));
+    TRI_HIP_TRY(tri_launch_pack_bgr24(static_cast<const uint32_t*>(bgra), static_cast<uint8_t*>(bgr), pixels,
+                                      alpha, flag, static_cast<hipStream_t>(stream)));
+    return TRI_OK;
 }
 
 int tri_unpack_bgr24(const void* bgr, void* bgra, uint64_t pixels, uint32_t alpha, void* stream) {
     if ((pixels && (!bgra || !bgr)) || alpha > 255u) return tri_internal_fail(TRI_E_INVALID, "tri_unpack_bgr24: bad argument");
     if ((uintptr_t)bgra & 3u) return tri_internal_fail(TRI_E_INVALID, "tri_unpack_bgr24: destination must be 4-B aligned");
-    const hipError_t e = tri_launch_unpack_bgr24(static_cast<const uint8_t*>(bgr), static_cast<uint32_t*>(bgra), pixels,
-                                                 alpha, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? TRI_OK : tri_internal_fail(TRI_E_HIP, hipGetErrorString(e));
+    TRI_HIP_TRY(tri_launch_unpack_bgr24(static_cast<const uint8_t*>(bgr), static_cast<uint32_t*>(bgra), pixels,
+                                        alpha, static_cast<hipStream_t>(stream)));
+    return TRI_OK;
 }
 
 }  // extern "C"

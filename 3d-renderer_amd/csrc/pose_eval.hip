@@ -11,6 +11,7 @@
 // Every input was validated on the host when it was added (tri_animset_add_*) or posed (tri_pose_check): the kernel has
 // no bounds branch for bad input. Built under the default HIPFLAGS: -ffp-contract=off, IEEE division and square root,
 // sinf / acosf as the device library gives them.
+#include "capi_util.h"
 #include "raster_launch.h"
 
 #include <hip/hip_runtime.h>
@@ -18,7 +19,6 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -292,21 +292,16 @@ namespace {
 // Bring the device images up to the host vectors. Kernels of earlier tri_pose_palette calls may still read an image
 // that has to move: the device is drained first, and the copies complete before the call returns.
 int animset_upload(tri_animset* s, const char* who) {
-    auto bad = [&](hipError_t e) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "%s: %s", who, hipGetErrorString(e));
-        return tri_internal_fail(e == hipErrorOutOfMemory ? TRI_E_OOM : TRI_E_HIP, msg);
-    };
     hipError_t e = hipSetDevice(s->device);
-    if (e != hipSuccess) return bad(e);
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return bad(e);
+    if (e != hipSuccess) return tri_hip_fail(e, who);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return tri_hip_fail(e, who);
 #define POSE_SYNC(arr, vec) \
-    if ((e = s->arr.sync(s->vec.data(), s->vec.size() * sizeof(s->vec[0]))) != hipSuccess) return bad(e)
+    if ((e = s->arr.sync(s->vec.data(), s->vec.size() * sizeof(s->vec[0]))) != hipSuccess) return tri_hip_fail(e, who)
     POSE_SYNC(d_skels, skels); POSE_SYNC(d_clips, clips); POSE_SYNC(d_bones, bones); POSE_SYNC(d_tracks, tracks);
     POSE_SYNC(d_vtimes, vtimes); POSE_SYNC(d_qtimes, qtimes); POSE_SYNC(d_vvals, vvals); POSE_SYNC(d_qvals, qvals);
     POSE_SYNC(d_order, order); POSE_SYNC(d_levels, levels);
 #undef POSE_SYNC
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return bad(e);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return tri_hip_fail(e, who);
     return TRI_OK;
 }
 
@@ -368,12 +363,8 @@ extern "C" {
 int tri_animset_create(int32_t device, tri_animset** out) {
     if (!out) return tri_internal_fail(TRI_E_INVALID, "tri_animset_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return tri_internal_fail(TRI_E_HIP, "tri_animset_create: no HIP device available");
-    int dev = device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return tri_internal_fail(TRI_E_HIP, "tri_animset_create: hipGetDevice failed");
-    if (dev >= ndev) return tri_internal_fail(TRI_E_INVALID, "tri_animset_create: no such device");
+    int dev = 0;
+    if (const int rc = tri_resolve_device(device, "tri_animset_create", &dev)) return rc;
     tri_animset* s = new tri_animset();
     s->device = dev;
     *out = s;

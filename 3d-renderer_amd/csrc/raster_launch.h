@@ -210,15 +210,3 @@ hipError_t tri_launch_pose(const tri_animset* set, const tri_pose_instance* d_in
                            uint32_t lds_bones, float* palette, hipStream_t stream);
 // The matrices of a context's uploaded palette prefix.
 uint32_t tri_internal_pose_prefix(tri_ctx* ctx);
-
-// Internal accessors for the group layer (tri_group.hip): a context's stream and device.
-hipStream_t tri_internal_stream(tri_ctx* ctx);
-int tri_internal_device(tri_ctx* ctx);
-// Whether the context renders every row of its frame (false: a row band).
-bool tri_internal_whole_frame(tri_ctx* ctx);
-// Record an error message for tri_last_error (returns `code`).
-int tri_internal_fail(int code, const char* msg);
-// The device a geometry object lives on; the UNORM8 decode table (b / 255) on a context's device.
-int tri_internal_geometry_device(const tri_geometry* geometry);
-int tri_internal_font_device(const tri_font* font);
-const float* tri_internal_unorm_lut(tri_ctx* ctx);

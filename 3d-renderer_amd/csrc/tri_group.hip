@@ -20,6 +20,7 @@
 // Streams: each band renders on its context's stream; per distinct device the group owns an assembly
 // stream that waits (events) for that device's bands and carries the device's RCCL calls, so every
 // communicator sees one stream.
+#include "capi_util.h"
 #include "raster_launch.h"
 
 #include <hip/hip_runtime.h>
@@ -70,21 +71,11 @@ bool travels(const tri_group* g, uint32_t r) {
     return r != g->display && (g->dev[r] != g->dev[g->display] || (g->gflags & TRI_GROUP_STAGE_BANDS));
 }
 
-int hip_fail(hipError_t e, const char* what) {
-    const std::string m = std::string(what) + ": " + hipGetErrorString(e);
-    return tri_internal_fail(e == hipErrorOutOfMemory ? TRI_E_OOM : TRI_E_HIP, m.c_str());
-}
-
 int nccl_fail(ncclResult_t r, const char* what) {
     const std::string m = std::string(what) + ": " + ncclGetErrorString(r);
     return tri_internal_fail(TRI_E_HIP, m.c_str());
 }
 
-#define GH(expr)                                            \
-    do {                                                    \
-        const hipError_t _e = (expr);                       \
-        if (_e != hipSuccess) return hip_fail(_e, #expr);   \
-    } while (0)
 #define GN(expr)                                            \
     do {                                                    \
         const ncclResult_t _r = (expr);                     \
@@ -387,38 +378,38 @@ int tri_group_render(tri_group* g) {
     const uint32_t slot = g->slot;  // this frame's dbp slot size (both ends of every band use it)
     auto pixels = [&](uint32_t r) { return (uint64_t)(g->y1[r] - g->y0[r]) * g->W; };
     for (uint32_t r = 0; r < g->n; ++r) {
-        GH(hipSetDevice(g->dev[r]));
+        TRI_HIP_TRY(hipSetDevice(g->dev[r]));
         hipStream_t s = tri_internal_stream(g->ctx[r]);
         uint32_t* out_ptr;
         if (!travels(g, r)) {
             out_ptr = g->frame[p] + (size_t)g->y0[r] * g->W;  // in place
             // the consumer of frame k - 2 (same buffer) has released it, and the group's blit has read it
-            if (g->present_armed[p]) GH(hipStreamWaitEvent(s, g->present_done[p], 0));
-            if (g->blit_armed[p]) GH(hipStreamWaitEvent(s, g->blit_done[p], 0));
+            if (g->present_armed[p]) TRI_HIP_TRY(hipStreamWaitEvent(s, g->present_done[p], 0));
+            if (g->blit_armed[p]) TRI_HIP_TRY(hipStreamWaitEvent(s, g->blit_done[p], 0));
         } else {
             out_ptr = g->band_buf[p][r];
             // frame k - 2's assembly read this buffer (and its packed copy)
-            if (g->asm_recorded[p]) GH(hipStreamWaitEvent(s, g->asm_done[p][g->urank[r]], 0));
+            if (g->asm_recorded[p]) TRI_HIP_TRY(hipStreamWaitEvent(s, g->asm_done[p][g->urank[r]], 0));
         }
         int rc = tri_bind_output(g->ctx[r], out_ptr, nullptr);  // depth stays in the band context
         if (rc) return rc;
         if ((rc = tri_render(g->ctx[r]))) return rc;
         if (pack && travels(g, r)) {  // behind the band's raster on its stream
             if (dbp)
-                GH(tri_launch_dbp_pack(g->band_buf[p][r], pixels(r), (uint32_t)alpha, g->band_pack[p][r], slot, g->flag[r], s));
+                TRI_HIP_TRY(tri_launch_dbp_pack(g->band_buf[p][r], pixels(r), (uint32_t)alpha, g->band_pack[p][r], slot, g->flag[r], s));
             else
-                GH(tri_launch_pack_bgr24(g->band_buf[p][r], g->band_pack[p][r], pixels(r), (uint32_t)alpha, g->flag[r], s));
+                TRI_HIP_TRY(tri_launch_pack_bgr24(g->band_buf[p][r], g->band_pack[p][r], pixels(r), (uint32_t)alpha, g->flag[r], s));
         }
-        GH(hipEventRecord(g->band_done[r], s));
+        TRI_HIP_TRY(hipEventRecord(g->band_done[r], s));
     }
     const int disp = g->urank[g->display];
     for (size_t u = 0; u < g->udev.size(); ++u) {  // each device's assembly stream waits for its bands
-        GH(hipSetDevice(g->udev[u]));
+        TRI_HIP_TRY(hipSetDevice(g->udev[u]));
         for (uint32_t r = 0; r < g->n; ++r)
-            if (g->urank[r] == (int)u) GH(hipStreamWaitEvent(g->astream[u], g->band_done[r], 0));
+            if (g->urank[r] == (int)u) TRI_HIP_TRY(hipStreamWaitEvent(g->astream[u], g->band_done[r], 0));
         // the receives into frame[p] wait for the consumer's fence on frame k - 2 as well (the blit of frame
         // k - 2 ran on this same stream, so it is ordered already)
-        if ((int)u == disp && g->present_armed[p]) GH(hipStreamWaitEvent(g->astream[u], g->present_done[p], 0));
+        if ((int)u == disp && g->present_armed[p]) TRI_HIP_TRY(hipStreamWaitEvent(g->astream[u], g->present_done[p], 0));
     }
     // where band r's bytes land on the display device: straight into the frame, or its receive buffer
     auto landing = [&](uint32_t r) -> void* {
@@ -439,10 +430,10 @@ int tri_group_render(tri_group* g) {
         }
         GN(ncclGroupEnd());
     }
-    GH(hipSetDevice(ddev));
+    TRI_HIP_TRY(hipSetDevice(ddev));
     for (uint32_t r = 0; r < g->n; ++r)  // staged bands on the display device itself: a device-local copy
         if (travels(g, r) && g->dev[r] == ddev)
-            GH(hipMemcpyAsync(landing(r), source(r), bytes(r), hipMemcpyDeviceToDevice, g->astream[disp]));
+            TRI_HIP_TRY(hipMemcpyAsync(landing(r), source(r), bytes(r), hipMemcpyDeviceToDevice, g->astream[disp]));
     if (pack) {  // restore the 4-byte pixels with the proven alpha, behind the receives
         std::vector<const uint8_t*> from;
         std::vector<uint32_t*> to;
@@ -452,16 +443,16 @@ int tri_group_render(tri_group* g) {
                 from.push_back(g->rx[p][r]);
                 to.push_back(g->frame[p] + (size_t)g->y0[r] * g->W);
                 npx.push_back(pixels(r));
-                if (!dbp) GH(tri_launch_unpack_bgr24(from.back(), to.back(), npx.back(), (uint32_t)alpha, g->astream[disp]));
+                if (!dbp) TRI_HIP_TRY(tri_launch_unpack_bgr24(from.back(), to.back(), npx.back(), (uint32_t)alpha, g->astream[disp]));
             }
         for (size_t k = 0; dbp && k < from.size(); k += TRI_DBP_MAX_BANDS)  // every remote band in one launch
-            GH(tri_launch_dbp_unpack_bands(from.data() + k, to.data() + k, npx.data() + k,
+            TRI_HIP_TRY(tri_launch_dbp_unpack_bands(from.data() + k, to.data() + k, npx.data() + k,
                                            (uint32_t)std::min<size_t>(TRI_DBP_MAX_BANDS, from.size() - k),
                                            (uint32_t)alpha, slot, g->astream[disp]));
     }
     for (size_t u = 0; u < g->udev.size(); ++u) {
-        GH(hipSetDevice(g->udev[u]));
-        GH(hipEventRecord(g->asm_done[p][u], g->astream[u]));
+        TRI_HIP_TRY(hipSetDevice(g->udev[u]));
+        TRI_HIP_TRY(hipEventRecord(g->asm_done[p][u], g->astream[u]));
     }
     g->asm_recorded[p] = true;
     g->present_armed[p] = false;  // waited for; the consumer re-arms it for this frame
@@ -479,10 +470,10 @@ int tri_group_present(tri_group* g, void* hip_stream) {
     if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_present: null group");
     if (!g->frames) return tri_internal_fail(TRI_E_STATE, "tri_group_present: no frame rendered");
     const uint32_t p = last_parity(g);
-    GH(hipSetDevice(g->dev[g->display]));
+    TRI_HIP_TRY(hipSetDevice(g->dev[g->display]));
     // host release: stamp it behind the frame's own assembly, so the fence can never precede the frame
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : g->astream[g->urank[g->display]];
-    GH(hipEventRecord(g->present_done[p], s));
+    TRI_HIP_TRY(hipEventRecord(g->present_done[p], s));
     g->present_armed[p] = true;
     return TRI_OK;
 }
@@ -495,8 +486,8 @@ int tri_group_synchronize(tri_group* g) {
         if (rc && status == TRI_OK) status = rc;
     }
     for (size_t u = 0; u < g->udev.size(); ++u) {
-        GH(hipSetDevice(g->udev[u]));
-        GH(hipStreamSynchronize(g->astream[u]));
+        TRI_HIP_TRY(hipSetDevice(g->udev[u]));
+        TRI_HIP_TRY(hipStreamSynchronize(g->astream[u]));
     }
     // every packed band kept the proven alpha and fitted its dbp slots; the dbp slot is refitted to the largest
     // slot the frames since the previous synchronize needed (+ 1/16)
@@ -505,12 +496,12 @@ int tri_group_synchronize(tri_group* g) {
     for (uint32_t r = 0; r < g->n; ++r) {
         if (!g->flag[r]) continue;
         uint32_t f[2] = {0, 0};
-        GH(hipSetDevice(g->dev[r]));
-        GH(hipMemcpy(f, g->flag[r], 8, hipMemcpyDeviceToHost));
+        TRI_HIP_TRY(hipSetDevice(g->dev[r]));
+        TRI_HIP_TRY(hipMemcpy(f, g->flag[r], 8, hipMemcpyDeviceToHost));
         if (f[0] || f[1])
             // reported once: cleared on the band's stream (idle here), so a later lossless frame synchronises clean.
             // Frames handed out (tri_group_frame / get_output / blit) without a synchronize are not checked.
-            GH(hipMemsetAsync(g->flag[r], 0, 8, tri_internal_stream(g->ctx[r])));
+            TRI_HIP_TRY(hipMemsetAsync(g->flag[r], 0, 8, tri_internal_stream(g->ctx[r])));
         alpha_bad |= (f[0] & 1u) != 0;
         overflow |= (f[0] & 2u) != 0;
         need = std::max(need, f[1]);
@@ -559,8 +550,8 @@ int tri_group_readback(tri_group* g, uint8_t* bgra, uint32_t* depth) {
     int rc = tri_group_synchronize(g);
     if (rc) return rc;
     if (bgra) {
-        GH(hipSetDevice(g->dev[g->display]));
-        GH(hipMemcpy(bgra, g->frame[last_parity(g)], (size_t)g->W * g->H * 4, hipMemcpyDeviceToHost));
+        TRI_HIP_TRY(hipSetDevice(g->dev[g->display]));
+        TRI_HIP_TRY(hipMemcpy(bgra, g->frame[last_parity(g)], (size_t)g->W * g->H * 4, hipMemcpyDeviceToHost));
     }
     if (depth)
         for (uint32_t r = 0; r < g->n; ++r)
@@ -589,21 +580,20 @@ int tri_group_get_output(tri_group* g, tri_image* out) {
 
 int tri_group_blit_linear(tri_group* g, void* dst, uint32_t width, uint32_t height) {
     if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_blit_linear: null group");
-    if (width == 0 || height == 0 || width > TRI_MAX_DIM || height > TRI_MAX_DIM)
-        return tri_internal_fail(TRI_E_INVALID, "tri_group_blit_linear: destination size out of range");
+    if (const int rc = tri_check_extent("tri_group_blit_linear", width, height, "destination")) return rc;
     if (!g->frames) return tri_internal_fail(TRI_E_STATE, "tri_group_blit_linear: no frame rendered");
     const int32_t ddev = g->dev[g->display];
-    GH(hipSetDevice(ddev));
+    TRI_HIP_TRY(hipSetDevice(ddev));
     hipStream_t s = g->astream[g->urank[g->display]];  // behind the frame's assembly
     uint32_t* out = static_cast<uint32_t*>(dst);
     if (!out) {
         const size_t need = (size_t)width * height;
         if (need > g->cap_present) {
-            GH(hipStreamSynchronize(s));
-            if (g->present) GH(hipFree(g->present));
+            TRI_HIP_TRY(hipStreamSynchronize(s));
+            if (g->present) TRI_HIP_TRY(hipFree(g->present));
             g->present = nullptr;
             g->cap_present = 0;
-            GH(hipMalloc(&g->present, need * 4));
+            TRI_HIP_TRY(hipMalloc(&g->present, need * 4));
             g->cap_present = need;
         }
         out = g->present;
@@ -613,10 +603,10 @@ int tri_group_blit_linear(tri_group* g, void* dst, uint32_t width, uint32_t heig
         g->present_w = g->present_h = 0;  // the owned target no longer holds the latest blit: read_present fails
     }
     const uint32_t p = last_parity(g);
-    GH(tri_launch_blit(g->frame[p], (int32_t)g->W, (int32_t)g->H, out, (int32_t)width, (int32_t)height,
+    TRI_HIP_TRY(tri_launch_blit(g->frame[p], (int32_t)g->W, (int32_t)g->H, out, (int32_t)width, (int32_t)height,
                        tri_internal_unorm_lut(g->ctx[g->display]), s));
     // the blit reads frame[p] on the assembly stream: frame k + 2's in-place bands (context streams) wait for it
-    GH(hipEventRecord(g->blit_done[p], s));
+    TRI_HIP_TRY(hipEventRecord(g->blit_done[p], s));
     g->blit_armed[p] = true;
     return TRI_OK;
 }
@@ -624,9 +614,9 @@ int tri_group_blit_linear(tri_group* g, void* dst, uint32_t width, uint32_t heig
 int tri_group_read_present(tri_group* g, uint8_t* bgra) {
     if (!g || !bgra) return tri_internal_fail(TRI_E_INVALID, "tri_group_read_present: null argument");
     if (!g->present || !g->present_w) return tri_internal_fail(TRI_E_STATE, "tri_group_read_present: nothing was blitted");
-    GH(hipSetDevice(g->dev[g->display]));
-    GH(hipStreamSynchronize(g->astream[g->urank[g->display]]));
-    GH(hipMemcpy(bgra, g->present, (size_t)g->present_w * g->present_h * 4, hipMemcpyDeviceToHost));
+    TRI_HIP_TRY(hipSetDevice(g->dev[g->display]));
+    TRI_HIP_TRY(hipStreamSynchronize(g->astream[g->urank[g->display]]));
+    TRI_HIP_TRY(hipMemcpy(bgra, g->present, (size_t)g->present_w * g->present_h * 4, hipMemcpyDeviceToHost));
     return TRI_OK;
 }
 

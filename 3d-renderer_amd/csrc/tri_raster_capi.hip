@@ -2,6 +2,7 @@
 // Owns device memory, the stream and timing events; mirrors Trident::Renderer's upload / frame
 // semantics (Renderer.cpp:1784-2116 geometry, :3404-3656 texture slots, :5822-6051 uniforms,
 // :5110-5151 draws, :5297-5338 readback).
+#include "capi_util.h"
 #include "raster_launch.h"
 
 #include <hip/hip_runtime.h>
@@ -31,21 +32,13 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess)                                                                \
-            return fail(_e == hipErrorOutOfMemory ? TRI_E_OOM : TRI_E_HIP, "%s: %s (%s:%d)", \
-                        #expr, hipGetErrorString(_e), __FILE__, __LINE__);                   \
-    } while (0)
-
 template <typename T>
 int grow(T*& p, size_t& cap, size_t need) {
     if (need <= cap && p) return TRI_OK;
-    if (p) HIP_TRY(hipFree(p));
+    if (p) TRI_HIP_TRY(hipFree(p));
     p = nullptr;
     cap = std::max<size_t>(need, 1);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), cap * sizeof(T)));
+    TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), cap * sizeof(T)));
     return TRI_OK;
 }
 
@@ -246,7 +239,7 @@ struct tri_ctx {
 namespace {
 
 int make_current(tri_ctx* c) {
-    HIP_TRY(hipSetDevice(c->device));
+    TRI_HIP_TRY(hipSetDevice(c->device));
     return TRI_OK;
 }
 
@@ -532,12 +525,12 @@ int resolve_draws(tri_ctx* c) {
     const size_t o_pb = o_vb + (n + 1) * 4;
     const size_t o_cb = o_pb + (n + 1) * 4;
     const size_t bytes = o_cb + (n + 1) * 4;
-    if (c->stage_free) HIP_TRY(hipEventSynchronize(c->stage_free));
+    if (c->stage_free) TRI_HIP_TRY(hipEventSynchronize(c->stage_free));
     if (bytes > c->cap_stage) {
-        if (c->h_stage) HIP_TRY(hipHostFree(c->h_stage));
+        if (c->h_stage) TRI_HIP_TRY(hipHostFree(c->h_stage));
         c->h_stage = nullptr;
         c->cap_stage = bytes * 2;
-        HIP_TRY(hipHostMalloc(&c->h_stage, c->cap_stage, hipHostMallocDefault));
+        TRI_HIP_TRY(hipHostMalloc(&c->h_stage, c->cap_stage, hipHostMallocDefault));
     }
     char* st = static_cast<char*>(c->h_stage);
     std::memcpy(st, dd.data(), n * sizeof(TriDrawDev));
@@ -546,15 +539,15 @@ int resolve_draws(tri_ctx* c) {
     std::memcpy(st + o_pb, pb.data(), (n + 1) * 4);
     std::memcpy(st + o_cb, cbase.data(), (n + 1) * 4);
     if (n) {
-        HIP_TRY(hipMemcpyAsync(c->d_draws, st, n * sizeof(TriDrawDev), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(c->d_draw_shade, st + o_shade, n * sizeof(TriDrawShade), hipMemcpyHostToDevice,
+        TRI_HIP_TRY(hipMemcpyAsync(c->d_draws, st, n * sizeof(TriDrawDev), hipMemcpyHostToDevice, c->stream));
+        TRI_HIP_TRY(hipMemcpyAsync(c->d_draw_shade, st + o_shade, n * sizeof(TriDrawShade), hipMemcpyHostToDevice,
                                c->stream));
     }
-    HIP_TRY(hipMemcpyAsync(c->d_vbase, st + o_vb, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_pbase, st + o_pb, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_cbase, st + o_cb, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (!c->stage_free) HIP_TRY(hipEventCreateWithFlags(&c->stage_free, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->stage_free, c->stream));
+    TRI_HIP_TRY(hipMemcpyAsync(c->d_vbase, st + o_vb, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    TRI_HIP_TRY(hipMemcpyAsync(c->d_pbase, st + o_pb, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    TRI_HIP_TRY(hipMemcpyAsync(c->d_cbase, st + o_cb, (n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (!c->stage_free) TRI_HIP_TRY(hipEventCreateWithFlags(&c->stage_free, hipEventDisableTiming));
+    TRI_HIP_TRY(hipEventRecord(c->stage_free, c->stream));
     c->ndraws = n;
     if (n == 1) {
         c->draw0 = dd[0];
@@ -610,17 +603,17 @@ int upload_text(tri_ctx* c) {
         if (bytes > c->cap_text) {  // (hipFree waits for the device: no frame still reads the old image)
             if ((rc = grow(c->d_text, c->cap_text, bytes * 2))) return rc;
         }
-        if (c->text_free) HIP_TRY(hipEventSynchronize(c->text_free));
+        if (c->text_free) TRI_HIP_TRY(hipEventSynchronize(c->text_free));
         if (bytes > c->cap_h_text) {
-            if (c->h_text) HIP_TRY(hipHostFree(c->h_text));
+            if (c->h_text) TRI_HIP_TRY(hipHostFree(c->h_text));
             c->h_text = nullptr;
             c->cap_h_text = bytes * 2;
-            HIP_TRY(hipHostMalloc(&c->h_text, c->cap_h_text, hipHostMallocDefault));
+            TRI_HIP_TRY(hipHostMalloc(&c->h_text, c->cap_h_text, hipHostMallocDefault));
         }
         std::memcpy(c->h_text, c->text_plan.blob.data(), bytes);
-        HIP_TRY(hipMemcpyAsync(c->d_text, c->h_text, bytes, hipMemcpyHostToDevice, c->stream));
-        if (!c->text_free) HIP_TRY(hipEventCreateWithFlags(&c->text_free, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->text_free, c->stream));
+        TRI_HIP_TRY(hipMemcpyAsync(c->d_text, c->h_text, bytes, hipMemcpyHostToDevice, c->stream));
+        if (!c->text_free) TRI_HIP_TRY(hipEventCreateWithFlags(&c->text_free, hipEventDisableTiming));
+        TRI_HIP_TRY(hipEventRecord(c->text_free, c->stream));
     }
     c->text_dirty = false;
     return TRI_OK;
@@ -654,7 +647,7 @@ int ensure_work_buffers(tri_ctx* c) {
     bool realloc = c->cap_clip < std::max<size_t>(c->nslots, 1) || c->cap_vary < nvary || c->cap_recs < nrec ||
                    c->cap_clip_slot < std::max<size_t>(c->nprims, 1) || c->cap_prim_vs < std::max<size_t>(c->nprims, 1) ||
                    c->cap_bin_list < nlist;
-    if (realloc) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (realloc) TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     if ((rc = grow(c->d_clip, c->cap_clip, std::max<size_t>(c->nslots, 1)))) return rc;
     if ((rc = grow(c->d_snap, c->cap_snap, std::max<size_t>(c->nslots, 1)))) return rc;
     if ((rc = grow(c->d_oc, c->cap_oc, std::max<size_t>(c->nslots, 1)))) return rc;
@@ -674,7 +667,7 @@ int ensure_work_buffers(tri_ctx* c) {
         const size_t smap = (size_t)c->shadow.size * c->shadow.size;
         if (c->cap_lpos < nvary / 3 || c->cap_lsnap < std::max<size_t>(c->nslots, 1) || c->cap_sbin_list < slist ||
             c->cap_sbin_count < c->s_nbins || c->cap_shadow < smap)
-            HIP_TRY(hipStreamSynchronize(c->stream));
+            TRI_HIP_TRY(hipStreamSynchronize(c->stream));
         if ((rc = grow(c->d_lpos, c->cap_lpos, nvary / 3))) return rc;
         if ((rc = grow(c->d_lsnap, c->cap_lsnap, std::max<size_t>(c->nslots, 1)))) return rc;
         if ((rc = grow(c->d_sbin_list, c->cap_sbin_list, slist))) return rc;
@@ -685,15 +678,15 @@ int ensure_work_buffers(tri_ctx* c) {
 
 int collect_timing(tri_ctx* c) {
     if (c->pending.empty()) return TRI_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     for (TimingSet& t : c->pending) {
         float ms[kStageCount] = {}, tot;
         // stamps: vertex | setup (+ the map's binning) | shadow-map raster (only with the pre-pass) | raster
-        HIP_TRY(hipEventElapsedTime(&ms[kStageVertex], t.ev[kStageVertex], t.ev[kStageSetup]));
-        HIP_TRY(hipEventElapsedTime(&ms[kStageSetup], t.ev[kStageSetup], t.ev[t.shadow ? kStageShadow : kStageRaster]));
-        if (t.shadow) HIP_TRY(hipEventElapsedTime(&ms[kStageShadow], t.ev[kStageShadow], t.ev[kStageRaster]));
-        HIP_TRY(hipEventElapsedTime(&ms[kStageRaster], t.ev[kStageRaster], t.ev[kStageCount]));
-        HIP_TRY(hipEventElapsedTime(&tot, t.ev[0], t.ev[kStageCount]));
+        TRI_HIP_TRY(hipEventElapsedTime(&ms[kStageVertex], t.ev[kStageVertex], t.ev[kStageSetup]));
+        TRI_HIP_TRY(hipEventElapsedTime(&ms[kStageSetup], t.ev[kStageSetup], t.ev[t.shadow ? kStageShadow : kStageRaster]));
+        if (t.shadow) TRI_HIP_TRY(hipEventElapsedTime(&ms[kStageShadow], t.ev[kStageShadow], t.ev[kStageRaster]));
+        TRI_HIP_TRY(hipEventElapsedTime(&ms[kStageRaster], t.ev[kStageRaster], t.ev[kStageCount]));
+        TRI_HIP_TRY(hipEventElapsedTime(&tot, t.ev[0], t.ev[kStageCount]));
         c->acc.ms_vertex += ms[kStageVertex];
         c->acc.ms_setup += ms[kStageSetup];
         c->acc.ms_shadow += ms[kStageShadow];
@@ -709,22 +702,22 @@ int collect_timing(tri_ctx* c) {
 int check_overflow(tri_ctx* c, const TriCounters* pinned = nullptr) {
     TriCounters h;
     if (pinned) h = *pinned;  // (copied on the context's stream before the wait)
-    else HIP_TRY(hipMemcpy(&h, c->d_ctr, sizeof h, hipMemcpyDeviceToHost));
+    else TRI_HIP_TRY(hipMemcpy(&h, c->d_ctr, sizeof h, hipMemcpyDeviceToHost));
     if (!h.flags) return TRI_OK;
     // the resets are stream-ordered before the next frame's kernels (the context's stream is non-blocking:
     // work on the null stream is not ordered with it)
-    HIP_TRY(hipMemsetAsync(&c->d_ctr->flags, 0, 4, c->stream));
+    TRI_HIP_TRY(hipMemsetAsync(&c->d_ctr->flags, 0, 4, c->stream));
     if (h.flags & TRI_OVF_CLIP_RECORDS) c->ovf_rec_cap *= 4;
     if (h.flags & TRI_OVF_CLIP_VERTS) c->ovf_vert_cap *= 4;
     if (h.flags & TRI_OVF_BIN_LIST) {
         c->bin_cap = std::max<uint32_t>(c->bin_cap * 2, h.bin_max + h.bin_max / 4);
         c->bin_cap = (c->bin_cap + 63) & ~63u;
-        HIP_TRY(hipMemsetAsync(&c->d_ctr->bin_max, 0, 4, c->stream));
+        TRI_HIP_TRY(hipMemsetAsync(&c->d_ctr->bin_max, 0, 4, c->stream));
     }
     if (h.flags & TRI_OVF_SHADOW_BIN_LIST) {
         c->s_bin_cap = std::max<uint32_t>(c->s_bin_cap * 2, h.sbin_max + h.sbin_max / 4);
         c->s_bin_cap = (c->s_bin_cap + 63) & ~63u;
-        HIP_TRY(hipMemsetAsync(&c->d_ctr->sbin_max, 0, 4, c->stream));
+        TRI_HIP_TRY(hipMemsetAsync(&c->d_ctr->sbin_max, 0, 4, c->stream));
     }
     int rc = ensure_work_buffers(c);
     if (rc) return rc;
@@ -754,7 +747,7 @@ int choose_bin_grid(tri_ctx* c) {
         bl = n32 > 16384 ? 6 : ((n32 < 4096 && density < 0.05) ? 4 : 5);
     }
     if (bl == c->bin_log2) return TRI_OK;
-    HIP_TRY(hipStreamSynchronize(c->stream));  // queued frames still use the old grid
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));  // queued frames still use the old grid
     int rc;
     const int32_t bs = 1 << bl;
     c->bin_log2 = bl;
@@ -763,7 +756,7 @@ int choose_bin_grid(tri_ctx* c) {
     c->nbins = c->nbx * c->nby;
     c->bin_cap = 0;  // re-derived for the new grid by ensure_work_buffers
     if ((rc = grow(c->d_bin_count, c->cap_bin_count, (size_t)c->nbins))) return rc;
-    HIP_TRY(hipMemsetAsync(c->d_bin_count, 0, (size_t)c->nbins * 4, c->stream));  // before this frame's k_setup
+    TRI_HIP_TRY(hipMemsetAsync(c->d_bin_count, 0, (size_t)c->nbins * 4, c->stream));  // before this frame's k_setup
     return TRI_OK;
 }
 
@@ -805,7 +798,7 @@ int geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uin
             std::memcpy(skin[i].w, v[i].bone_weights, 16);
         }
         if ((rc = grow(g->d_skin, g->cap_skin, nv))) return rc;
-        HIP_TRY(hipMemcpy(g->d_skin, skin.data(), nv * sizeof(TriVsSkin), hipMemcpyHostToDevice));
+        TRI_HIP_TRY(hipMemcpy(g->d_skin, skin.data(), nv * sizeof(TriVsSkin), hipMemcpyHostToDevice));
     }
     g->has_skin_data = has_skin;
     g->obj_ok = obj_ok;
@@ -815,7 +808,7 @@ int geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uin
         g->uni_col = vin[i].cr == vin[0].cr && vin[i].cg == vin[0].cg && vin[i].cb == vin[0].cb;
     if (g->uni_col) { g->ucol[0] = vin[0].cr; g->ucol[1] = vin[0].cg; g->ucol[2] = vin[0].cb; }
     if ((rc = grow(g->d_vin, g->cap_vin, std::max<uint64_t>(nv, 1)))) return rc;
-    if (nv) HIP_TRY(hipMemcpy(g->d_vin, vin.data(), nv * sizeof(TriVsIn), hipMemcpyHostToDevice));
+    if (nv) TRI_HIP_TRY(hipMemcpy(g->d_vin, vin.data(), nv * sizeof(TriVsIn), hipMemcpyHostToDevice));
     {  // the object-space streams of vary_obj frames: positions (k_vertex) and 36-B attribute records (k_raster)
         std::vector<float> pos(3 * nv), attr(9 * nv);
         for (uint64_t i = 0; i < nv; ++i) {
@@ -826,11 +819,11 @@ int geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uin
         }
         if ((rc = grow(g->d_pos, g->cap_pos, std::max<uint64_t>(3 * nv, 3)))) return rc;
         if ((rc = grow(g->d_attr, g->cap_attr, std::max<uint64_t>(9 * nv, 9)))) return rc;
-        if (nv) HIP_TRY(hipMemcpy(g->d_pos, pos.data(), nv * 12, hipMemcpyHostToDevice));
-        if (nv) HIP_TRY(hipMemcpy(g->d_attr, attr.data(), nv * 36, hipMemcpyHostToDevice));
+        if (nv) TRI_HIP_TRY(hipMemcpy(g->d_pos, pos.data(), nv * 12, hipMemcpyHostToDevice));
+        if (nv) TRI_HIP_TRY(hipMemcpy(g->d_attr, attr.data(), nv * 36, hipMemcpyHostToDevice));
     }
     if ((rc = grow(g->d_idx, g->cap_idx, std::max<uint64_t>(ni, 1)))) return rc;
-    if (ni) HIP_TRY(hipMemcpy(g->d_idx, idx, ni * 4, hipMemcpyHostToDevice));
+    if (ni) TRI_HIP_TRY(hipMemcpy(g->d_idx, idx, ni * 4, hipMemcpyHostToDevice));
     g->nverts = nv;
     g->nidx = ni;
     g->meshes.assign(meshes, meshes + nm);
@@ -907,12 +900,12 @@ int geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uin
         }
     }
     if ((rc = grow(g->d_clusters, g->cap_clusters, std::max<size_t>(cl.size(), 1)))) return rc;
-    if (!cl.empty()) HIP_TRY(hipMemcpy(g->d_clusters, cl.data(), cl.size() * sizeof(TriCluster), hipMemcpyHostToDevice));
+    if (!cl.empty()) TRI_HIP_TRY(hipMemcpy(g->d_clusters, cl.data(), cl.size() * sizeof(TriCluster), hipMemcpyHostToDevice));
     if ((rc = grow(g->d_vbox, g->cap_vbox, std::max<size_t>(vbox.size(), 1)))) return rc;
-    if (!vbox.empty()) HIP_TRY(hipMemcpy(g->d_vbox, vbox.data(), vbox.size() * sizeof(TriCluster), hipMemcpyHostToDevice));
+    if (!vbox.empty()) TRI_HIP_TRY(hipMemcpy(g->d_vbox, vbox.data(), vbox.size() * sizeof(TriCluster), hipMemcpyHostToDevice));
     // null-stream copies are not ordered with the contexts' non-blocking streams: complete them before any
     // context can launch a frame that reads this geometry
-    HIP_TRY(hipStreamSynchronize(nullptr));
+    TRI_HIP_TRY(hipStreamSynchronize(nullptr));
     g->geometry_set = true;
     // versions come from one process-wide counter: a context that switches between geometry objects
     // (tri_bind_geometry, tri_upload_geometry) can never see an equal version on a different object
@@ -935,10 +928,40 @@ hipStream_t tri_internal_stream(tri_ctx* c) { return c->stream; }
 int tri_internal_device(tri_ctx* c) { return c->device; }
 bool tri_internal_whole_frame(tri_ctx* c) { return c->y0 == 0 && c->y1 == c->H; }
 int tri_internal_fail(int code, const char* msg) { return fail(code, "%s", msg); }
+int tri_hip_fail(hipError_t e, const char* what) {
+    return fail(e == hipErrorOutOfMemory ? TRI_E_OOM : TRI_E_HIP, "%s: %s", what, hipGetErrorString(e));
+}
 int tri_internal_geometry_device(const tri_geometry* g) { return g->device; }
 int tri_internal_font_device(const tri_font* f) { return f->device; }
 uint32_t tri_internal_pose_prefix(tri_ctx* c) { return c->nbones_prefix; }
 const float* tri_internal_unorm_lut(tri_ctx* c) { return c->d_lut + 256; }
+
+int tri_resolve_device(int32_t requested, const char* who, int* device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TRI_E_HIP, "%s: no HIP device available", who);
+    if (requested >= ndev) return fail(TRI_E_INVALID, "%s: device %d of %d", who, requested, ndev);
+    *device = requested;
+    if (requested < 0) {
+        const hipError_t e = hipGetDevice(device);
+        if (e != hipSuccess) return fail(TRI_E_HIP, "%s: hipGetDevice: %s", who, hipGetErrorString(e));
+    }
+    return TRI_OK;
+}
+
+int tri_check_extent(const char* who, uint32_t w, uint32_t h, const char* what) {
+    if (w == 0 || h == 0 || w > TRI_MAX_DIM || h > TRI_MAX_DIM)
+        return fail(TRI_E_INVALID, "%s: %s %ux%u outside 1..%d", who, what, w, h, TRI_MAX_DIM);
+    return TRI_OK;
+}
+
+int tri_check_bgra_source(const char* who, const void* bgra, uint32_t w, uint32_t h, uint32_t pitch_bytes) {
+    if (!bgra) return fail(TRI_E_INVALID, "%s: null pointer", who);
+    if (const int rc = tri_check_extent(who, w, h)) return rc;
+    if (pitch_bytes < w * 4u || (pitch_bytes & 3u))
+        return fail(TRI_E_INVALID, "%s: pitch below width * 4 or not a multiple of 4", who);
+    if ((uintptr_t)bgra & 3u) return fail(TRI_E_INVALID, "%s: source must be 4-B aligned", who);
+    return TRI_OK;
+}
 
 extern "C" {
 
@@ -948,31 +971,23 @@ int tri_abi_version(void) { return TRI_RASTER_ABI_VERSION; }
 int tri_create(const tri_config* cfg, tri_ctx** out) {
     if (!cfg || !out) return fail(TRI_E_INVALID, "tri_create: null argument");
     *out = nullptr;
-    if (cfg->width == 0 || cfg->height == 0 || cfg->width > TRI_MAX_DIM || cfg->height > TRI_MAX_DIM)
-        return fail(TRI_E_INVALID, "tri_create: framebuffer %ux%u outside 1..%d", cfg->width, cfg->height, TRI_MAX_DIM);
+    int rc = tri_check_extent("tri_create", cfg->width, cfg->height, "framebuffer");
+    if (rc) return rc;
     uint32_t y0 = cfg->band_y0, y1 = cfg->band_y1;
     if (y0 == 0 && y1 == 0) y1 = cfg->height;
     if (y0 >= y1 || y1 > cfg->height) return fail(TRI_E_INVALID, "tri_create: bad row band [%u,%u)", y0, y1);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(TRI_E_HIP, "tri_create: no HIP device available");
+    int dev = 0;
+    if ((rc = tri_resolve_device(cfg->device, "tri_create", &dev))) return rc;
     tri_ctx* c = new tri_ctx();
     c->cfg = *cfg;
-    if (cfg->device >= 0) {
-        if (cfg->device >= ndev) { delete c; return fail(TRI_E_INVALID, "tri_create: device %d of %d", cfg->device, ndev); }
-        c->device = cfg->device;
-    } else if (hipGetDevice(&c->device) != hipSuccess) {
-        delete c;
-        return fail(TRI_E_HIP, "tri_create: hipGetDevice failed");
-    }
+    c->device = dev;
     c->W = (int32_t)cfg->width;
     c->H = (int32_t)cfg->height;
     c->y0 = (int32_t)y0;
     c->y1 = (int32_t)y1;
     c->bin_log2 = 0;  // the bin grid is chosen at the first tri_render (choose_bin_grid)
     auto bail = [&](int rc) { tri_destroy(c); return rc; };
-    int rc = make_current(c);
-    if (rc) return bail(rc);
+    if ((rc = make_current(c))) return bail(rc);
     if (hipDeviceGetAttribute(&c->cu_count, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess ||
         c->cu_count <= 0)
         c->cu_count = 256;
@@ -1050,10 +1065,10 @@ int tri_set_stream(tri_ctx* c, void* s) {
         int rc = make_current(c);
         if (rc) return rc;
         hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(e, c->stream));
-        HIP_TRY(hipStreamWaitEvent(next, e, 0));
-        HIP_TRY(hipEventDestroy(e));
+        TRI_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        TRI_HIP_TRY(hipEventRecord(e, c->stream));
+        TRI_HIP_TRY(hipStreamWaitEvent(next, e, 0));
+        TRI_HIP_TRY(hipEventDestroy(e));
     }
     c->stream = next;
     return TRI_OK;
@@ -1064,7 +1079,7 @@ int tri_upload_geometry(tri_ctx* c, const tri_vertex* v, uint64_t nv, const uint
     if (!c) return fail(TRI_E_INVALID, "tri_upload_geometry: null context");
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     c->geom = &c->own_geom;
     c->own_geom.device = c->device;
     c->geom_seen = 0;  // re-resolve the draws against the new buffers even if the draw list is unchanged
@@ -1075,11 +1090,8 @@ int tri_upload_geometry(tri_ctx* c, const tri_vertex* v, uint64_t nv, const uint
 int tri_geometry_create(int32_t device, tri_geometry** out) {
     if (!out) return fail(TRI_E_INVALID, "tri_geometry_create: null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TRI_E_HIP, "tri_geometry_create: no HIP device available");
-    int d = device;
-    if (d < 0 && hipGetDevice(&d) != hipSuccess) return fail(TRI_E_HIP, "tri_geometry_create: hipGetDevice failed");
-    if (d >= ndev) return fail(TRI_E_INVALID, "tri_geometry_create: device %d of %d", d, ndev);
+    int d = 0;
+    if (const int rc = tri_resolve_device(device, "tri_geometry_create", &d)) return rc;
     tri_geometry* g = new tri_geometry();
     g->device = d;
     g->shared = true;
@@ -1090,8 +1102,8 @@ int tri_geometry_create(int32_t device, tri_geometry** out) {
 int tri_geometry_upload(tri_geometry* g, const tri_vertex* v, uint64_t nv, const uint32_t* idx, uint64_t ni,
                         const tri_mesh_range* meshes, uint32_t nm) {
     if (!g) return fail(TRI_E_INVALID, "tri_geometry_upload: null geometry");
-    HIP_TRY(hipSetDevice(g->device));
-    HIP_TRY(hipDeviceSynchronize());  // any context's stream may be reading the old buffers
+    TRI_HIP_TRY(hipSetDevice(g->device));
+    TRI_HIP_TRY(hipDeviceSynchronize());  // any context's stream may be reading the old buffers
     return geometry_upload(g, v, nv, idx, ni, meshes, nm);
 }
 
@@ -1110,7 +1122,7 @@ int tri_bind_geometry(tri_ctx* c, tri_geometry* g) {
         return fail(TRI_E_INVALID, "tri_bind_geometry: geometry on device %d, context on device %d", g->device, c->device);
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     c->geom = g ? g : &c->own_geom;
     c->geom_seen = 0;
     c->draws_dirty = true;
@@ -1131,12 +1143,12 @@ int tri_upload_texture(tri_ctx* c, uint32_t slot, const uint8_t* rgba, uint32_t 
         return fail(TRI_E_INVALID, "tri_upload_texture: bad texture %ux%u", w, h);
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_tex[slot]) HIP_TRY(hipFree(c->d_tex[slot]));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->d_tex[slot]) TRI_HIP_TRY(hipFree(c->d_tex[slot]));
     c->d_tex[slot] = nullptr;
-    HIP_TRY(hipMalloc(&c->d_tex[slot], (size_t)w * h * 4));
-    HIP_TRY(hipMemcpy(c->d_tex[slot], rgba, (size_t)w * h * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
+    TRI_HIP_TRY(hipMalloc(&c->d_tex[slot], (size_t)w * h * 4));
+    TRI_HIP_TRY(hipMemcpy(c->d_tex[slot], rgba, (size_t)w * h * 4, hipMemcpyHostToDevice));
+    TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->tex_w[slot] = w;
     c->tex_h[slot] = h;
     std::memcpy(&c->tex_solid[slot], rgba, 4);
@@ -1155,10 +1167,10 @@ int tri_upload_bone_palette(tri_ctx* c, const float* m, uint32_t n) {
     if (n && !m) return fail(TRI_E_INVALID, "tri_upload_bone_palette: null matrices");
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     if ((rc = grow(c->d_bones, c->cap_bones, std::max<size_t>(16ull * n, 16)))) return rc;
-    if (n) HIP_TRY(hipMemcpy(c->d_bones, m, 64ull * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
+    if (n) TRI_HIP_TRY(hipMemcpy(c->d_bones, m, 64ull * n, hipMemcpyHostToDevice));
+    TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->nbones = n;
     c->nbones_prefix = n;  // the posed suffix, if any, is dropped
     return TRI_OK;
@@ -1178,10 +1190,10 @@ int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst
     if ((rc = make_current(c))) return rc;
     if (16ull * extent > c->cap_bones || !c->d_bones) {
         // grow, keeping the prefix: frames in flight read the old palette
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        TRI_HIP_TRY(hipStreamSynchronize(c->stream));
         float* grown = nullptr;
         const size_t cap = std::max<size_t>(16ull * extent, 2 * c->cap_bones);
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(float)));
+        TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(float)));
         hipError_t e = hipMemset(grown, 0, cap * sizeof(float));
         if (e == hipSuccess && c->nbones_prefix)
             e = hipMemcpy(grown, c->d_bones, 64ull * c->nbones_prefix, hipMemcpyDeviceToDevice);
@@ -1190,25 +1202,25 @@ int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst
             (void)hipFree(grown);
             return fail(TRI_E_HIP, "tri_pose_palette: growing the palette: %s", hipGetErrorString(e));
         }
-        if (c->d_bones) HIP_TRY(hipFree(c->d_bones));
+        if (c->d_bones) TRI_HIP_TRY(hipFree(c->d_bones));
         c->d_bones = grown;
         c->cap_bones = cap;
     }
     tri_ctx::PoseStage& ps = c->pose_stage[c->pose_next];
-    if (ps.busy) HIP_TRY(hipEventSynchronize(ps.done));  // four calls back: long complete unless the device is that far behind
+    if (ps.busy) TRI_HIP_TRY(hipEventSynchronize(ps.done));  // four calls back: long complete unless the device is that far behind
     ps.busy = false;
     if (n > ps.cap) {
-        if (ps.h) HIP_TRY(hipHostFree(ps.h));
+        if (ps.h) TRI_HIP_TRY(hipHostFree(ps.h));
         ps.h = nullptr;
-        if (ps.d) HIP_TRY(hipFree(ps.d));
+        if (ps.d) TRI_HIP_TRY(hipFree(ps.d));
         ps.d = nullptr;
         ps.cap = 0;
         const size_t cap = std::max<size_t>(n, 256);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ps.h), cap * sizeof(tri_pose_instance), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ps.d), cap * sizeof(tri_pose_instance)));
+        TRI_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ps.h), cap * sizeof(tri_pose_instance), hipHostMallocDefault));
+        TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ps.d), cap * sizeof(tri_pose_instance)));
         ps.cap = cap;
     }
-    if (!ps.done) HIP_TRY(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
+    if (!ps.done) TRI_HIP_TRY(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
     // the records grouped by skeleton size, one launch per group: a workgroup's LDS is sized by its launch's largest
     // skeleton, and a 256-bone instance should not make every 20-bone one reserve 40 KiB
     static const uint32_t kBucket[3] = {32, 128, TRI_POSE_MAX_BONES};
@@ -1219,10 +1231,10 @@ int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst
     first[3] += first[2];
     uint32_t at[3] = {0, first[1], first[2]};
     for (uint32_t i = 0; i < n; ++i) ps.h[at[bones[i] <= kBucket[0] ? 0 : bones[i] <= kBucket[1] ? 1 : 2]++] = inst[i];
-    HIP_TRY(hipMemcpyAsync(ps.d, ps.h, (size_t)n * sizeof(tri_pose_instance), hipMemcpyHostToDevice, c->stream));
+    TRI_HIP_TRY(hipMemcpyAsync(ps.d, ps.h, (size_t)n * sizeof(tri_pose_instance), hipMemcpyHostToDevice, c->stream));
     for (int b = 0; b < 3; ++b)
-        HIP_TRY(tri_launch_pose(set, ps.d + first[b], first[b + 1] - first[b], kBucket[b], c->d_bones, c->stream));
-    HIP_TRY(hipEventRecord(ps.done, c->stream));
+        TRI_HIP_TRY(tri_launch_pose(set, ps.d + first[b], first[b + 1] - first[b], kBucket[b], c->d_bones, c->stream));
+    TRI_HIP_TRY(hipEventRecord(ps.done, c->stream));
     ps.busy = true;
     c->pose_next = (c->pose_next + 1) % 4;
     c->nbones = extent;
@@ -1236,8 +1248,8 @@ int tri_read_bone_palette(tri_ctx* c, float* out, uint32_t n) {
     if (!out) return fail(TRI_E_INVALID, "tri_read_bone_palette: null destination");
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(out, c->d_bones, 64ull * n, hipMemcpyDeviceToHost));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipMemcpy(out, c->d_bones, 64ull * n, hipMemcpyDeviceToHost));
     return TRI_OK;
 }
 
@@ -1250,11 +1262,11 @@ int tri_upload_skybox(tri_ctx* c, const uint8_t* faces, uint32_t n) {
     if (n > 16384) return fail(TRI_E_INVALID, "tri_upload_skybox: face size %u too large", n);
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     const size_t texels = 6ull * n * n;
     if ((rc = grow(c->d_sky, c->cap_sky, texels))) return rc;
-    HIP_TRY(hipMemcpy(c->d_sky, faces, texels * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
+    TRI_HIP_TRY(hipMemcpy(c->d_sky, faces, texels * 4, hipMemcpyHostToDevice));
+    TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->sky_size = n;
     const uint32_t* t = reinterpret_cast<const uint32_t*>(faces);
     uint32_t t0;
@@ -1283,10 +1295,10 @@ int tri_upload_ai_frame(tri_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h
         return fail(TRI_E_INVALID, "tri_upload_ai_frame: extent %ux%u outside 1..%d", w, h, TRI_MAX_DIM);
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));  // no queued frame still samples the previous texture
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));  // no queued frame still samples the previous texture
     if ((rc = grow(c->d_ai, c->cap_ai, (size_t)w * h))) return rc;
-    HIP_TRY(hipMemcpy(c->d_ai, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
+    TRI_HIP_TRY(hipMemcpy(c->d_ai, rgba8, (size_t)w * h * 4, hipMemcpyHostToDevice));
+    TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->ai_w = w;
     c->ai_h = h;
     return TRI_OK;
@@ -1311,9 +1323,9 @@ int tri_set_shadow(tri_ctx* c, const tri_shadow_config* cfg) {
     if (rc) return rc;
     const uint32_t nbx = (cfg->size + 31) / 32;
     if (cfg->size != c->shadow.size) {  // new map grid: fresh (zeroed) queue counters
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        TRI_HIP_TRY(hipStreamSynchronize(c->stream));
         if ((rc = grow(c->d_sbin_count, c->cap_sbin_count, (size_t)nbx * nbx))) return rc;
-        HIP_TRY(hipMemsetAsync(c->d_sbin_count, 0, (size_t)nbx * nbx * 4, c->stream));
+        TRI_HIP_TRY(hipMemsetAsync(c->d_sbin_count, 0, (size_t)nbx * nbx * 4, c->stream));
         c->s_bin_cap = 0;
         c->shadow_rendered = false;
     }
@@ -1337,7 +1349,7 @@ int tri_read_shadow_map(tri_ctx* c, uint32_t* out) {
     if (!c->shadow.size || !c->shadow_rendered) return fail(TRI_E_STATE, "tri_read_shadow_map: no shadow pass rendered");
     int rc = tri_synchronize(c);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(out, c->d_shadow, (size_t)c->shadow.size * c->shadow.size * 4, hipMemcpyDeviceToHost));
+    TRI_HIP_TRY(hipMemcpy(out, c->d_shadow, (size_t)c->shadow.size * c->shadow.size * 4, hipMemcpyDeviceToHost));
     return TRI_OK;
 }
 
@@ -1381,14 +1393,10 @@ int tri_frame_alpha(tri_ctx* c, int32_t* alpha) {
 int tri_font_create(int32_t device, const uint8_t* alpha, uint32_t width, uint32_t height, tri_font** out) {
     if (!alpha || !out) return fail(TRI_E_INVALID, "tri_font_create: null argument");
     *out = nullptr;
-    if (width == 0 || height == 0 || width > TRI_MAX_DIM || height > TRI_MAX_DIM)
-        return fail(TRI_E_INVALID, "tri_font_create: atlas %ux%u outside 1..%d", width, height, TRI_MAX_DIM);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TRI_E_HIP, "tri_font_create: no HIP device available");
-    int dev = device;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    if (dev >= ndev) return fail(TRI_E_INVALID, "tri_font_create: device %d of %d", dev, ndev);
-    HIP_TRY(hipSetDevice(dev));
+    if (const int rc = tri_check_extent("tri_font_create", width, height, "atlas")) return rc;
+    int dev = 0;
+    if (const int rc = tri_resolve_device(device, "tri_font_create", &dev)) return rc;
+    TRI_HIP_TRY(hipSetDevice(dev));
     tri_font* f = new tri_font();
     f->device = dev;
     f->w = width;
@@ -1491,8 +1499,8 @@ int tri_render(tri_ctx* c) {
         // geometry may be shared with contexts on other streams, so the zeros are in place (device
         // synchronised) before the shared flag says so.
         if ((rc = grow(c->geom->d_skin, c->geom->cap_skin, std::max<uint64_t>(c->geom->nverts, 1)))) return rc;
-        HIP_TRY(hipMemset(c->geom->d_skin, 0, std::max<uint64_t>(c->geom->nverts, 1) * sizeof(TriVsSkin)));
-        HIP_TRY(hipDeviceSynchronize());
+        TRI_HIP_TRY(hipMemset(c->geom->d_skin, 0, std::max<uint64_t>(c->geom->nverts, 1) * sizeof(TriVsSkin)));
+        TRI_HIP_TRY(hipDeviceSynchronize());
         c->geom->has_skin_data = true;
     }
     if ((rc = choose_bin_grid(c))) return rc;
@@ -1677,7 +1685,7 @@ int tri_render(tri_ctx* c) {
             ts = c->free_sets.back();
             c->free_sets.pop_back();
         } else {
-            for (auto& e : ts.ev) HIP_TRY(hipEventCreate(&e));
+            for (auto& e : ts.ev) TRI_HIP_TRY(hipEventCreate(&e));
         }
         ev = ts.ev;
     }
@@ -1690,13 +1698,13 @@ int tri_render(tri_ctx* c) {
     if (c->diag_frames++ > 0) tri_diag_front_plan(plan);
 #endif
     TRI_HSTAMP(3);
-    HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev));
+    TRI_HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev));
     c->launched = true;
     // the text pass (TextRenderer::RecordViewport, after the mesh / sky pass): only when quads are set. A
     // TRI_E_OVERFLOW re-render restarts from the clear, so the overlay is reapplied by construction.
     if (c->text_font && !c->text_quads.empty()) {
         if ((rc = upload_text(c))) return rc;
-        HIP_TRY(tri_launch_text(c->d_color, c->W, c->y0, c->y1, c->text_plan, c->d_text, c->text_font->d_alpha,
+        TRI_HIP_TRY(tri_launch_text(c->d_color, c->W, c->y0, c->y1, c->text_plan, c->d_text, c->text_font->d_alpha,
                                 c->text_font->w, c->text_font->h, c->stream));
     }
     if (timed) c->pending.push_back(ts);
@@ -1717,9 +1725,9 @@ int tri_synchronize(tri_ctx* c) {
     if (rc) return rc;
     // the counters ride the stream into pinned memory, so one wait covers the frame and its flags (a blocking
     // hipMemcpy after the wait cost the engine's per-frame fence another round trip)
-    if (!c->h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_ctr), sizeof(TriCounters), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(TriCounters), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (!c->h_ctr) TRI_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_ctr), sizeof(TriCounters), hipHostMallocDefault));
+    TRI_HIP_TRY(hipMemcpyAsync(c->h_ctr, c->d_ctr, sizeof(TriCounters), hipMemcpyDeviceToHost, c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     return check_overflow(c, c->h_ctr);
 }
 
@@ -1728,11 +1736,11 @@ int tri_readback(tri_ctx* c, uint8_t* bgra, uint32_t* depth) {
     int rc = tri_synchronize(c);
     if (rc) return rc;
     const size_t px = (size_t)c->W * (size_t)(c->y1 - c->y0);
-    if (bgra) HIP_TRY(hipMemcpy(bgra, c->d_color, px * 4, hipMemcpyDeviceToHost));
+    if (bgra) TRI_HIP_TRY(hipMemcpy(bgra, c->d_color, px * 4, hipMemcpyDeviceToHost));
     if (depth) {
         if (c->cfg.flags & TRI_FLAG_NO_DEPTH_OUTPUT)
             return fail(TRI_E_STATE, "tri_readback: depth output disabled by TRI_FLAG_NO_DEPTH_OUTPUT");
-        HIP_TRY(hipMemcpy(depth, c->d_depth, px * 4, hipMemcpyDeviceToHost));
+        TRI_HIP_TRY(hipMemcpy(depth, c->d_depth, px * 4, hipMemcpyDeviceToHost));
     }
     return TRI_OK;
 }
@@ -1751,15 +1759,14 @@ int tri_get_output(tri_ctx* c, tri_image* out) {
 
 int tri_blit_linear(tri_ctx* c, void* dst, uint32_t width, uint32_t height) {
     if (!c) return fail(TRI_E_INVALID, "tri_blit_linear: null context");
-    if (width == 0 || height == 0 || width > TRI_MAX_DIM || height > TRI_MAX_DIM)
-        return fail(TRI_E_INVALID, "tri_blit_linear: destination %ux%u outside 1..%d", width, height, TRI_MAX_DIM);
+    if (const int rc = tri_check_extent("tri_blit_linear", width, height, "destination")) return rc;
     if (c->y0 != 0 || c->y1 != c->H) return fail(TRI_E_STATE, "tri_blit_linear: a row-band context has no whole frame");
     int rc = make_current(c);
     if (rc) return rc;
     uint32_t* out = static_cast<uint32_t*>(dst);
     if (!out) {
         if ((size_t)width * height > c->cap_present) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
+            TRI_HIP_TRY(hipStreamSynchronize(c->stream));
         }
         if ((rc = grow(c->d_present, c->cap_present, (size_t)width * height))) return rc;
         out = c->d_present;
@@ -1769,7 +1776,7 @@ int tri_blit_linear(tri_ctx* c, void* dst, uint32_t width, uint32_t height) {
         c->present_w = c->present_h = 0;  // the owned target no longer holds the latest blit: read_present fails
     }
     // the alpha half of the decode LUT is the UNORM8 decode b / 255 (IEEE float division)
-    HIP_TRY(tri_launch_blit(c->d_color, c->W, c->H, out, (int32_t)width, (int32_t)height, c->d_lut + 256, c->stream));
+    TRI_HIP_TRY(tri_launch_blit(c->d_color, c->W, c->H, out, (int32_t)width, (int32_t)height, c->d_lut + 256, c->stream));
     return TRI_OK;
 }
 
@@ -1778,8 +1785,8 @@ int tri_read_present(tri_ctx* c, uint8_t* bgra) {
     if (!c->d_present || !c->present_w) return fail(TRI_E_STATE, "tri_read_present: nothing was blitted");
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    HIP_TRY(hipMemcpy(bgra, c->d_present, (size_t)c->present_w * c->present_h * 4, hipMemcpyDeviceToHost));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipMemcpy(bgra, c->d_present, (size_t)c->present_w * c->present_h * 4, hipMemcpyDeviceToHost));
     return TRI_OK;
 }
 
@@ -1807,13 +1814,13 @@ int tri_get_frame_stats(tri_ctx* c, tri_frame_stats* out) {
     if (!c || !out) return fail(TRI_E_INVALID, "tri_get_frame_stats: null argument");
     int rc = make_current(c);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
     TriCounters h;
-    HIP_TRY(hipMemcpy(&h, c->d_ctr, sizeof h, hipMemcpyDeviceToHost));
+    TRI_HIP_TRY(hipMemcpy(&h, c->d_ctr, sizeof h, hipMemcpyDeviceToHost));
     std::memset(out, 0, sizeof *out);
     out->triangles_in = c->nprims;
     std::vector<uint2> ws(c->last_nchunks);
-    if (!ws.empty()) HIP_TRY(hipMemcpy(ws.data(), c->d_setup_stats, ws.size() * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (!ws.empty()) TRI_HIP_TRY(hipMemcpy(ws.data(), c->d_setup_stats, ws.size() * sizeof(uint2), hipMemcpyDeviceToHost));
     uint64_t setup = h.tris_setup, entries = h.bin_entries;  // per-frame counters (0 unless a kernel adds)
     for (const uint2& w : ws) {
         setup += w.x;

@@ -32,6 +32,7 @@
 // is received). Everything else — the pack, the receive buffers, the batched decode and an assemble-only display's
 // own streams — is the code the N-GPU run executes. The caller drives the ranks frame by frame, senders before the
 // display (a receive whose send was not posted yet is TRI_E_STATE).
+#include "capi_util.h"
 #include "raster_launch.h"
 
 #include <hip/hip_runtime.h>
@@ -102,19 +103,10 @@ struct tri_xfer {
 
 namespace {
 
-int xfail(hipError_t e, const char* what) {
-    const std::string m = std::string(what) + ": " + hipGetErrorString(e);
-    return tri_internal_fail(e == hipErrorOutOfMemory ? TRI_E_OOM : TRI_E_HIP, m.c_str());
-}
 int nfail(ncclResult_t r, const char* what) {
     const std::string m = std::string(what) + ": " + ncclGetErrorString(r);
     return tri_internal_fail(TRI_E_HIP, m.c_str());
 }
-#define XH(expr)                                          \
-    do {                                                  \
-        const hipError_t _e = (expr);                     \
-        if (_e != hipSuccess) return xfail(_e, #expr);    \
-    } while (0)
 #define XN(expr)                                          \
     do {                                                  \
         const ncclResult_t _r = (expr);                   \
@@ -137,9 +129,9 @@ int lb_send(tri_xfer_comm* c, const void* src, uint64_t bytes, uint32_t peer, hi
     auto m = std::make_shared<LbMsg>();
     m->src = src;
     m->bytes = bytes;
-    XH(hipEventCreateWithFlags(&m->ready, hipEventDisableTiming));
-    XH(hipEventCreateWithFlags(&m->consumed, hipEventDisableTiming));
-    XH(hipEventRecord(m->ready, s));
+    TRI_HIP_TRY(hipEventCreateWithFlags(&m->ready, hipEventDisableTiming));
+    TRI_HIP_TRY(hipEventCreateWithFlags(&m->consumed, hipEventDisableTiming));
+    TRI_HIP_TRY(hipEventRecord(m->ready, s));
     c->lb->chan[c->channel][c->rank].push_back(m);
     out = m;
     return TRI_OK;
@@ -151,9 +143,9 @@ int lb_recv(tri_xfer_comm* c, void* to, uint64_t bytes, uint32_t peer, hipStream
     std::shared_ptr<LbMsg> m = q.front();
     q.pop_front();
     if (m->bytes != bytes) return tri_internal_fail(TRI_E_STATE, "tri_xfer loopback: send and receive sizes differ");
-    XH(hipStreamWaitEvent(s, m->ready, 0));
-    XH(hipMemcpyAsync(to, m->src, bytes, hipMemcpyDeviceToDevice, s));
-    XH(hipEventRecord(m->consumed, s));
+    TRI_HIP_TRY(hipStreamWaitEvent(s, m->ready, 0));
+    TRI_HIP_TRY(hipMemcpyAsync(to, m->src, bytes, hipMemcpyDeviceToDevice, s));
+    TRI_HIP_TRY(hipEventRecord(m->consumed, s));
     m->received = true;
     return TRI_OK;
 }
@@ -182,7 +174,7 @@ int tri_xfer_unique_id(uint8_t* id) {
 int tri_xfer_comm_create(const uint8_t* id, uint32_t world, uint32_t rank, int32_t device, tri_xfer_comm** out) {
     if (!id || !out || world == 0 || rank >= world) return tri_internal_fail(TRI_E_INVALID, "tri_xfer_comm_create: bad argument");
     *out = nullptr;
-    XH(hipSetDevice(device));
+    TRI_HIP_TRY(hipSetDevice(device));
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof(u));
     tri_xfer_comm* xc = new tri_xfer_comm();
@@ -224,7 +216,7 @@ int tri_xfer_loopback_destroy(tri_xfer_loopback* lb) {
 int tri_xfer_comm_create_loopback(tri_xfer_loopback* lb, uint32_t rank, int32_t device, tri_xfer_comm** out) {
     if (!lb || !out || rank >= lb->world) return tri_internal_fail(TRI_E_INVALID, "tri_xfer_comm_create_loopback: bad argument");
     *out = nullptr;
-    XH(hipSetDevice(device));
+    TRI_HIP_TRY(hipSetDevice(device));
     tri_xfer_comm* xc = new tri_xfer_comm();
     xc->device = device;
     xc->world = lb->world;
@@ -272,7 +264,7 @@ int tri_xfer_create(tri_xfer_comm* const* comms, uint32_t ncomm, const tri_xfer_
     for (uint32_t r = 0; r < N; ++r)
         if (cfg->band_y[r + 1] < cfg->band_y[r] || (cfg->band_y[r + 1] == cfg->band_y[r] && (r != cfg->display || N == 1)))
             return tri_internal_fail(TRI_E_INVALID, "tri_xfer_create: every band but the display's needs at least one row");
-    XH(hipSetDevice(comms[0]->device));
+    TRI_HIP_TRY(hipSetDevice(comms[0]->device));
     tri_xfer* x = new tri_xfer();
     x->xc.assign(comms, comms + ncomm);
     x->device = comms[0]->device;
@@ -333,21 +325,21 @@ int tri_xfer_frame(tri_xfer* x, uint32_t slot, tri_ctx* ctx, void* depth, const 
     if (ctx && band_pixels(x, me) == 0)
         return tri_internal_fail(TRI_E_INVALID, "tri_xfer_frame: an assemble-only display (empty band) renders nothing");
     const bool disp = me == x->display;
-    XH(hipSetDevice(x->device));
+    TRI_HIP_TRY(hipSetDevice(x->device));
     uint32_t* frame = x->pixels[slot];  // the band (sender) or the frame (display)
     // the slot's stream: its context's (render and transfer in one stream order), else the last one it ran on
     if (!ctx && !x->stream[slot] && !x->own[slot])  // an exchange-only slot that never rendered: a stream of its own
-        XH(hipStreamCreateWithFlags(&x->own[slot], hipStreamNonBlocking));
+        TRI_HIP_TRY(hipStreamCreateWithFlags(&x->own[slot], hipStreamNonBlocking));
     hipStream_t s = ctx ? tri_internal_stream(ctx) : (x->stream[slot] ? x->stream[slot] : x->own[slot]);
     if (x->stream[slot] && x->stream[slot] != s) {  // the slot moves to another stream: fence its last frame
-        XH(hipEventRecord(x->freed[slot], x->stream[slot]));
-        XH(hipStreamWaitEvent(s, x->freed[slot], 0));
+        TRI_HIP_TRY(hipEventRecord(x->freed[slot], x->stream[slot]));
+        TRI_HIP_TRY(hipStreamWaitEvent(s, x->freed[slot], 0));
     }
     x->stream[slot] = s;
     if (x->lb_sent[slot]) {  // loopback: the slot's previous send must be received before its buffers are reused
         if (!x->lb_sent[slot]->received)
             return tri_internal_fail(TRI_E_STATE, "tri_xfer loopback: the display has not received this slot's previous frame");
-        XH(hipStreamWaitEvent(s, x->lb_sent[slot]->consumed, 0));
+        TRI_HIP_TRY(hipStreamWaitEvent(s, x->lb_sent[slot]->consumed, 0));
         x->lb_sent[slot].reset();
     }
     if (ctx) {
@@ -364,18 +356,18 @@ int tri_xfer_frame(tri_xfer* x, uint32_t slot, tri_ctx* ctx, void* depth, const 
     // fewer communicators than slots: a communicator's operations on another stream are fenced behind its last ones
     const bool shared = x->xc.size() < x->nbuf;
     if (shared) {
-        if (!xc->after) XH(hipEventCreateWithFlags(&xc->after, hipEventDisableTiming));
-        if (xc->last && xc->last != s) XH(hipStreamWaitEvent(s, xc->after, 0));
+        if (!xc->after) TRI_HIP_TRY(hipEventCreateWithFlags(&xc->after, hipEventDisableTiming));
+        if (xc->last && xc->last != s) TRI_HIP_TRY(hipStreamWaitEvent(s, xc->after, 0));
     }
     ncclComm_t comm = xc->comm;
     if (!disp) {
         const void* src = frame;
         const uint64_t px = band_pixels(x, me);
         if (x->fmt == TRI_GROUP_FMT_DBP) {
-            XH(tri_launch_dbp_pack(frame, px, x->alpha, x->stage[slot], x->slot_bytes, x->flags, s));
+            TRI_HIP_TRY(tri_launch_dbp_pack(frame, px, x->alpha, x->stage[slot], x->slot_bytes, x->flags, s));
             src = x->stage[slot];
         } else if (x->fmt == TRI_GROUP_FMT_BGR24) {
-            XH(tri_launch_pack_bgr24(frame, x->stage[slot], px, x->alpha, x->flags, s,
+            TRI_HIP_TRY(tri_launch_pack_bgr24(frame, x->stage[slot], px, x->alpha, x->flags, s,
                                      reinterpret_cast<uint32_t*>(x->stage[slot] + bgr24_trailer(px))));
             src = x->stage[slot];
         }
@@ -410,23 +402,23 @@ int tri_xfer_frame(tri_xfer* x, uint32_t slot, tri_ctx* ctx, void* depth, const 
                 to[k] = frame + (size_t)x->y[r] * x->W;
                 npx[k] = band_pixels(x, r);
                 if (++k == TRI_DBP_MAX_BANDS) {
-                    XH(tri_launch_dbp_unpack_bands(from, to, npx, k, x->alpha, x->slot_bytes, s, x->flags));
+                    TRI_HIP_TRY(tri_launch_dbp_unpack_bands(from, to, npx, k, x->alpha, x->slot_bytes, s, x->flags));
                     k = 0;
                 }
             }
-            if (k) XH(tri_launch_dbp_unpack_bands(from, to, npx, k, x->alpha, x->slot_bytes, s, x->flags));
+            if (k) TRI_HIP_TRY(tri_launch_dbp_unpack_bands(from, to, npx, k, x->alpha, x->slot_bytes, s, x->flags));
         } else if (x->fmt == TRI_GROUP_FMT_BGR24) {
             for (uint32_t r = 0; r < N; ++r)
                 if (r != me) {
                     const uint64_t px = band_pixels(x, r);
-                    XH(tri_launch_unpack_bgr24(x->rx[slot][r], frame + (size_t)x->y[r] * x->W, px, x->alpha, s,
+                    TRI_HIP_TRY(tri_launch_unpack_bgr24(x->rx[slot][r], frame + (size_t)x->y[r] * x->W, px, x->alpha, s,
                                                reinterpret_cast<const uint32_t*>(x->rx[slot][r] + bgr24_trailer(px)),
                                                x->flags));
                 }
         }
     }
     if (shared) {
-        XH(hipEventRecord(xc->after, s));
+        TRI_HIP_TRY(hipEventRecord(xc->after, s));
         xc->last = s;
     }
     return TRI_OK;
@@ -440,7 +432,7 @@ int tri_xfer_set_timeout(tri_xfer* x, uint32_t timeout_ms) {
 
 int tri_xfer_wait(tri_xfer* x) {
     if (!x) return tri_internal_fail(TRI_E_INVALID, "tri_xfer_wait: null exchange");
-    XH(hipSetDevice(x->device));
+    TRI_HIP_TRY(hipSetDevice(x->device));
     // every slot's stream, polled against the deadline together with the communicators' asynchronous errors: a
     // transfer whose peer never comes (a dead or diverged rank) must end the caller, not hang the whole job
     const auto t0 = std::chrono::steady_clock::now();
@@ -449,7 +441,7 @@ int tri_xfer_wait(tri_xfer* x) {
         for (;;) {
             const hipError_t e = hipStreamQuery(st);
             if (e == hipSuccess) break;
-            if (e != hipErrorNotReady) return xfail(e, "tri_xfer_wait: hipStreamQuery");
+            if (e != hipErrorNotReady) return tri_hip_fail(e, "tri_xfer_wait: hipStreamQuery");
             for (tri_xfer_comm* c : x->xc) {
                 ncclResult_t ae = ncclSuccess;
                 if (c->comm && ncclCommGetAsyncError(c->comm, &ae) == ncclSuccess && ae != ncclSuccess && ae != ncclInProgress) {
@@ -475,7 +467,7 @@ int tri_xfer_synchronize(tri_xfer* x) {
     const int rc = tri_xfer_wait(x);
     if (rc) return rc;
     uint32_t f[2] = {0, 0};
-    XH(hipMemcpy(f, x->flags, 8, hipMemcpyDeviceToHost));
+    TRI_HIP_TRY(hipMemcpy(f, x->flags, 8, hipMemcpyDeviceToHost));
     if (f[0] & 1u) return tri_internal_fail(TRI_E_STATE, "tri_xfer: a band's alpha was not the proven value (lossy packed transfer)");
     if (f[0] & 2u) return tri_internal_fail(TRI_E_OVERFLOW, "tri_xfer: a band outgrew the agreed dbp slot size (lossy transfer)");
     return TRI_OK;
@@ -500,7 +492,7 @@ int tri_xfer_info(tri_xfer* x, uint64_t* sent_bytes, uint64_t* received_bytes, u
         const int rc = tri_xfer_synchronize(x);
         if (rc && rc != TRI_E_STATE && rc != TRI_E_OVERFLOW) return rc;
         uint32_t f[2] = {0, 0};
-        XH(hipMemcpy(f, x->flags, 8, hipMemcpyDeviceToHost));
+        TRI_HIP_TRY(hipMemcpy(f, x->flags, 8, hipMemcpyDeviceToHost));
         *max_slot_bytes = f[1];
     }
     return TRI_OK;

@@ -78,6 +78,37 @@ def test_fails_loudly_without_gpu(hiplib):
     assert not ctx.value
 
 
+def test_every_create_resolves_its_device_after_its_arguments(hiplib):
+    """Without a HIP device each of the six creates fails the same way, TRI_E_HIP with a message that names the device
+    and a null handle, and only once its own arguments are in order: a bad argument is TRI_E_INVALID on every host."""
+    from tests_gpu_probe import gpu_present
+
+    if gpu_present():
+        pytest.skip("a GPU is present")
+    cfg = abi.TriConfig(64, 64, 0, 0, -1, 0)
+    atlas = (C.c_uint8 * (8 * 8))()
+    creates = {
+        "tri_create": lambda out: hiplib.tri_create(C.byref(cfg), out),
+        "tri_geometry_create": lambda out: hiplib.tri_geometry_create(-1, out),
+        "tri_font_create": lambda out: hiplib.tri_font_create(-1, atlas, 8, 8, out),
+        "tri_animset_create": lambda out: hiplib.tri_animset_create(-1, out),
+        "tri_recorder_create": lambda out: hiplib.tri_recorder_create(-1, 64, 64, 2, out),
+        "tri_framegrab_create": lambda out: hiplib.tri_framegrab_create(-1, 64, 64, 2, abi.TRI_GRAB_HOST_COPY, out),
+    }
+    for name, create in creates.items():
+        handle = C.c_void_p(1)
+        assert create(C.byref(handle)) == abi.TRI_E_HIP, name
+        message = hiplib.tri_last_error()
+        assert b"device" in message and name.encode() in message, (name, message)
+        assert not handle.value, name
+    handle = C.c_void_p()
+    cfg = abi.TriConfig(0, 64, 0, 0, -1, 0)
+    assert hiplib.tri_create(C.byref(cfg), C.byref(handle)) == abi.TRI_E_INVALID
+    assert hiplib.tri_font_create(-1, atlas, 0, 8, C.byref(handle)) == abi.TRI_E_INVALID
+    assert hiplib.tri_recorder_create(-1, 0, 64, 2, C.byref(handle)) == abi.TRI_E_INVALID
+    assert hiplib.tri_framegrab_create(-1, 0, 64, 2, 0, C.byref(handle)) == abi.TRI_E_INVALID
+
+
 def test_invalid_arguments_are_rejected(hiplib):
     cfg = abi.TriConfig(0, 64, 0, 0, -1, 0)
     ctx = C.c_void_p()

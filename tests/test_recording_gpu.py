@@ -170,6 +170,36 @@ def test_recorder_states(hiplib):
     assert hiplib.tri_recorder_destroy(None) == abi.TRI_OK
 
 
+def test_rings_are_destroyed_with_captures_in_flight(hiplib):
+    """The documented teardown (Renderer::StopRecording, Renderer::DropGrab): a recorder, a grab with the host copy and a
+    grab without it are destroyed behind two captures that nobody waited for or released. The context is unharmed: it
+    synchronises, and its next frame is the one a fresh context renders."""
+    from trident_raster import abi, raster, scenes
+
+    frames = [sc.c1_cube_skybox(f) for f in (0, 1)]
+    with raster.TriRaster(640, 480) as fresh:
+        scenes.load_scene(fresh, frames[1])
+        fresh.render_frame()
+        want_col, want_dep = fresh.readback()
+    rings = [(lambda: raster.TriRecorder(640, 480, 2), "_r", hiplib.tri_recorder_destroy),
+             (lambda: raster.FrameGrab(640, 480, 2, host_copy=True), "_g", hiplib.tri_framegrab_destroy),
+             (lambda: raster.FrameGrab(640, 480, 2), "_g", hiplib.tri_framegrab_destroy)]
+    for make, attr, destroy in rings:
+        with raster.TriRaster(640, 480) as r:
+            ring = make()
+            for slot, s in enumerate(frames):
+                scenes.load_scene(r, s)
+                r.render()
+                ring.capture(slot, r)
+            handle = getattr(ring, attr)
+            setattr(ring, attr, None)  # the wrapper must not destroy it again
+            assert destroy(handle) == abi.TRI_OK
+            r.synchronize()
+            r.render_frame()
+            col, dep = r.readback()
+            assert np.array_equal(col, want_col) and np.array_equal(dep, want_dep)
+
+
 # ---- the shim, end to end -------------------------------------------------------------------------------------
 
 def _scene_app(app_mod, w1=321, h1=201):

@@ -11,8 +11,8 @@ rm -rf $out/obj_$name
 mkdir -p $src/pkg/csrc $src/include $out/obj_$name
 units=""
 for f in raster_kernels.hip raster_plain.hip vertex_stage.hip tri_raster_capi.hip tri_group.hip band_codec.hip tri_xfer.hip \
-         record_yuv.hip tri_record.hip frame_tensor.hip tri_framegrab.hip text_overlay.hip raster_common.h raster_launch.h \
-         raster_device.h raster_bin.h; do
+         record_yuv.hip tri_record.hip frame_tensor.hip tri_framegrab.hip tri_capture.hip text_overlay.hip pose_eval.hip \
+         raster_common.h raster_launch.h capi_util.h raster_device.h raster_bin.h; do
   if git cat-file -e $rev:3d-renderer_amd/csrc/$f 2>/dev/null; then
     git show $rev:3d-renderer_amd/csrc/$f > $src/pkg/csrc/$f
     case $f in *.hip) units="$units ${f%.hip}";; esac

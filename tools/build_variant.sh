@@ -6,8 +6,8 @@ set -e
 cd "$(dirname "$0")/../3d-renderer_amd"
 name=$1; shift
 mkdir -p lib/variants/obj_$name
-for s in raster_kernels raster_plain vertex_stage tri_raster_capi tri_group band_codec tri_xfer record_yuv tri_record \
-         frame_tensor tri_framegrab text_overlay; do
+for s in raster_kernels raster_plain vertex_stage tri_raster_capi tri_group band_codec tri_xfer record_yuv \
+         frame_tensor tri_capture text_overlay pose_eval; do
   extra=""; [ $s = raster_plain ] && extra="-fno-slp-vectorize -mllvm --amdgpu-sched-strategy=max-ilp"
   [ $s = vertex_stage ] && extra="${VERTEX_SCHED-}"  # (the Makefile default: the default scheduler)
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -Wno-unused-function -mllvm -amdgpu-kernarg-preload-count=2 $extra "$@" \
