@@ -201,6 +201,7 @@ int tri_internal_animset_device(const tri_animset* set);
 struct TriPoseScratch {
     std::vector<std::pair<uint32_t, uint32_t>> spans;  // {first matrix, matrices}, sorted for the overlap test
     std::vector<uint32_t> bones;
+    std::vector<tri_pose_instance> plain;  // tri_pose_graph_check's: its instances as tri_pose_check takes them
 };
 int tri_pose_check(const tri_animset* set, const tri_pose_instance* instances, uint32_t count, uint32_t prefix,
                    uint32_t* extent, TriPoseScratch& scratch);
@@ -208,5 +209,14 @@ int tri_pose_check(const tri_animset* set, const tri_pose_instance* instances, u
 // LDS is sized by it); palette: at least *extent matrices.
 hipError_t tri_launch_pose(const tri_animset* set, const tri_pose_instance* d_instances, uint32_t count,
                            uint32_t lds_bones, float* palette, hipStream_t stream);
+// The same for a tri_pose_graph call: tri_pose_check on the instances' skeletons and palette slices, then every
+// program's op range, stack discipline, limits, ops, clips and masks. Every index k_pose_graph uses is checked here.
+int tri_pose_graph_check(const tri_animset* set, const tri_pose_graph_instance* instances, uint32_t count,
+                         const tri_pose_op* ops, uint32_t op_count, uint32_t prefix, uint32_t* extent,
+                         TriPoseScratch& scratch);
+// d_instances as for tri_launch_pose; d_ops: the operations their op_first index, on the same device.
+hipError_t tri_launch_pose_graph(const tri_animset* set, const tri_pose_graph_instance* d_instances,
+                                 const tri_pose_op* d_ops, uint32_t count, uint32_t lds_bones, float* palette,
+                                 hipStream_t stream);
 // The matrices of a context's uploaded palette prefix.
 uint32_t tri_internal_pose_prefix(tri_ctx* ctx);

@@ -362,6 +362,31 @@ int tri_group_pose_palette(tri_group* g, tri_animset* const* sets, const tri_pos
     return TRI_OK;
 }
 
+int tri_group_pose_graph(tri_group* g, tri_animset* const* sets, const tri_pose_graph_instance* inst, uint32_t n,
+                         const tri_pose_op* ops, uint32_t nops) {
+    if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_pose_graph: null group");
+    if (!n) return each(g, [&](tri_ctx* c) { return tri_pose_graph(c, nullptr, nullptr, 0, nullptr, 0); });
+    if (!sets || !inst || !ops) return tri_internal_fail(TRI_E_INVALID, "tri_group_pose_graph: null argument");
+    // as tri_group_pose_palette: every band's set resolved and its check passed before the first band enqueues anything
+    std::vector<tri_animset*> use(g->n, nullptr);
+    for (uint32_t r = 0; r < g->n; ++r) {
+        for (size_t i = 0; i < g->udev.size() && !use[r]; ++i)
+            if (sets[i] && tri_internal_animset_device(sets[i]) == g->dev[r]) use[r] = sets[i];
+        if (!use[r]) return tri_internal_fail(TRI_E_INVALID, "tri_group_pose_graph: no set on a band's device");
+    }
+    TriPoseScratch scratch;
+    for (uint32_t r = 0; r < g->n; ++r) {
+        uint32_t extent = 0;
+        const int rc = tri_pose_graph_check(use[r], inst, n, ops, nops, tri_internal_pose_prefix(g->ctx[r]), &extent, scratch);
+        if (rc) return rc;
+    }
+    for (uint32_t r = 0; r < g->n; ++r) {
+        const int rc = tri_pose_graph(g->ctx[r], use[r], inst, n, ops, nops);
+        if (rc) return rc;
+    }
+    return TRI_OK;
+}
+
 int tri_group_render(tri_group* g) {
     if (!g) return tri_internal_fail(TRI_E_INVALID, "tri_group_render: null group");
     const int32_t ddev = g->dev[g->display];

@@ -141,6 +141,16 @@ struct tri_ctx {
     };
     PoseStage pose_stage[4];
     uint32_t pose_next = 0;
+    // tri_pose_graph's ring: a call's instance records followed by its operations (16-B records both), fenced alike
+    struct GraphStage {
+        uint4* h = nullptr;
+        uint4* d = nullptr;
+        size_t cap = 0;  // records
+        hipEvent_t done = nullptr;
+        bool busy = false;
+    };
+    GraphStage graph_stage[4];
+    uint32_t graph_next = 0;
     TriPoseScratch pose_scratch;  // tri_pose_check's, kept between calls
 
     // per frame
@@ -1043,6 +1053,11 @@ int tri_destroy(tri_ctx* c) {
         if (ps.h) (void)hipHostFree(ps.h);
         if (ps.done) (void)hipEventDestroy(ps.done);
     }
+    for (auto& gs : c->graph_stage) {
+        f(gs.d);
+        if (gs.h) (void)hipHostFree(gs.h);
+        if (gs.done) (void)hipEventDestroy(gs.done);
+    }
     if (c->h_text) (void)hipHostFree(c->h_text);
     if (c->text_free) (void)hipEventDestroy(c->text_free);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -1176,6 +1191,33 @@ int tri_upload_bone_palette(tri_ctx* c, const float* m, uint32_t n) {
     return TRI_OK;
 }
 
+// Room for `extent` matrices in the palette, keeping the prefix: frames in flight read the old palette, so growing
+// synchronises.
+static int pose_reserve_palette(tri_ctx* c, uint32_t extent, const char* who) {
+    if (16ull * extent <= c->cap_bones && c->d_bones) return TRI_OK;
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+    float* grown = nullptr;
+    const size_t cap = std::max<size_t>(16ull * extent, 2 * c->cap_bones);
+    TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(float)));
+    hipError_t e = hipMemset(grown, 0, cap * sizeof(float));
+    if (e == hipSuccess && c->nbones_prefix)
+        e = hipMemcpy(grown, c->d_bones, 64ull * c->nbones_prefix, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();  // null-stream work: complete before the context's stream reads it
+    if (e != hipSuccess) {
+        (void)hipFree(grown);
+        return fail(TRI_E_HIP, "%s: growing the palette: %s", who, hipGetErrorString(e));
+    }
+    if (c->d_bones) TRI_HIP_TRY(hipFree(c->d_bones));
+    c->d_bones = grown;
+    c->cap_bones = cap;
+    return TRI_OK;
+}
+
+// The skeleton-size groups of the pose kernels, one launch each: a workgroup's LDS is sized by its launch's largest
+// skeleton, and a 256-bone instance should not make every 20-bone one reserve 40 KiB.
+static const uint32_t kPoseBucket[3] = {32, 128, TRI_POSE_MAX_BONES};
+static inline int pose_bucket(uint32_t bones) { return bones <= kPoseBucket[0] ? 0 : bones <= kPoseBucket[1] ? 1 : 2; }
+
 int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst, uint32_t n) {
     if (!c) return fail(TRI_E_INVALID, "tri_pose_palette: null context");
     if (!n) {
@@ -1188,24 +1230,7 @@ int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst
     int rc = tri_pose_check(set, inst, n, c->nbones_prefix, &extent, c->pose_scratch);
     if (rc) return rc;
     if ((rc = make_current(c))) return rc;
-    if (16ull * extent > c->cap_bones || !c->d_bones) {
-        // grow, keeping the prefix: frames in flight read the old palette
-        TRI_HIP_TRY(hipStreamSynchronize(c->stream));
-        float* grown = nullptr;
-        const size_t cap = std::max<size_t>(16ull * extent, 2 * c->cap_bones);
-        TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&grown), cap * sizeof(float)));
-        hipError_t e = hipMemset(grown, 0, cap * sizeof(float));
-        if (e == hipSuccess && c->nbones_prefix)
-            e = hipMemcpy(grown, c->d_bones, 64ull * c->nbones_prefix, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess) e = hipDeviceSynchronize();  // null-stream work: complete before the context's stream reads it
-        if (e != hipSuccess) {
-            (void)hipFree(grown);
-            return fail(TRI_E_HIP, "tri_pose_palette: growing the palette: %s", hipGetErrorString(e));
-        }
-        if (c->d_bones) TRI_HIP_TRY(hipFree(c->d_bones));
-        c->d_bones = grown;
-        c->cap_bones = cap;
-    }
+    if ((rc = pose_reserve_palette(c, extent, "tri_pose_palette"))) return rc;
     tri_ctx::PoseStage& ps = c->pose_stage[c->pose_next];
     if (ps.busy) TRI_HIP_TRY(hipEventSynchronize(ps.done));  // four calls back: long complete unless the device is that far behind
     ps.busy = false;
@@ -1221,22 +1246,74 @@ int tri_pose_palette(tri_ctx* c, tri_animset* set, const tri_pose_instance* inst
         ps.cap = cap;
     }
     if (!ps.done) TRI_HIP_TRY(hipEventCreateWithFlags(&ps.done, hipEventDisableTiming));
-    // the records grouped by skeleton size, one launch per group: a workgroup's LDS is sized by its launch's largest
-    // skeleton, and a 256-bone instance should not make every 20-bone one reserve 40 KiB
-    static const uint32_t kBucket[3] = {32, 128, TRI_POSE_MAX_BONES};
+    // the records grouped by skeleton size, one launch per group
     const std::vector<uint32_t>& bones = c->pose_scratch.bones;
     uint32_t first[4] = {0, 0, 0, 0};
-    for (uint32_t i = 0; i < n; ++i) ++first[(bones[i] <= kBucket[0] ? 0 : bones[i] <= kBucket[1] ? 1 : 2) + 1];
+    for (uint32_t i = 0; i < n; ++i) ++first[pose_bucket(bones[i]) + 1];
     first[2] += first[1];
     first[3] += first[2];
     uint32_t at[3] = {0, first[1], first[2]};
-    for (uint32_t i = 0; i < n; ++i) ps.h[at[bones[i] <= kBucket[0] ? 0 : bones[i] <= kBucket[1] ? 1 : 2]++] = inst[i];
+    for (uint32_t i = 0; i < n; ++i) ps.h[at[pose_bucket(bones[i])]++] = inst[i];
     TRI_HIP_TRY(hipMemcpyAsync(ps.d, ps.h, (size_t)n * sizeof(tri_pose_instance), hipMemcpyHostToDevice, c->stream));
     for (int b = 0; b < 3; ++b)
-        TRI_HIP_TRY(tri_launch_pose(set, ps.d + first[b], first[b + 1] - first[b], kBucket[b], c->d_bones, c->stream));
+        TRI_HIP_TRY(tri_launch_pose(set, ps.d + first[b], first[b + 1] - first[b], kPoseBucket[b], c->d_bones, c->stream));
     TRI_HIP_TRY(hipEventRecord(ps.done, c->stream));
     ps.busy = true;
     c->pose_next = (c->pose_next + 1) % 4;
+    c->nbones = extent;
+    return TRI_OK;
+}
+
+int tri_pose_graph(tri_ctx* c, tri_animset* set, const tri_pose_graph_instance* inst, uint32_t n, const tri_pose_op* ops,
+                   uint32_t nops) {
+    if (!c) return fail(TRI_E_INVALID, "tri_pose_graph: null context");
+    if (!n) {
+        c->nbones = c->nbones_prefix;
+        return TRI_OK;
+    }
+    if (!set || !inst || !ops) return fail(TRI_E_INVALID, "tri_pose_graph: null argument");
+    if (tri_internal_animset_device(set) != c->device) return fail(TRI_E_INVALID, "tri_pose_graph: the set is on another device");
+    uint32_t extent = 0;
+    int rc = tri_pose_graph_check(set, inst, n, ops, nops, c->nbones_prefix, &extent, c->pose_scratch);
+    if (rc) return rc;
+    if ((rc = make_current(c))) return rc;
+    if ((rc = pose_reserve_palette(c, extent, "tri_pose_graph"))) return rc;
+    tri_ctx::GraphStage& gs = c->graph_stage[c->graph_next];
+    if (gs.busy) TRI_HIP_TRY(hipEventSynchronize(gs.done));  // four calls back
+    gs.busy = false;
+    static_assert(sizeof(tri_pose_graph_instance) == sizeof(uint4) && sizeof(tri_pose_op) == sizeof(uint4), "16-B records");
+    const size_t records = (size_t)n + nops;
+    if (records > gs.cap) {
+        if (gs.h) TRI_HIP_TRY(hipHostFree(gs.h));
+        gs.h = nullptr;
+        if (gs.d) TRI_HIP_TRY(hipFree(gs.d));
+        gs.d = nullptr;
+        gs.cap = 0;
+        const size_t cap = std::max<size_t>(records, 512);
+        TRI_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&gs.h), cap * sizeof(uint4), hipHostMallocDefault));
+        TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&gs.d), cap * sizeof(uint4)));
+        gs.cap = cap;
+    }
+    if (!gs.done) TRI_HIP_TRY(hipEventCreateWithFlags(&gs.done, hipEventDisableTiming));
+    // the instances grouped by skeleton size, then the operations as given (op_first stays an index into them)
+    const std::vector<uint32_t>& bones = c->pose_scratch.bones;
+    uint32_t first[4] = {0, 0, 0, 0};
+    for (uint32_t i = 0; i < n; ++i) ++first[pose_bucket(bones[i]) + 1];
+    first[2] += first[1];
+    first[3] += first[2];
+    uint32_t at[3] = {0, first[1], first[2]};
+    tri_pose_graph_instance* h_inst = reinterpret_cast<tri_pose_graph_instance*>(gs.h);
+    for (uint32_t i = 0; i < n; ++i) h_inst[at[pose_bucket(bones[i])]++] = inst[i];
+    std::memcpy(gs.h + n, ops, (size_t)nops * sizeof(tri_pose_op));
+    TRI_HIP_TRY(hipMemcpyAsync(gs.d, gs.h, records * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+    const tri_pose_graph_instance* d_inst = reinterpret_cast<const tri_pose_graph_instance*>(gs.d);
+    const tri_pose_op* d_ops = reinterpret_cast<const tri_pose_op*>(gs.d + n);
+    for (int b = 0; b < 3; ++b)
+        TRI_HIP_TRY(tri_launch_pose_graph(set, d_inst + first[b], d_ops, first[b + 1] - first[b], kPoseBucket[b], c->d_bones,
+                                          c->stream));
+    TRI_HIP_TRY(hipEventRecord(gs.done, c->stream));
+    gs.busy = true;
+    c->graph_next = (c->graph_next + 1) % 4;
     c->nbones = extent;
     return TRI_OK;
 }

@@ -3,7 +3,7 @@
 // are the reference's: they are the interface. The pose rules the player evaluates are stated once in
 // include/tri_raster.h ("skeletal poses evaluated on the device"); this is their float32 CPU restatement, with the
 // operation order of the device kernel (the shim builds with -ffp-contract=off).
-// Not restated: the state machine and blend tree.
+// Also here: the pose-space types (Animation/AnimationPose.h) and the pose programs both pose evaluators interpret.
 #pragma once
 
 #include <cstddef>
@@ -160,6 +160,65 @@ private:
     bool m_IsPlaying = true;
     std::vector<glm::mat4> m_PoseMatrices{};
 };
+
+// ---- pose space (Animation/AnimationPose.h) ----
+// A pose as decomposed TRS values per bone, masks of per-bone weights, and the arithmetic on them. The rules are
+// include/tri_raster.h's ("Pose space"); this is their float32 restatement in the device kernel's operation order
+// (k_pose_graph, csrc/pose_eval.hip): where neither side evaluates sin / acos the two agree bit for bit.
+struct AnimationPose {
+    void Resize(size_t boneCount);  // new bones: translation 0, rotation identity, scale 1
+
+    std::vector<glm::vec3> m_Translations{};
+    std::vector<glm::quat> m_Rotations{};
+    std::vector<glm::vec3> m_Scales{};
+};
+
+struct AnimationMask {
+    void Resize(size_t boneCount);             // pads with 1.0, truncates
+    float GetWeight(size_t boneIndex) const;   // 1.0 beyond the weights
+
+    std::vector<float> m_BoneWeights{};
+};
+
+namespace AnimationPoseUtilities {
+AnimationPose BuildRestPose(const Skeleton& skeleton);
+AnimationPose SampleClipPose(const Skeleton& skeleton, const AnimationClip& clip, float sampleTimeSeconds);
+// Both run over min(sizes) bones: an empty pose on either side leaves the base as it is.
+void BlendPose(AnimationPose& basePose, const AnimationPose& targetPose, float blendWeight, const AnimationMask* mask);
+void AdditivePose(AnimationPose& basePose, const AnimationPose& additivePose, float additiveWeight, const AnimationMask* mask);
+// One matrix per bone. A pose shorter than the skeleton is completed with the rest pose's values; a parent cycle the
+// traversal would reach gives identities (the reference would not return).
+std::vector<glm::mat4> ComposeSkinningMatrices(const Skeleton& skeleton, const AnimationPose& pose);
+}  // namespace AnimationPoseUtilities
+
+// ---- pose programs ----
+// What one update of an animation graph means, as the postfix program of include/tri_raster.h (tri_pose_op): the
+// state machine emits it, EvaluatePoseProgram is its CPU meaning and tri_pose_graph its device meaning. m_A of a Clip
+// indexes the animation library's clips, m_A of a Blend / Add indexes m_Masks (or is s_NoMask).
+struct PoseOp {
+    enum Kind : uint32_t { Rest = 0, Clip = 1, Blend = 2, Add = 3 };
+    static constexpr uint32_t s_NoMask = 0xFFFFFFFFu;
+    uint32_t m_Op = Rest;
+    uint32_t m_A = 0;
+    float m_F = 0.0f;
+};
+
+struct PoseProgram {
+    static constexpr size_t s_MaxOps = 64;   // TRI_POSE_MAX_OPS
+    static constexpr size_t s_MaxStack = 8;  // TRI_POSE_STACK
+    std::vector<PoseOp> m_Ops{};
+    std::vector<AnimationMask> m_Masks{};
+
+    // The stack discipline alone (never below two entries for a Blend / Add, one entry at the end, known ops).
+    bool WellFormed() const;
+    // WellFormed within the device's two limits.
+    bool FitsDevice() const;
+};
+
+// The program's final pose; false (outPose untouched) for a program that is not WellFormed or names a clip or mask
+// that does not exist. No limit on depth or length here.
+bool EvaluatePoseProgram(const Skeleton& skeleton, const std::vector<AnimationClip>* clips, const PoseProgram& program,
+                         AnimationPose& outPose);
 
 }  // namespace Animation
 }  // namespace Trident

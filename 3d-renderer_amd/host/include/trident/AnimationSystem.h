@@ -1,10 +1,13 @@
 // AnimationSystem.h — ECS::AnimationSystem (ECS/AnimationSystem.h, ECS/Components/AnimationSystem.cpp:23-164): every
 // entity with an AnimationComponent and a MeshComponent has its cached handles refreshed, its clip time advanced and,
-// unless poses are evaluated on the device, its m_BoneMatrices written by the CPU player. State machines are not
-// restated: every component plays its clip directly.
+// unless poses are evaluated on the device, its m_BoneMatrices written by the CPU player. A component with an
+// m_StateMachine is driven by it instead (:77-86, :126-137): the machine takes the component's handles, updates by the
+// frame's delta (0 while m_IsPlaying is false) and its pose becomes m_BoneMatrices. With a renderer that poses on the
+// device (Renderer::PosesOnDevice) the machine is only advanced: the renderer submits the program the update emitted.
 #pragma once
 
 #include "Animation.h"
+#include "AnimationStateMachine.h"
 #include "Scene.h"
 
 namespace Trident {

@@ -18,6 +18,7 @@
 #include "../../../../include/tri_raster.h"
 #include "Camera.h"
 #include "Scene.h"
+#include "AnimationStateMachine.h"
 #include "FrameDatasetRecorder.h"
 #include "VideoEncoder.h"
 #include "TextRenderer.h"
@@ -325,10 +326,12 @@ private:
         size_t m_Skeleton, m_Animation, m_Clip;  // asset handles and the clip index
         float m_Time;
         uint32_t m_Offset;
+        const Animation::PoseProgram* m_Program;  // a state machine's program of this update, or null: the clip at m_Time
     };
     struct PoseAssetOnDevice {
         uint32_t m_Skeleton = 0;
         std::vector<uint32_t> m_Clips;
+        std::map<std::vector<float>, uint32_t> m_Masks;  // masks on the device by content (padded to the bone count)
     };
     struct PoseDeviceSet {
         tri_animset* m_Set = nullptr;
@@ -342,8 +345,11 @@ private:
     uint64_t m_PoseSetsGeneration = 0;                // ... and the one the devices' sets were filled under
     std::map<int32_t, PoseDeviceSet> m_PoseSets;
     std::vector<tri_pose_instance> m_PoseInstances;
+    std::vector<tri_pose_graph_instance> m_PoseGraphInstances;  // a frame with at least one program: every posed draw
+    std::vector<tri_pose_op> m_PoseOps;
     bool SubmitPoses(ViewportContext& context);
-    const PoseAssetOnDevice* PoseAssetOn(int32_t device, size_t skeleton, size_t animation);
+    PoseAssetOnDevice* PoseAssetOn(int32_t device, size_t skeleton, size_t animation);
+    bool SubmitPoseGraph(ViewportContext& context, const std::vector<int32_t>& devices);
     void DropPoseSets();
     size_t m_PrimitiveMeshIndices[3] = {SIZE_MAX, SIZE_MAX, SIZE_MAX};
     bool m_IsUploadingMeshes = false;

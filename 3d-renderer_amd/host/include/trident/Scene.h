@@ -31,6 +31,10 @@ static_assert(sizeof(Vertex) == 100, "Vertex must keep Trident's 100-byte stride
 
 namespace Trident {
 
+namespace Animation {
+class AnimationStateMachine;  // AnimationStateMachine.h
+}
+
 namespace Geometry {
 struct Material {
     glm::vec4 BaseColorFactor{1.0f, 1.0f, 1.0f, 1.0f};
@@ -136,7 +140,7 @@ struct SpriteComponent {
 // AnimationComponent (ECS/Components/AnimationComponent.h:29-73): the playback state ECS::AnimationSystem advances
 // (AnimationSystem.h), the cached asset handles, and the skinning palette the renderer reads (m_BoneMatrices,
 // column-major mat4s: written by the CPU animation system each frame, or by any other code). The reference's
-// m_StateMachine does not exist here (the state machine and blend tree are not restated).
+// m_StateMachine, when set, drives the pose instead of the clip fields (AnimationStateMachine.h).
 struct AnimationComponent {
     std::string m_SkeletonAssetId{};
     std::string m_AnimationAssetId{};
@@ -146,6 +150,7 @@ struct AnimationComponent {
     bool m_IsLooping{true};
     bool m_IsPlaying{true};
     std::vector<glm::mat4> m_BoneMatrices{};
+    std::shared_ptr<Animation::AnimationStateMachine> m_StateMachine{};
 
     size_t m_SkeletonAssetHandle{std::numeric_limits<size_t>::max()};
     size_t m_AnimationAssetHandle{std::numeric_limits<size_t>::max()};

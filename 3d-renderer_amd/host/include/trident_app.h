@@ -250,6 +250,60 @@ int trident_anim_resolve_channels(uint64_t handle, uint32_t clip_index, int32_t*
  * gives the fallback pose, one identity. */
 int trident_anim_evaluate(uint64_t handle, uint32_t clip_index, float time, float* out, uint32_t capacity,
                           uint32_t* count);
+/* Animation::EvaluatePoseProgram + ComposeSkinningMatrices on the asset: the float32 CPU meaning of a pose program
+ * (include/tri_raster.h). A CLIP's `a` indexes the asset's clips; a BLEND / ADD's `a` indexes the masks given here
+ * (mask m holds mask_counts[m] weights, concatenated in mask_weights) or is TRI_POSE_NO_MASK. No limit on length or
+ * depth. TRI_E_INVALID: an unknown handle, a program that breaks the stack discipline, an unknown op, clip or mask. */
+int trident_anim_eval_program(uint64_t handle, const tri_pose_op* ops, uint32_t op_count, const float* mask_weights,
+                              const uint32_t* mask_counts, uint32_t mask_count, float* out, uint32_t capacity,
+                              uint32_t* count);
+/* ---- animation state machines and blend trees (host/include/trident/AnimationStateMachine.h), no GPU ----
+ * Machines and nodes are named by ids (never 0). A node id is consumed when the node becomes a child of a blend node
+ * or the root of a state; node id 0 stands for "no node". */
+enum { TRIDENT_SM_FLOAT = 0, TRIDENT_SM_BOOL = 1, TRIDENT_SM_INTEGER = 2, TRIDENT_SM_TRIGGER = 3 };
+enum { TRIDENT_SM_EQUALS = 0, TRIDENT_SM_NOT_EQUALS, TRIDENT_SM_GREATER, TRIDENT_SM_LESS, TRIDENT_SM_GREATER_EQUAL,
+       TRIDENT_SM_LESS_EQUAL, TRIDENT_SM_TRIGGERED };
+typedef struct trident_sm_condition {
+    const char* parameter;
+    int32_t comparison; /* TRIDENT_SM_EQUALS .. TRIDENT_SM_TRIGGERED */
+    float float_value;
+    int32_t int_value;
+    int32_t bool_value;
+} trident_sm_condition;
+/* ClipNode (clip_index UINT32_MAX: no clip), BlendNode, BlendSpace1DNode; the parameter names may be NULL. */
+int trident_node_clip(uint32_t clip_index, int looping, float speed, const char* speed_parameter, uint64_t* out_node);
+int trident_node_blend(uint64_t first, uint64_t second, float weight, const char* weight_parameter, uint64_t* out_node);
+int trident_node_blend_space(const uint32_t* clip_indices, const float* positions, uint32_t count, float parameter_default,
+                             const char* parameter, uint64_t* out_node);
+int trident_node_destroy(uint64_t node);
+/* An AnimationStateMachine on the asset service with its two handles set (UINT64_MAX: invalid). */
+int trident_sm_create(uint64_t skeleton_handle, uint64_t library_handle, uint64_t* out_machine);
+int trident_sm_destroy(uint64_t machine);
+int trident_sm_set_handles(uint64_t machine, uint64_t skeleton_handle, uint64_t library_handle);
+/* add != 0: Add*Parameter(name, value); add == 0: Set*Parameter, and for a trigger FireTrigger (value != 0) or
+ * ResetTrigger (value == 0). Bool: value != 0; Integer: (int)value. */
+int trident_sm_parameter(uint64_t machine, const char* name, int type, float value, int add);
+/* TRI_E_INVALID for a parameter the machine does not have. */
+int trident_sm_get_parameter(uint64_t machine, const char* name, int* type, float* as_float, int* trigger_set);
+int trident_sm_add_layer(uint64_t machine, const char* name, float weight, int additive, uint32_t* out_layer);
+int trident_sm_set_layer_mask(uint64_t machine, uint32_t layer, const float* weights, uint32_t count);
+int trident_sm_set_layer_weight(uint64_t machine, uint32_t layer, float weight);
+int trident_sm_set_layer_entry(uint64_t machine, uint32_t layer, const char* state);
+int trident_sm_add_state(uint64_t machine, uint32_t layer, const char* name, uint64_t root_node);
+/* TRI_E_STATE: from_state is not a state of the layer (AddTransition's std::runtime_error). */
+int trident_sm_add_transition(uint64_t machine, uint32_t layer, const char* from_state, const char* target_state,
+                              int has_exit_time, float exit_time, float fade_duration,
+                              const trident_sm_condition* conditions, uint32_t condition_count);
+/* AnimationStateMachine::Update / CopyPose. */
+int trident_sm_update(uint64_t machine, float dt);
+int trident_sm_pose(uint64_t machine, float* out, uint32_t capacity, uint32_t* count);
+/* The pose program the last update emitted (a CLIP's `a`: the library's clip index; a BLEND / ADD's `a`: a mask of
+ * this program, read with trident_sm_program_mask, or TRI_POSE_NO_MASK). */
+int trident_sm_program(uint64_t machine, tri_pose_op* ops, uint32_t capacity, uint32_t* count, uint32_t* mask_count);
+int trident_sm_program_mask(uint64_t machine, uint32_t mask, float* weights, uint32_t capacity, uint32_t* count);
+/* A layer's runtime state: the names of its current and next state ("" for none; either may be NULL) and its timers. */
+int trident_sm_layer_state(uint64_t machine, uint32_t layer, char* current, char* next, uint32_t name_capacity,
+                           float* time_in_state, float* transition_elapsed, float* transition_duration);
 /* AnimationPlayer::Update on a player set to (time, speed, looping, playing): the time and play state after dt. */
 int trident_anim_advance(uint64_t handle, uint32_t clip_index, float time, float speed, int looping, int playing,
                          float dt, float* out_time, int* out_playing);
@@ -260,6 +314,9 @@ int trident_anim_advance(uint64_t handle, uint32_t clip_index, float time, float
 int trident_app_set_entity_animation(trident_app* app, uint32_t entity, const char* skeleton_asset_id,
                                      const char* animation_asset_id, const char* clip, float time, float speed,
                                      int looping, int playing);
+/* AnimationComponent::m_StateMachine of an entity that has the component: the machine of trident_sm_create (shared
+ * with its id, which keeps setting its parameters), or 0 to remove it. */
+int trident_app_set_entity_state_machine(trident_app* app, uint32_t entity, uint64_t machine);
 /* AnimationSystem::Update(registry, dt): poses into m_BoneMatrices, or time only in device mode. */
 int trident_app_update_animation(trident_app* app, float dt);
 /* AnimationSystem::InitialisePose of the entity's component. */

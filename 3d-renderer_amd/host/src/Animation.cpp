@@ -350,6 +350,77 @@ void AnimationPlayer::EvaluateAt(float sampleTimeSeconds) {
     EvaluatePose(sampleTimeSeconds);
 }
 
+namespace {
+
+// A clip's channels applied in order to per-bone values that hold the defaults.
+void SampleChannels(const Skeleton& skeleton, const AnimationClip& clip, float t, std::vector<TransformDecomposition>& value) {
+    const size_t n = value.size();
+    for (const TransformChannel& ch : clip.m_Channels) {
+        const int bone = ResolveChannelBoneIndex(ch, skeleton, clip.m_Name);
+        if (bone < 0 || (size_t)bone >= n) continue;
+        TransformDecomposition& v = value[(size_t)bone];
+        v.m_Translation = SampleVectorKeys(ch.m_TranslationKeys, t, v.m_Translation);
+        v.m_Rotation = SampleQuaternionKeys(ch.m_RotationKeys, t, v.m_Rotation);
+        v.m_Scale = SampleVectorKeys(ch.m_ScaleKeys, t, v.m_Scale);
+    }
+}
+
+// Local matrices, the traversal along the parents (a bone's children are the bones that name it as their parent), the
+// two fix-ups and global * inverse_bind. False for a cycle the reference would walk for ever.
+bool ComposeValues(const Skeleton& skeleton, const std::vector<TransformDecomposition>& value, std::vector<glm::mat4>& out) {
+    const size_t n = skeleton.m_Bones.size();
+    std::vector<glm::mat4> local(n), global(n);
+    for (size_t b = 0; b < n; ++b) local[b] = LocalMatrix(value[b].m_Translation, value[b].m_Rotation, value[b].m_Scale);
+
+    std::vector<char> reached(n, 0);
+    std::vector<size_t> queue;
+    queue.reserve(n);
+    const glm::mat4 identity(1.0f);
+    auto start = [&](size_t b) {
+        reached[b] = 1;
+        global[b] = identity * local[b];
+        queue.push_back(b);
+    };
+    if (skeleton.m_RootBoneIndex >= 0 && (size_t)skeleton.m_RootBoneIndex < n) start((size_t)skeleton.m_RootBoneIndex);
+    else {
+        for (size_t b = 0; b < n; ++b)
+            if (skeleton.m_Bones[b].m_ParentIndex < 0) start(b);
+        if (queue.empty()) start(0);
+    }
+    for (size_t q = 0; q < queue.size(); ++q) {
+        const size_t b = queue[q];
+        for (size_t c = 0; c < n; ++c) {
+            if (skeleton.m_Bones[c].m_ParentIndex != (int)b) continue;
+            if (reached[c]) {  // a cycle the reference would walk for ever: refused
+                std::fprintf(stderr, "[Trident] Animation: the skeleton's parents form a cycle; identity pose\n");
+                return false;
+            }
+            reached[c] = 1;
+            global[c] = global[b] * local[c];
+            queue.push_back(c);
+        }
+    }
+    out.resize(n);
+    for (size_t b = 0; b < n; ++b) {
+        if (!reached[b] || IsIdentity(global[b])) global[b] = local[b];
+        out[b] = global[b] * skeleton.m_Bones[b].m_InverseBindMatrix;
+    }
+    return true;
+}
+
+// glm's quaternion product, each line left to right
+glm::quat QuatMul(const glm::quat& p, const glm::quat& q) {
+    return glm::quat(((p.w * q.w - p.x * q.x) - p.y * q.y) - p.z * q.z, ((p.w * q.x + p.x * q.w) + p.y * q.z) - p.z * q.y,
+                     ((p.w * q.y + p.y * q.w) + p.z * q.x) - p.x * q.z, ((p.w * q.z + p.z * q.w) + p.x * q.y) - p.y * q.x);
+}
+
+glm::vec3 Mix3(const glm::vec3& a, const glm::vec3& b, float F) {
+    const float u = 1.0f - F;
+    return glm::vec3(a.x * u + b.x * F, a.y * u + b.y * F, a.z * u + b.z * F);
+}
+
+}  // namespace
+
 void AnimationPlayer::EvaluatePose(float t) {
     const Skeleton* skeleton = m_AssetService ? m_AssetService->GetSkeleton(m_SkeletonHandle) : nullptr;
     auto fallback = [&]() {  // identities, as many as the last pose had (at least one)
@@ -361,53 +432,139 @@ void AnimationPlayer::EvaluatePose(float t) {
 
     std::vector<TransformDecomposition> value(n);
     for (size_t b = 0; b < n; ++b) value[b] = DecomposeBindTransform(skeleton->m_Bones[b].m_LocalBindTransform);
-    if (clip) {
-        for (const TransformChannel& ch : clip->m_Channels) {
-            const int bone = ResolveChannelBoneIndex(ch, *skeleton, clip->m_Name);
-            if (bone < 0 || (size_t)bone >= n) continue;
-            TransformDecomposition& v = value[(size_t)bone];
-            v.m_Translation = SampleVectorKeys(ch.m_TranslationKeys, t, v.m_Translation);
-            v.m_Rotation = SampleQuaternionKeys(ch.m_RotationKeys, t, v.m_Rotation);
-            v.m_Scale = SampleVectorKeys(ch.m_ScaleKeys, t, v.m_Scale);
-        }
-    }
-    std::vector<glm::mat4> local(n), global(n);
-    for (size_t b = 0; b < n; ++b) local[b] = LocalMatrix(value[b].m_Translation, value[b].m_Rotation, value[b].m_Scale);
+    if (clip) SampleChannels(*skeleton, *clip, t, value);
+    std::vector<glm::mat4> pose;
+    if (!ComposeValues(*skeleton, value, pose)) return fallback();
+    m_PoseMatrices = std::move(pose);
+}
 
-    // the traversal, along the parents (a bone's children are the bones that name it as their parent)
-    std::vector<char> reached(n, 0);
-    std::vector<size_t> queue;
-    queue.reserve(n);
-    const glm::mat4 identity(1.0f);
-    auto start = [&](size_t b) {
-        reached[b] = 1;
-        global[b] = identity * local[b];
-        queue.push_back(b);
-    };
-    if (skeleton->m_RootBoneIndex >= 0 && (size_t)skeleton->m_RootBoneIndex < n) start((size_t)skeleton->m_RootBoneIndex);
-    else {
-        for (size_t b = 0; b < n; ++b)
-            if (skeleton->m_Bones[b].m_ParentIndex < 0) start(b);
-        if (queue.empty()) start(0);
+// ---- pose space ----
+void AnimationPose::Resize(size_t boneCount) {
+    m_Translations.resize(boneCount, glm::vec3(0.0f));
+    m_Rotations.resize(boneCount, glm::quat(1.0f, 0.0f, 0.0f, 0.0f));
+    m_Scales.resize(boneCount, glm::vec3(1.0f));
+}
+
+void AnimationMask::Resize(size_t boneCount) { m_BoneWeights.resize(boneCount, 1.0f); }
+
+float AnimationMask::GetWeight(size_t boneIndex) const {
+    return boneIndex >= m_BoneWeights.size() ? 1.0f : m_BoneWeights[boneIndex];
+}
+
+namespace {
+
+AnimationPose PoseOfValues(const std::vector<TransformDecomposition>& value) {
+    AnimationPose pose;
+    pose.Resize(value.size());
+    for (size_t b = 0; b < value.size(); ++b) {
+        pose.m_Translations[b] = value[b].m_Translation;
+        pose.m_Rotations[b] = value[b].m_Rotation;
+        pose.m_Scales[b] = value[b].m_Scale;
     }
-    for (size_t q = 0; q < queue.size(); ++q) {
-        const size_t b = queue[q];
-        for (size_t c = 0; c < n; ++c) {
-            if (skeleton->m_Bones[c].m_ParentIndex != (int)b) continue;
-            if (reached[c]) {  // a cycle the reference would walk for ever: refused
-                std::fprintf(stderr, "[Trident] Animation: the skeleton's parents form a cycle; identity pose\n");
-                return fallback();
-            }
-            reached[c] = 1;
-            global[c] = global[b] * local[c];
-            queue.push_back(c);
+    return pose;
+}
+
+std::vector<TransformDecomposition> RestValues(const Skeleton& skeleton) {
+    std::vector<TransformDecomposition> value(skeleton.m_Bones.size());
+    for (size_t b = 0; b < value.size(); ++b) value[b] = DecomposeBindTransform(skeleton.m_Bones[b].m_LocalBindTransform);
+    return value;
+}
+
+}  // namespace
+
+AnimationPose AnimationPoseUtilities::BuildRestPose(const Skeleton& skeleton) { return PoseOfValues(RestValues(skeleton)); }
+
+AnimationPose AnimationPoseUtilities::SampleClipPose(const Skeleton& skeleton, const AnimationClip& clip, float sampleTimeSeconds) {
+    std::vector<TransformDecomposition> value = RestValues(skeleton);
+    SampleChannels(skeleton, clip, sampleTimeSeconds, value);
+    return PoseOfValues(value);
+}
+
+void AnimationPoseUtilities::BlendPose(AnimationPose& base, const AnimationPose& target, float blendWeight, const AnimationMask* mask) {
+    const float W = Clamp01(blendWeight);
+    const size_t count = std::min(base.m_Translations.size(), target.m_Translations.size());
+    for (size_t b = 0; b < count; ++b) {
+        const float m = mask ? mask->GetWeight(b) : 1.0f;
+        const float F = Clamp01(W * m);
+        base.m_Translations[b] = Mix3(base.m_Translations[b], target.m_Translations[b], F);
+        base.m_Scales[b] = Mix3(base.m_Scales[b], target.m_Scales[b], F);
+        base.m_Rotations[b] = glm::normalize(Slerp(base.m_Rotations[b], target.m_Rotations[b], F));
+    }
+}
+
+void AnimationPoseUtilities::AdditivePose(AnimationPose& base, const AnimationPose& add, float additiveWeight, const AnimationMask* mask) {
+    const size_t count = std::min(base.m_Translations.size(), add.m_Translations.size());
+    for (size_t b = 0; b < count; ++b) {
+        const float m = mask ? mask->GetWeight(b) : 1.0f;
+        const float F = additiveWeight * m;
+        const glm::vec3 &T = base.m_Translations[b], &S = base.m_Scales[b], &aT = add.m_Translations[b], &aS = add.m_Scales[b];
+        base.m_Translations[b] = glm::vec3(T.x + aT.x * F, T.y + aT.y * F, T.z + aT.z * F);
+        base.m_Scales[b] = glm::vec3(S.x + aS.x * F, S.y + aS.y * F, S.z + aS.z * F);
+        const glm::quat target = QuatMul(base.m_Rotations[b], glm::normalize(add.m_Rotations[b]));
+        base.m_Rotations[b] = glm::normalize(Slerp(base.m_Rotations[b], target, F));
+    }
+}
+
+std::vector<glm::mat4> AnimationPoseUtilities::ComposeSkinningMatrices(const Skeleton& skeleton, const AnimationPose& pose) {
+    std::vector<TransformDecomposition> value = RestValues(skeleton);
+    const size_t have = std::min({value.size(), pose.m_Translations.size(), pose.m_Rotations.size(), pose.m_Scales.size()});
+    for (size_t b = 0; b < have; ++b) {
+        value[b].m_Translation = pose.m_Translations[b];
+        value[b].m_Rotation = pose.m_Rotations[b];
+        value[b].m_Scale = pose.m_Scales[b];
+    }
+    std::vector<glm::mat4> out;
+    if (!ComposeValues(skeleton, value, out)) out.assign(skeleton.m_Bones.size(), glm::mat4(1.0f));
+    return out;
+}
+
+// ---- pose programs ----
+bool PoseProgram::WellFormed() const {
+    size_t depth = 0;
+    for (const PoseOp& op : m_Ops) {
+        if (op.m_Op == PoseOp::Rest || op.m_Op == PoseOp::Clip) ++depth;
+        else if (op.m_Op == PoseOp::Blend || op.m_Op == PoseOp::Add) {
+            if (depth < 2) return false;
+            --depth;
+        } else return false;
+    }
+    return depth == 1;
+}
+
+bool PoseProgram::FitsDevice() const {
+    if (m_Ops.size() > s_MaxOps || !WellFormed()) return false;
+    size_t depth = 0;
+    for (const PoseOp& op : m_Ops) {
+        if (op.m_Op == PoseOp::Rest || op.m_Op == PoseOp::Clip) {
+            if (++depth > s_MaxStack) return false;
+        } else --depth;
+    }
+    return true;
+}
+
+bool EvaluatePoseProgram(const Skeleton& skeleton, const std::vector<AnimationClip>* clips, const PoseProgram& program,
+                         AnimationPose& outPose) {
+    if (!program.WellFormed()) return false;
+    for (const PoseOp& op : program.m_Ops) {
+        if (op.m_Op == PoseOp::Clip && (!clips || op.m_A >= clips->size())) return false;
+        if ((op.m_Op == PoseOp::Blend || op.m_Op == PoseOp::Add) && op.m_A != PoseOp::s_NoMask && op.m_A >= program.m_Masks.size())
+            return false;
+    }
+    const AnimationPose rest = AnimationPoseUtilities::BuildRestPose(skeleton);
+    std::vector<AnimationPose> stack;
+    for (const PoseOp& op : program.m_Ops) {
+        if (op.m_Op == PoseOp::Rest) stack.push_back(rest);
+        else if (op.m_Op == PoseOp::Clip) stack.push_back(AnimationPoseUtilities::SampleClipPose(skeleton, (*clips)[op.m_A], op.m_F));
+        else {
+            const AnimationPose top = std::move(stack.back());
+            stack.pop_back();
+            const AnimationMask* mask = op.m_A == PoseOp::s_NoMask ? nullptr : &program.m_Masks[op.m_A];
+            if (op.m_Op == PoseOp::Blend) AnimationPoseUtilities::BlendPose(stack.back(), top, op.m_F, mask);
+            else AnimationPoseUtilities::AdditivePose(stack.back(), top, op.m_F, mask);
         }
     }
-    m_PoseMatrices.resize(n);
-    for (size_t b = 0; b < n; ++b) {
-        if (!reached[b] || IsIdentity(global[b])) global[b] = local[b];
-        m_PoseMatrices[b] = global[b] * skeleton->m_Bones[b].m_InverseBindMatrix;
-    }
+    outPose = std::move(stack.back());
+    return true;
 }
 
 }  // namespace Animation

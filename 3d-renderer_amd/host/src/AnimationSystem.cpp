@@ -53,6 +53,13 @@ void AnimationSystem::InitialisePose(AnimationComponent& c) {
     c.m_BoneMatrices.clear();
     Animation::AnimationAssetService& service = Animation::AnimationAssetService::Get();
     RefreshCachedHandles(c, service);
+    if (c.m_StateMachine) {
+        c.m_StateMachine->SetSkeletonHandle(c.m_SkeletonAssetHandle);
+        c.m_StateMachine->SetAnimationLibraryHandle(c.m_AnimationAssetHandle);
+        c.m_StateMachine->Update(0.0f);
+        c.m_StateMachine->CopyPose(c.m_BoneMatrices);
+        return;
+    }
     Animation::AnimationPlayer player(service);
     Configure(player, c);
     player.SetIsPlaying(true);
@@ -63,6 +70,11 @@ void AnimationSystem::InitialisePose(AnimationComponent& c) {
 void AnimationSystem::EvaluatePose(AnimationComponent& c) {
     Animation::AnimationAssetService& service = Animation::AnimationAssetService::Get();
     RefreshCachedHandles(c, service);
+    if (c.m_StateMachine) {  // at the machine's current state: its last program, nothing advanced
+        c.m_StateMachine->Evaluate();
+        c.m_StateMachine->CopyPose(c.m_BoneMatrices);
+        return;
+    }
     Animation::AnimationPlayer player(service);
     Configure(player, c);
     player.EvaluateAt(c.m_CurrentTime);
@@ -78,6 +90,15 @@ void AnimationSystem::Update(Registry& registry, float deltaTime) {
 
 void AnimationSystem::UpdateComponent(AnimationComponent& c, float deltaTime) {
     RefreshCachedHandles(c, Animation::AnimationAssetService::Get());
+    if (c.m_StateMachine) {
+        c.m_StateMachine->SetSkeletonHandle(c.m_SkeletonAssetHandle);
+        c.m_StateMachine->SetAnimationLibraryHandle(c.m_AnimationAssetHandle);
+        if (!c.m_StateMachine->Advance(c.m_IsPlaying ? deltaTime : 0.0f)) return;
+        if (m_Renderer && m_Renderer->PosesOnDevice(c)) return;  // the device evaluates this update's program
+        c.m_StateMachine->Evaluate();
+        c.m_StateMachine->CopyPose(c.m_BoneMatrices);
+        return;
+    }
     Configure(m_Player, c);
     m_Player.SetIsPlaying(c.m_IsPlaying);
     m_Player.SetCurrentTime(c.m_CurrentTime);

@@ -192,6 +192,9 @@ struct Target {
     int Pose(tri_animset* const* sets, const tri_pose_instance* i, uint32_t n) const {
         return g ? tri_group_pose_palette(g, sets, i, n) : tri_pose_palette(c, n ? sets[0] : nullptr, i, n);
     }
+    int PoseGraph(tri_animset* const* sets, const tri_pose_graph_instance* i, uint32_t n, const tri_pose_op* ops, uint32_t nops) const {
+        return g ? tri_group_pose_graph(g, sets, i, n, ops, nops) : tri_pose_graph(c, n ? sets[0] : nullptr, i, n, ops, nops);
+    }
     int Frame(const tri_global_ubo* u, const float* clear) const {
         return g ? tri_group_set_frame(g, u, clear) : tri_set_frame(c, u, clear);
     }
@@ -788,13 +791,20 @@ void Renderer::PrepareBonePaletteBuffer() {
         const size_t bones = Animation::AnimationAssetService::Get().GetSkeleton(a.m_SkeletonAssetHandle)->m_Bones.size();
         cmd->m_BoneOffset = total;
         cmd->m_BoneCount = (uint32_t)std::min<size_t>(bones, s_MaxBonesPerSkeleton);
-        m_PoseDraws.push_back({a.m_SkeletonAssetHandle, a.m_AnimationAssetHandle, a.m_CurrentClipIndex, a.m_CurrentTime, total});
+        m_PoseDraws.push_back({a.m_SkeletonAssetHandle, a.m_AnimationAssetHandle, a.m_CurrentClipIndex, a.m_CurrentTime, total,
+                               a.m_StateMachine ? &a.m_StateMachine->GetProgram() : nullptr});
         total += cmd->m_BoneCount;
     }
 }
 
 bool Renderer::PosesOnDevice(const AnimationComponent& a) const {
     if (!m_DevicePose || a.m_SkeletonAssetHandle == Animation::AnimationAssetService::s_InvalidHandle) return false;
+    // a state machine: the program its last Advance emitted must be one the device takes and must have been emitted
+    // against this component's assets; otherwise the CPU system evaluates it and its matrices join the uploaded prefix
+    if (a.m_StateMachine && (!a.m_StateMachine->GetProgram().FitsDevice() ||
+                             a.m_StateMachine->GetSkeletonHandle() != a.m_SkeletonAssetHandle ||
+                             a.m_StateMachine->GetAnimationLibraryHandle() != a.m_AnimationAssetHandle))
+        return false;
     const auto& service = Animation::AnimationAssetService::Get();
     if (m_PoseCompatibleGeneration != service.GetGeneration()) {  // something was registered: look again
         m_PoseCompatible.clear();
@@ -816,7 +826,7 @@ void Renderer::DropPoseSets() {  // only while no context can still pose from th
 
 // The (skeleton asset, animation asset) pair on a device, added to that device's set at its first use: the decomposed
 // defaults, and every clip with its channels resolved against the skeleton (a channel without a bone is left out).
-const Renderer::PoseAssetOnDevice* Renderer::PoseAssetOn(int32_t device, size_t skeleton, size_t animation) {
+Renderer::PoseAssetOnDevice* Renderer::PoseAssetOn(int32_t device, size_t skeleton, size_t animation) {
     if (m_PoseSets.empty()) m_PoseSetsGeneration = Animation::AnimationAssetService::Get().GetGeneration();
     PoseDeviceSet& ds = m_PoseSets[device];
     if (!ds.m_Set && tri_animset_create(device, &ds.m_Set) != TRI_OK) return nullptr;
@@ -891,6 +901,9 @@ bool Renderer::SubmitPoses(ViewportContext& vc) {
         if (tri_get_output(vc.m_Ctx, &img) != TRI_OK) return false;
         devices.push_back(img.device);
     }
+    // one program among the draws: every posed draw goes through tri_pose_graph, the plain clips as [CLIP] programs
+    for (const PoseDraw& p : m_PoseDraws)
+        if (p.m_Program) return SubmitPoseGraph(vc, devices);
     std::vector<tri_animset*> sets;
     m_PoseInstances.clear();
     for (size_t di = 0; di < devices.size(); ++di) {
@@ -910,6 +923,68 @@ bool Renderer::SubmitPoses(ViewportContext& vc) {
     }
     if (t.Pose(sets.data(), m_PoseInstances.data(), (uint32_t)m_PoseInstances.size()) != TRI_OK) return false;
     vc.m_HasPosedSuffix = !m_PoseInstances.empty();
+    return true;
+}
+
+bool Renderer::SubmitPoseGraph(ViewportContext& vc, const std::vector<int32_t>& devices) {
+    const Target t{vc.m_Ctx, vc.m_Group};
+    std::vector<tri_animset*> sets;
+    std::vector<tri_pose_graph_instance> instances;
+    std::vector<tri_pose_op> ops;
+    std::vector<float> weights;
+    for (size_t di = 0; di < devices.size(); ++di) {
+        instances.clear();
+        ops.clear();
+        for (const PoseDraw& p : m_PoseDraws) {
+            PoseAssetOnDevice* on = PoseAssetOn(devices[di], p.m_Skeleton, p.m_Animation);
+            if (!on) return false;
+            const uint32_t first = (uint32_t)ops.size();
+            if (!p.m_Program) {
+                if (p.m_Clip < on->m_Clips.size()) ops.push_back(tri_pose_op{TRI_POSE_OP_CLIP, on->m_Clips[p.m_Clip], p.m_Time, 0u});
+                else ops.push_back(tri_pose_op{TRI_POSE_OP_REST, 0u, 0.0f, 0u});
+            } else {
+                const size_t bones = Animation::AnimationAssetService::Get().GetSkeleton(p.m_Skeleton)->m_Bones.size();
+                for (const Animation::PoseOp& op : p.m_Program->m_Ops) {
+                    tri_pose_op o{op.m_Op, op.m_A, op.m_F, 0u};
+                    if (op.m_Op == Animation::PoseOp::Clip) {
+                        if (op.m_A >= on->m_Clips.size()) return false;
+                        o.a = on->m_Clips[op.m_A];
+                    } else if ((op.m_Op == Animation::PoseOp::Blend || op.m_Op == Animation::PoseOp::Add) &&
+                               op.m_A != Animation::PoseOp::s_NoMask) {
+                        if (op.m_A >= p.m_Program->m_Masks.size()) return false;
+                        // by content, at its first use on this device: new weights are a new mask
+                        weights = p.m_Program->m_Masks[op.m_A].m_BoneWeights;
+                        weights.resize(bones, 1.0f);
+                        auto have = on->m_Masks.find(weights);
+                        if (have == on->m_Masks.end()) {
+                            uint32_t index = 0;
+                            if (tri_animset_add_mask(m_PoseSets[devices[di]].m_Set, on->m_Skeleton, weights.data(), (uint32_t)weights.size(),
+                                                     &index) != TRI_OK)
+                                return false;
+                            have = on->m_Masks.emplace(weights, index).first;
+                        }
+                        o.a = have->second;
+                    }
+                    ops.push_back(o);
+                }
+            }
+            instances.push_back(tri_pose_graph_instance{on->m_Skeleton, first, (uint32_t)ops.size() - first, p.m_Offset});
+        }
+        if (di == 0) {
+            m_PoseGraphInstances = instances;
+            m_PoseOps = ops;
+        } else if (instances.size() != m_PoseGraphInstances.size() || ops.size() != m_PoseOps.size() ||
+                   std::memcmp(instances.data(), m_PoseGraphInstances.data(), instances.size() * sizeof instances[0]) != 0 ||
+                   std::memcmp(ops.data(), m_PoseOps.data(), ops.size() * sizeof ops[0]) != 0) {  // the sets were filled in one order
+            LogError("device poses", "the devices' sets disagree");
+            return false;
+        }
+        sets.push_back(m_PoseSets[devices[di]].m_Set);
+    }
+    if (t.PoseGraph(sets.data(), m_PoseGraphInstances.data(), (uint32_t)m_PoseGraphInstances.size(), m_PoseOps.data(),
+                    (uint32_t)m_PoseOps.size()) != TRI_OK)
+        return false;
+    vc.m_HasPosedSuffix = true;
     return true;
 }
 

@@ -15,6 +15,7 @@
 #include "trident/ModelLoader.h"
 #include "trident/Animation.h"
 #include "trident/AnimationSystem.h"
+#include "trident/AnimationStateMachine.h"
 
 #include <algorithm>
 #include <array>
@@ -988,6 +989,42 @@ size_t AnimHandle(uint64_t handle) {
 
 size_t AnimClip(uint32_t clip) { return clip == UINT32_MAX ? Animation::AnimationAssetService::s_InvalidHandle : (size_t)clip; }
 
+// trident_sm_* / trident_node_*: machines and not yet attached blend-tree nodes by id
+std::unordered_map<uint64_t, std::shared_ptr<Animation::AnimationStateMachine>> g_machines;
+std::unordered_map<uint64_t, std::unique_ptr<Animation::AnimationBlendNode>> g_nodes;
+uint64_t g_next_graph_id = 1;
+
+Animation::AnimationStateMachine* Machine(uint64_t id) {
+    auto found = g_machines.find(id);
+    return found == g_machines.end() ? nullptr : found->second.get();
+}
+
+// Takes the node out of the table: 0 is "no node"; an unknown id sets *ok to false.
+std::unique_ptr<Animation::AnimationBlendNode> TakeNode(uint64_t id, bool* ok) {
+    if (!id) return nullptr;
+    auto found = g_nodes.find(id);
+    if (found == g_nodes.end()) {
+        *ok = false;
+        return nullptr;
+    }
+    std::unique_ptr<Animation::AnimationBlendNode> node = std::move(found->second);
+    g_nodes.erase(found);
+    return node;
+}
+
+uint64_t KeepNode(std::unique_ptr<Animation::AnimationBlendNode> node) {
+    const uint64_t id = g_next_graph_id++;
+    g_nodes[id] = std::move(node);
+    return id;
+}
+
+int CopyName(const std::string& name, char* out, uint32_t capacity) {
+    if (!out) return TRI_OK;
+    if (capacity < name.size() + 1) return TRI_E_INVALID;
+    std::memcpy(out, name.c_str(), name.size() + 1);
+    return TRI_OK;
+}
+
 template <typename F>
 int GuardAnim(F&& f) {
     try {
@@ -1015,6 +1052,21 @@ int trident_app_set_entity_animation(trident_app* app, uint32_t entity, const ch
         a.m_PlaybackSpeed = speed;
         a.m_IsLooping = looping != 0;
         a.m_IsPlaying = playing != 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_entity_state_machine(trident_app* app, uint32_t entity, uint64_t machine) {
+    return Guard(app, [&] {
+        if (!app->registry.HasComponent<AnimationComponent>(entity)) return TRI_E_INVALID;
+        AnimationComponent& a = app->registry.GetComponent<AnimationComponent>(entity);
+        if (!machine) {
+            a.m_StateMachine.reset();
+            return TRI_OK;
+        }
+        auto found = g_machines.find(machine);
+        if (found == g_machines.end()) return TRI_E_INVALID;
+        a.m_StateMachine = found->second;  // shared: the id keeps driving its parameters
         return TRI_OK;
     });
 }
@@ -1298,6 +1350,286 @@ int trident_anim_evaluate(uint64_t handle, uint32_t clip_index, float time, floa
                 for (int k = 0; k < 4; ++k) out[16 * b + 4 * c + k] = pose[b][c][k];
         return TRI_OK;
     });
+}
+
+int trident_anim_eval_program(uint64_t handle, const tri_pose_op* ops, uint32_t op_count, const float* mask_weights,
+                              const uint32_t* mask_counts, uint32_t mask_count, float* out, uint32_t capacity,
+                              uint32_t* count) {
+    if (!count || (op_count && !ops) || (mask_count && !mask_counts)) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        auto& service = Animation::AnimationAssetService::Get();
+        const Animation::Skeleton* sk = service.GetSkeleton(AnimHandle(handle));
+        if (!sk) return TRI_E_INVALID;
+        Animation::PoseProgram program;
+        for (uint32_t i = 0; i < op_count; ++i) {
+            Animation::PoseOp op;
+            op.m_Op = ops[i].op;
+            op.m_A = ops[i].a;
+            op.m_F = ops[i].f;
+            program.m_Ops.push_back(op);
+        }
+        size_t at = 0;
+        for (uint32_t m = 0; m < mask_count; ++m) {
+            if (mask_counts[m] && !mask_weights) return TRI_E_INVALID;
+            Animation::AnimationMask mask;
+            mask.m_BoneWeights.assign(mask_weights + at, mask_weights + at + mask_counts[m]);
+            at += mask_counts[m];
+            program.m_Masks.push_back(std::move(mask));
+        }
+        Animation::AnimationPose pose;
+        if (!Animation::EvaluatePoseProgram(*sk, service.GetAnimationClips(AnimHandle(handle)), program, pose)) return TRI_E_INVALID;
+        const std::vector<glm::mat4> mats = Animation::AnimationPoseUtilities::ComposeSkinningMatrices(*sk, pose);
+        *count = (uint32_t)mats.size();
+        if (!out) return TRI_OK;
+        if (capacity < mats.size()) return TRI_E_INVALID;
+        for (size_t b = 0; b < mats.size(); ++b)
+            for (int c = 0; c < 4; ++c)
+                for (int k = 0; k < 4; ++k) out[16 * b + 4 * c + k] = mats[b][c][k];
+        return TRI_OK;
+    });
+}
+
+int trident_node_clip(uint32_t clip_index, int looping, float speed, const char* speed_parameter, uint64_t* out) {
+    if (!out) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        auto node = std::make_unique<Animation::ClipNode>(AnimClip(clip_index), looping != 0, speed);
+        if (speed_parameter) node->SetSpeedParameter(speed_parameter);
+        *out = KeepNode(std::move(node));
+        return TRI_OK;
+    });
+}
+
+int trident_node_blend(uint64_t first, uint64_t second, float weight, const char* weight_parameter, uint64_t* out) {
+    if (!out) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        if ((first && !g_nodes.count(first)) || (second && !g_nodes.count(second)) || (first && first == second)) return TRI_E_INVALID;
+        bool ok = true;
+        auto a = TakeNode(first, &ok);
+        auto b = TakeNode(second, &ok);
+        auto node = std::make_unique<Animation::BlendNode>(std::move(a), std::move(b), weight);
+        if (weight_parameter) node->SetWeightParameter(weight_parameter);
+        *out = KeepNode(std::move(node));
+        return TRI_OK;
+    });
+}
+
+int trident_node_blend_space(const uint32_t* clip_indices, const float* positions, uint32_t count, float parameter_default,
+                             const char* parameter, uint64_t* out) {
+    if (!out || (count && (!clip_indices || !positions))) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        std::vector<Animation::BlendSpace1DNode::Sample> samples(count);
+        for (uint32_t i = 0; i < count; ++i) {
+            samples[i].m_ClipIndex = AnimClip(clip_indices[i]);
+            samples[i].m_Position = positions[i];
+        }
+        auto node = std::make_unique<Animation::BlendSpace1DNode>(std::move(samples), parameter_default);
+        if (parameter) node->SetParameterName(parameter);
+        *out = KeepNode(std::move(node));
+        return TRI_OK;
+    });
+}
+
+int trident_node_destroy(uint64_t node) { return g_nodes.erase(node) ? TRI_OK : TRI_E_INVALID; }
+
+int trident_sm_create(uint64_t skeleton_handle, uint64_t library_handle, uint64_t* out) {
+    if (!out) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        auto machine = std::make_shared<Animation::AnimationStateMachine>(Animation::AnimationAssetService::Get());
+        machine->SetSkeletonHandle(AnimHandle(skeleton_handle));
+        machine->SetAnimationLibraryHandle(AnimHandle(library_handle));
+        *out = g_next_graph_id++;
+        g_machines[*out] = std::move(machine);
+        return TRI_OK;
+    });
+}
+
+int trident_sm_destroy(uint64_t machine) { return g_machines.erase(machine) ? TRI_OK : TRI_E_INVALID; }
+
+int trident_sm_set_handles(uint64_t machine, uint64_t skeleton_handle, uint64_t library_handle) {
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m) return TRI_E_INVALID;
+        m->SetSkeletonHandle(AnimHandle(skeleton_handle));
+        m->SetAnimationLibraryHandle(AnimHandle(library_handle));
+        return TRI_OK;
+    });
+}
+
+int trident_sm_parameter(uint64_t machine, const char* name, int type, float value, int add) {
+    if (!name) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m) return TRI_E_INVALID;
+        switch (type) {
+            case TRIDENT_SM_FLOAT: add ? m->AddFloatParameter(name, value) : m->SetFloatParameter(name, value); break;
+            case TRIDENT_SM_BOOL: add ? m->AddBoolParameter(name, value != 0.0f) : m->SetBoolParameter(name, value != 0.0f); break;
+            case TRIDENT_SM_INTEGER: add ? m->AddIntegerParameter(name, (int)value) : m->SetIntegerParameter(name, (int)value); break;
+            case TRIDENT_SM_TRIGGER:
+                if (add) m->AddTriggerParameter(name);
+                else if (value != 0.0f) m->FireTrigger(name);
+                else m->ResetTrigger(name);
+                break;
+            default: return TRI_E_INVALID;
+        }
+        return TRI_OK;
+    });
+}
+
+int trident_sm_get_parameter(uint64_t machine, const char* name, int* type, float* as_float, int* trigger_set) {
+    if (!name) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        const Animation::AnimationParameter* p = m ? m->FindParameter(name) : nullptr;
+        if (!p) return TRI_E_INVALID;
+        if (type) *type = (int)p->m_Type;
+        if (as_float) *as_float = p->AsFloat(0.0f);
+        if (trigger_set) *trigger_set = p->m_TriggerValue ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_sm_add_layer(uint64_t machine, const char* name, float weight, int additive, uint32_t* out_layer) {
+    if (!out_layer) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m) return TRI_E_INVALID;
+        *out_layer = (uint32_t)m->AddLayer(name ? name : "", weight, additive != 0);
+        return TRI_OK;
+    });
+}
+
+int trident_sm_set_layer_mask(uint64_t machine, uint32_t layer, const float* weights, uint32_t count) {
+    if (count && !weights) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m) return TRI_E_INVALID;
+        Animation::AnimationMask mask;
+        mask.m_BoneWeights.assign(weights, weights + count);
+        m->SetLayerMask(layer, std::move(mask));
+        return TRI_OK;
+    });
+}
+
+int trident_sm_set_layer_weight(uint64_t machine, uint32_t layer, float weight) {
+    Animation::AnimationStateMachine* m = Machine(machine);
+    if (!m) return TRI_E_INVALID;
+    m->SetLayerWeight(layer, weight);
+    return TRI_OK;
+}
+
+int trident_sm_set_layer_entry(uint64_t machine, uint32_t layer, const char* state) {
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m || !state) return TRI_E_INVALID;
+        m->SetLayerEntryState(layer, state);
+        return TRI_OK;
+    });
+}
+
+int trident_sm_add_state(uint64_t machine, uint32_t layer, const char* name, uint64_t root_node) {
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m || !name || layer >= m->GetLayerCount() || (root_node && !g_nodes.count(root_node))) return TRI_E_INVALID;
+        bool ok = true;
+        m->AddState(layer, name, TakeNode(root_node, &ok));
+        return TRI_OK;
+    });
+}
+
+int trident_sm_add_transition(uint64_t machine, uint32_t layer, const char* from_state, const char* target_state,
+                              int has_exit_time, float exit_time, float fade_duration,
+                              const trident_sm_condition* conditions, uint32_t condition_count) {
+    if (!from_state || !target_state || (condition_count && !conditions)) return TRI_E_INVALID;
+    try {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m || layer >= m->GetLayerCount()) return TRI_E_INVALID;
+        Animation::AnimationTransition t;
+        t.m_TargetState = target_state;
+        t.m_HasExitTime = has_exit_time != 0;
+        t.m_ExitTimeSeconds = exit_time;
+        t.m_FadeDurationSeconds = fade_duration;
+        for (uint32_t i = 0; i < condition_count; ++i) {
+            const trident_sm_condition& c = conditions[i];
+            if (!c.parameter || c.comparison < 0 || c.comparison > TRIDENT_SM_TRIGGERED) return TRI_E_INVALID;
+            Animation::AnimationTransitionCondition cond;
+            cond.m_ParameterName = c.parameter;
+            cond.m_Comparison = (Animation::AnimationConditionComparison)c.comparison;
+            cond.m_FloatValue = c.float_value;
+            cond.m_IntValue = c.int_value;
+            cond.m_BoolValue = c.bool_value != 0;
+            t.m_Conditions.push_back(std::move(cond));
+        }
+        m->AddTransition(layer, from_state, t);
+        return TRI_OK;
+    } catch (const std::runtime_error&) {  // AddTransition from a state the layer does not have
+        return TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+int trident_sm_update(uint64_t machine, float dt) {
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m) return TRI_E_INVALID;
+        m->Update(dt);
+        return TRI_OK;
+    });
+}
+
+int trident_sm_pose(uint64_t machine, float* out, uint32_t capacity, uint32_t* count) {
+    if (!count) return TRI_E_INVALID;
+    return GuardAnim([&] {
+        Animation::AnimationStateMachine* m = Machine(machine);
+        if (!m) return TRI_E_INVALID;
+        std::vector<glm::mat4> pose;
+        m->CopyPose(pose);
+        *count = (uint32_t)pose.size();
+        if (!out) return TRI_OK;
+        if (capacity < pose.size()) return TRI_E_INVALID;
+        for (size_t b = 0; b < pose.size(); ++b)
+            for (int c = 0; c < 4; ++c)
+                for (int k = 0; k < 4; ++k) out[16 * b + 4 * c + k] = pose[b][c][k];
+        return TRI_OK;
+    });
+}
+
+int trident_sm_program(uint64_t machine, tri_pose_op* ops, uint32_t capacity, uint32_t* count, uint32_t* mask_count) {
+    if (!count) return TRI_E_INVALID;
+    Animation::AnimationStateMachine* m = Machine(machine);
+    if (!m) return TRI_E_INVALID;
+    const Animation::PoseProgram& program = m->GetProgram();
+    *count = (uint32_t)program.m_Ops.size();
+    if (mask_count) *mask_count = (uint32_t)program.m_Masks.size();
+    if (!ops) return TRI_OK;
+    if (capacity < program.m_Ops.size()) return TRI_E_INVALID;
+    for (size_t i = 0; i < program.m_Ops.size(); ++i) ops[i] = tri_pose_op{program.m_Ops[i].m_Op, program.m_Ops[i].m_A, program.m_Ops[i].m_F, 0u};
+    return TRI_OK;
+}
+
+int trident_sm_program_mask(uint64_t machine, uint32_t mask, float* weights, uint32_t capacity, uint32_t* count) {
+    if (!count) return TRI_E_INVALID;
+    Animation::AnimationStateMachine* m = Machine(machine);
+    if (!m || mask >= m->GetProgram().m_Masks.size()) return TRI_E_INVALID;
+    const std::vector<float>& w = m->GetProgram().m_Masks[mask].m_BoneWeights;
+    *count = (uint32_t)w.size();
+    if (!weights) return TRI_OK;
+    if (capacity < w.size()) return TRI_E_INVALID;
+    std::copy(w.begin(), w.end(), weights);
+    return TRI_OK;
+}
+
+int trident_sm_layer_state(uint64_t machine, uint32_t layer, char* current, char* next, uint32_t name_capacity,
+                           float* time_in_state, float* transition_elapsed, float* transition_duration) {
+    Animation::AnimationStateMachine* m = Machine(machine);
+    const Animation::AnimationLayer* l = m ? m->GetLayer(layer) : nullptr;
+    if (!l) return TRI_E_INVALID;
+    if (CopyName(l->m_CurrentState ? l->m_CurrentState->m_Name : std::string(), current, name_capacity)) return TRI_E_INVALID;
+    if (CopyName(l->m_NextState ? l->m_NextState->m_Name : std::string(), next, name_capacity)) return TRI_E_INVALID;
+    if (time_in_state) *time_in_state = l->m_TimeInState;
+    if (transition_elapsed) *transition_elapsed = l->m_TransitionElapsed;
+    if (transition_duration) *transition_duration = l->m_TransitionDuration;
+    return TRI_OK;
 }
 
 int trident_anim_advance(uint64_t handle, uint32_t clip_index, float time, float speed, int looping, int playing, float dt,

@@ -260,6 +260,26 @@ assert C.sizeof(TriPoseBone) == POSE_BONE_DTYPE.itemsize == 128
 assert C.sizeof(TriPoseChannel) == POSE_CHANNEL_DTYPE.itemsize == 32
 assert C.sizeof(TriPoseInstance) == POSE_INSTANCE_DTYPE.itemsize == 16
 
+# pose programs (tri_pose_graph)
+TRI_POSE_STACK, TRI_POSE_MAX_OPS, TRI_POSE_NO_MASK = 8, 64, 0xFFFFFFFF
+TRI_POSE_OP_REST, TRI_POSE_OP_CLIP, TRI_POSE_OP_BLEND, TRI_POSE_OP_ADD = 0, 1, 2, 3
+
+
+class TriPoseOp(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("a", C.c_uint32), ("f", C.c_float), ("reserved", C.c_uint32)]
+
+
+class TriPoseGraphInstance(C.Structure):
+    _fields_ = [("skeleton", C.c_uint32), ("op_first", C.c_uint32), ("op_count", C.c_uint32),
+                ("palette_offset", C.c_uint32)]
+
+
+POSE_OP_DTYPE = np.dtype([("op", "<u4"), ("a", "<u4"), ("f", "<f4"), ("reserved", "<u4")])
+POSE_GRAPH_INSTANCE_DTYPE = np.dtype([("skeleton", "<u4"), ("op_first", "<u4"), ("op_count", "<u4"),
+                                      ("palette_offset", "<u4")])
+assert C.sizeof(TriPoseOp) == POSE_OP_DTYPE.itemsize == 16
+assert C.sizeof(TriPoseGraphInstance) == POSE_GRAPH_INSTANCE_DTYPE.itemsize == 16
+
 
 class TriXferConfig(C.Structure):
     _fields_ = [("width", C.c_uint32), ("band_y", C.POINTER(C.c_uint32)), ("display", C.c_uint32),
@@ -340,6 +360,10 @@ CABI_FUNCTIONS = [
     ("tri_pose_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     ("tri_read_bone_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("tri_group_pose_palette", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32]),
+    ("tri_animset_add_mask", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("tri_pose_graph", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    ("tri_group_pose_graph", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_uint32]),
     ("tri_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("tri_get_timing", C.c_int, [C.c_void_p, C.POINTER(TriTiming)]),
     ("tri_get_frame_stats", C.c_int, [C.c_void_p, C.POINTER(TriFrameStats)]),

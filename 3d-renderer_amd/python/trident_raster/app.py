@@ -123,6 +123,7 @@ _APP_FUNCTIONS = [
                                                    C.c_float, C.c_int, C.c_int]),
     ("trident_app_update_animation", C.c_int, [C.c_void_p, C.c_float]),
     ("trident_app_initialise_pose", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("trident_app_set_entity_state_machine", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64]),
     ("trident_app_entity_pose", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("trident_app_entity_animation_state", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                                      C.POINTER(C.c_uint64 * 3)]),
@@ -141,6 +142,30 @@ _APP_FUNCTIONS = [
     ("trident_anim_evaluate", C.c_int, [C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("trident_anim_advance", C.c_int, [C.c_uint64, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
                                        C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    ("trident_anim_eval_program", C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_node_clip", C.c_int, [C.c_uint32, C.c_int, C.c_float, C.c_char_p, C.POINTER(C.c_uint64)]),
+    ("trident_node_blend", C.c_int, [C.c_uint64, C.c_uint64, C.c_float, C.c_char_p, C.POINTER(C.c_uint64)]),
+    ("trident_node_blend_space", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_char_p, C.POINTER(C.c_uint64)]),
+    ("trident_node_destroy", C.c_int, [C.c_uint64]),
+    ("trident_sm_create", C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("trident_sm_destroy", C.c_int, [C.c_uint64]),
+    ("trident_sm_set_handles", C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64]),
+    ("trident_sm_parameter", C.c_int, [C.c_uint64, C.c_char_p, C.c_int, C.c_float, C.c_int]),
+    ("trident_sm_get_parameter", C.c_int, [C.c_uint64, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    ("trident_sm_add_layer", C.c_int, [C.c_uint64, C.c_char_p, C.c_float, C.c_int, C.POINTER(C.c_uint32)]),
+    ("trident_sm_set_layer_mask", C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32]),
+    ("trident_sm_set_layer_weight", C.c_int, [C.c_uint64, C.c_uint32, C.c_float]),
+    ("trident_sm_set_layer_entry", C.c_int, [C.c_uint64, C.c_uint32, C.c_char_p]),
+    ("trident_sm_add_state", C.c_int, [C.c_uint64, C.c_uint32, C.c_char_p, C.c_uint64]),
+    ("trident_sm_add_transition", C.c_int, [C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_float, C.c_float,
+                                            C.c_void_p, C.c_uint32]),
+    ("trident_sm_update", C.c_int, [C.c_uint64, C.c_float]),
+    ("trident_sm_pose", C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_sm_program", C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("trident_sm_program_mask", C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_sm_layer_state", C.c_int, [C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 ]
 
 _lib = None
@@ -299,6 +324,11 @@ class TridentApp:
     def update_animation(self, dt):
         """ECS::AnimationSystem::Update."""
         _check(self._lib.trident_app_update_animation(self._h, dt), "update_animation")
+
+    def set_entity_state_machine(self, entity, machine):
+        """AnimationComponent::m_StateMachine: a StateMachine, or None to remove it."""
+        _check(self._lib.trident_app_set_entity_state_machine(self._h, entity, machine.id if machine is not None else 0),
+               "set_entity_state_machine")
 
     def initialise_pose(self, entity):
         _check(self._lib.trident_app_initialise_pose(self._h, entity), "initialise_pose")
@@ -888,6 +918,28 @@ def anim_evaluate(handle, clip_index, time):
     return out
 
 
+def anim_eval_program(handle, ops, masks=()):
+    """The CPU interpreter's matrices for a pose program: ops = rows of (op, a, f) or an abi.POSE_OP_DTYPE array (a CLIP's
+    `a` indexes the asset's clips, a BLEND / ADD's `a` indexes `masks`, a sequence of weight arrays); float32 [bones, 16]."""
+    lib = load_library()
+    if isinstance(ops, np.ndarray) and ops.dtype == abi.POSE_OP_DTYPE:
+        o = np.ascontiguousarray(ops)
+    else:
+        o = np.zeros(len(ops), abi.POSE_OP_DTYPE)
+        for i, (op, a, f) in enumerate(ops):
+            o[i] = (op, a, f, 0)
+    counts = np.array([len(m) for m in masks], np.uint32)
+    weights = np.concatenate([np.asarray(m, np.float32).reshape(-1) for m in masks]) if len(masks) else np.zeros(0, np.float32)
+    weights = np.ascontiguousarray(weights, np.float32)
+    opt = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    n = C.c_uint32()
+    args = (handle, opt(o), o.size, opt(weights), opt(counts), counts.size)
+    _check(lib.trident_anim_eval_program(*args, None, 0, C.byref(n)), "anim_eval_program")
+    out = np.empty((n.value, 16), np.float32)
+    _check(lib.trident_anim_eval_program(*args, out.ctypes.data, n.value, C.byref(n)), "anim_eval_program")
+    return out
+
+
 def anim_advance(handle, clip_index, time, dt, speed=1.0, looping=True, playing=True):
     """AnimationPlayer::Update from the given state: (time, playing) afterwards."""
     lib = load_library()
@@ -895,3 +947,153 @@ def anim_advance(handle, clip_index, time, dt, speed=1.0, looping=True, playing=
     _check(lib.trident_anim_advance(handle, ANIM_NO_CLIP if clip_index is None else clip_index, time, speed,
                                     int(looping), int(playing), dt, C.byref(t), C.byref(p)), "anim_advance")
     return t.value, bool(p.value)
+
+
+# ---- animation state machines and blend trees (trident_sm_* / trident_node_*): host state only, no GPU ----
+SM_FLOAT, SM_BOOL, SM_INTEGER, SM_TRIGGER = 0, 1, 2, 3
+SM_COMPARISON = {"==": 0, "!=": 1, ">": 2, "<": 3, ">=": 4, "<=": 5, "triggered": 6}
+
+
+class SmCondition(C.Structure):
+    _fields_ = [("parameter", C.c_char_p), ("comparison", C.c_int32), ("float_value", C.c_float),
+                ("int_value", C.c_int32), ("bool_value", C.c_int32)]
+
+
+def _opt_name(name):
+    return None if name is None else name.encode()
+
+
+def node_clip(clip_index, looping=True, speed=1.0, speed_parameter=None):
+    """A ClipNode's id (clip_index None: no clip)."""
+    out = C.c_uint64()
+    _check(load_library().trident_node_clip(ANIM_NO_CLIP if clip_index is None else clip_index, int(looping), speed,
+                                            _opt_name(speed_parameter), C.byref(out)), "node_clip")
+    return out.value
+
+
+def node_blend(first, second, weight=0.5, weight_parameter=None):
+    """A BlendNode's id over two node ids (None: no child); the children's ids are consumed."""
+    out = C.c_uint64()
+    _check(load_library().trident_node_blend(first or 0, second or 0, weight, _opt_name(weight_parameter), C.byref(out)),
+           "node_blend")
+    return out.value
+
+
+def node_blend_space(samples, default=0.0, parameter=None):
+    """A BlendSpace1DNode's id: samples = (clip index or None, position) pairs."""
+    clips = np.array([ANIM_NO_CLIP if c is None else c for c, _ in samples], np.uint32)
+    pos = np.array([p for _, p in samples], np.float32)
+    out = C.c_uint64()
+    _check(load_library().trident_node_blend_space(clips.ctypes.data if clips.size else None,
+                                                   pos.ctypes.data if pos.size else None, clips.size, default,
+                                                   _opt_name(parameter), C.byref(out)), "node_blend_space")
+    return out.value
+
+
+class StateMachine:
+    """Animation::AnimationStateMachine on the shim's asset service (handles from anim_register; None: invalid)."""
+
+    def __init__(self, skeleton_handle, library_handle=None):
+        self._lib = load_library()
+        out = C.c_uint64()
+        lib_handle = skeleton_handle if library_handle is None else library_handle
+        _check(self._lib.trident_sm_create(ANIM_NO_HANDLE if skeleton_handle is None else skeleton_handle,
+                                           ANIM_NO_HANDLE if lib_handle is None else lib_handle, C.byref(out)), "sm_create")
+        self.id = out.value
+
+    def close(self):
+        if self.id:
+            self._lib.trident_sm_destroy(self.id)
+            self.id = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_handles(self, skeleton_handle, library_handle):
+        h = lambda v: ANIM_NO_HANDLE if v is None else v  # noqa: E731
+        _check(self._lib.trident_sm_set_handles(self.id, h(skeleton_handle), h(library_handle)), "sm_set_handles")
+
+    def add_parameter(self, name, kind, value=0.0):
+        _check(self._lib.trident_sm_parameter(self.id, name.encode(), kind, float(value), 1), "sm_add_parameter")
+
+    def set_parameter(self, name, kind, value):
+        _check(self._lib.trident_sm_parameter(self.id, name.encode(), kind, float(value), 0), "sm_set_parameter")
+
+    def fire(self, name):
+        self.set_parameter(name, SM_TRIGGER, 1.0)
+
+    def reset_trigger(self, name):
+        self.set_parameter(name, SM_TRIGGER, 0.0)
+
+    def parameter(self, name):
+        """(type, AsFloat, trigger set) or None for a parameter the machine does not have."""
+        t, f, trig = C.c_int(), C.c_float(), C.c_int()
+        if self._lib.trident_sm_get_parameter(self.id, name.encode(), C.byref(t), C.byref(f), C.byref(trig)) != abi.TRI_OK:
+            return None
+        return t.value, f.value, bool(trig.value)
+
+    def add_layer(self, name, weight=1.0, additive=False):
+        out = C.c_uint32()
+        _check(self._lib.trident_sm_add_layer(self.id, name.encode(), weight, int(additive), C.byref(out)), "sm_add_layer")
+        return out.value
+
+    def set_layer_mask(self, layer, weights):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        _check(self._lib.trident_sm_set_layer_mask(self.id, layer, w.ctypes.data if w.size else None, w.size), "sm_set_layer_mask")
+
+    def set_layer_weight(self, layer, weight):
+        _check(self._lib.trident_sm_set_layer_weight(self.id, layer, weight), "sm_set_layer_weight")
+
+    def set_layer_entry(self, layer, state):
+        _check(self._lib.trident_sm_set_layer_entry(self.id, layer, state.encode()), "sm_set_layer_entry")
+
+    def add_state(self, layer, name, root_node):
+        _check(self._lib.trident_sm_add_state(self.id, layer, name.encode(), root_node or 0), "sm_add_state")
+
+    def add_transition(self, layer, from_state, target_state, fade=0.2, exit_time=None, conditions=()):
+        """conditions: (parameter, comparison in SM_COMPARISON, value) with value a bool, an int or a float."""
+        arr = (SmCondition * max(len(conditions), 1))()
+        for i, (name, cmp_, value) in enumerate(conditions):
+            arr[i] = SmCondition(name.encode(), SM_COMPARISON[cmp_], float(value), int(value), int(bool(value)))
+        _check(self._lib.trident_sm_add_transition(self.id, layer, from_state.encode(), target_state.encode(),
+                                                   int(exit_time is not None), exit_time or 0.0, fade,
+                                                   C.cast(arr, C.c_void_p) if conditions else None, len(conditions)),
+               "sm_add_transition")
+
+    def update(self, dt):
+        _check(self._lib.trident_sm_update(self.id, dt), "sm_update")
+
+    def pose(self):
+        n = C.c_uint32()
+        _check(self._lib.trident_sm_pose(self.id, None, 0, C.byref(n)), "sm_pose")
+        out = np.empty((n.value, 16), np.float32)
+        _check(self._lib.trident_sm_pose(self.id, out.ctypes.data if n.value else None, n.value, C.byref(n)), "sm_pose")
+        return out
+
+    def program(self):
+        """(ops as (op, a, f) tuples, masks as float32 arrays) of the last update."""
+        n, m = C.c_uint32(), C.c_uint32()
+        _check(self._lib.trident_sm_program(self.id, None, 0, C.byref(n), C.byref(m)), "sm_program")
+        ops = np.zeros(n.value, abi.POSE_OP_DTYPE)
+        _check(self._lib.trident_sm_program(self.id, ops.ctypes.data if n.value else None, n.value, C.byref(n), C.byref(m)),
+               "sm_program")
+        masks = []
+        for i in range(m.value):
+            k = C.c_uint32()
+            _check(self._lib.trident_sm_program_mask(self.id, i, None, 0, C.byref(k)), "sm_program_mask")
+            w = np.zeros(k.value, np.float32)
+            _check(self._lib.trident_sm_program_mask(self.id, i, w.ctypes.data if k.value else None, k.value, C.byref(k)),
+                   "sm_program_mask")
+            masks.append(w)
+        return [(int(o["op"]), int(o["a"]), float(o["f"])) for o in ops], masks
+
+    def layer_state(self, layer):
+        """(current state name, next state name, time in state, transition elapsed, transition duration)."""
+        cur, nxt = C.create_string_buffer(256), C.create_string_buffer(256)
+        t, e, d = C.c_float(), C.c_float(), C.c_float()
+        _check(self._lib.trident_sm_layer_state(self.id, layer, cur, nxt, 256, C.byref(t), C.byref(e), C.byref(d)),
+               "sm_layer_state")
+        return cur.value.decode(), nxt.value.decode(), t.value, e.value, d.value

@@ -134,6 +134,13 @@ class TriRaster:
         _check(_lib.tri_pose_palette(self._ctx, animset._s if animset is not None else None, _ptr(p) if p.size else None,
                                      p.size))
 
+    def pose_graph(self, animset, instances, ops):
+        """tri_pose_graph: instances = rows of (skeleton, op_first, op_count, palette_offset), ops = rows of
+        (op, a, f) (or the POSE_GRAPH_INSTANCE_DTYPE / POSE_OP_DTYPE arrays); no instances drops the posed suffix."""
+        p, o = _pose_graph_records(instances, ops)
+        _check(_lib.tri_pose_graph(self._ctx, animset._s if animset is not None else None, _ptr(p) if p.size else None,
+                                   p.size, _ptr(o) if o.size else None, o.size))
+
     def read_bone_palette(self, count):
         """tri_read_bone_palette: float32 [count, 16], column-major matrices."""
         out = np.empty((count, 16), dtype=np.float32)
@@ -300,8 +307,24 @@ def _pose_instances(instances):
     return p
 
 
+def _pose_graph_records(instances, ops):
+    if isinstance(instances, np.ndarray) and instances.dtype == abi.POSE_GRAPH_INSTANCE_DTYPE:
+        p = np.ascontiguousarray(instances)
+    else:
+        p = np.zeros(len(instances), dtype=abi.POSE_GRAPH_INSTANCE_DTYPE)
+        for i, (skeleton, first, count, offset) in enumerate(instances):
+            p[i] = (skeleton, first, count, offset)
+    if isinstance(ops, np.ndarray) and ops.dtype == abi.POSE_OP_DTYPE:
+        o = np.ascontiguousarray(ops)
+    else:
+        o = np.zeros(len(ops), dtype=abi.POSE_OP_DTYPE)
+        for i, (op, a, f) in enumerate(ops):
+            o[i] = (op, a, f, 0)
+    return p, o
+
+
 class TriAnimSet:
-    """tri_animset: skeletons and clips on one device, posed by tri_pose_palette."""
+    """tri_animset: skeletons, clips and masks on one device, posed by tri_pose_palette / tri_pose_graph."""
 
     def __init__(self, device=-1):
         lib = load_library()
@@ -328,6 +351,13 @@ class TriAnimSet:
         opt = lambda a: _ptr(a) if a.size else None  # noqa: E731
         _check(_lib.tri_animset_add_clip(self._s, skeleton, opt(ch), ch.size, opt(vt), opt(vv), vt.size, opt(qt), opt(qv),
                                          qt.size, duration, C.byref(out)))
+        return out.value
+
+    def add_mask(self, skeleton, weights):
+        """tri_animset_add_mask: per-bone weights (shorter: the rest weigh 1.0; longer: dropped); returns the mask index."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        out = C.c_uint32()
+        _check(_lib.tri_animset_add_mask(self._s, skeleton, _ptr(w) if w.size else None, w.size, C.byref(out)))
         return out.value
 
     def close(self):
@@ -620,6 +650,15 @@ class TriGroup:
             raise ValueError(f"{ndev} devices need {ndev} fonts")
         arr = (C.c_void_p * len(fonts))(*[f._f.value for f in fonts])
         _check(_lib.tri_group_set_text(self._g, arr, _ptr(q), q.shape[0]))
+
+    def pose_graph(self, animsets, instances, ops):
+        """tri_group_pose_graph: animsets = one TriAnimSet per distinct device of the group (any order)."""
+        p, o = _pose_graph_records(instances, ops)
+        if not p.size:
+            _check(_lib.tri_group_pose_graph(self._g, None, None, 0, None, 0))
+            return
+        arr = (C.c_void_p * len(animsets))(*[s._s.value for s in animsets])
+        _check(_lib.tri_group_pose_graph(self._g, arr, _ptr(p), p.size, _ptr(o) if o.size else None, o.size))
 
     def render(self):
         _check(_lib.tri_group_render(self._g))

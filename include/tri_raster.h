@@ -298,13 +298,52 @@ int tri_upload_bone_palette(tri_ctx* ctx, const float* matrices, uint32_t matrix
  * pose = global * inverse_bind. A parent graph with a cycle reachable from the start set, which the reference would
  * walk for ever, is refused when the skeleton is added.
  *
- * Time advance (AnimationPlayer::Update, :57-102) is the caller's: an instance carries the final sample time. */
+ * Time advance (AnimationPlayer::Update, :57-102) is the caller's: an instance carries the final sample time.
+ *
+ * Pose space (Animation::AnimationPoseUtilities, AnimationPose.cpp:153-225). A pose is, per bone, a translation, a
+ * rotation quaternion and a scale; everything below is per bone: bone b of a result depends on bone b of its inputs
+ * alone. Implemented three times like the rules above: k_pose_graph (csrc/pose_eval.hip), the shim's float32
+ * interpreter (host/src/Animation.cpp, EvaluatePoseProgram) and float64 numpy (tests/anim_graph_ref.py).
+ *   Rest pose (BuildRestPose): the bone's decomposed defaults, as tri_pose_bone carries them.
+ *   Clip pose (SampleClipPose, :171-196): the rest pose with every track that has keys sampled at the time by the
+ *     track rules above (SampleVectorKeys / SampleQuaternionKeys of AnimationPose.cpp:40-94 are the player's: the
+ *     same branches, the same clamp, normalize on every sampled quaternion). The value the player holds before the
+ *     local matrix's normalize: a default rotation is taken as stored.
+ *   blend(base, target, weight, mask) (BlendPose, :198-211): W = clamp(weight, 0, 1); per bone F = clamp(W * m, 0, 1)
+ *     with m the bone's mask weight, 1.0 without a mask (the product and the second clamp are evaluated then too);
+ *     T = mix(base.T, target.T, F), S = mix(base.S, target.S, F), R = normalize(slerp(base.R, target.R, F)).
+ *   additive(base, add, weight, mask) (AdditivePose, :213-225): F = weight * m, not clamped; per component
+ *     T = base.T + add.T * F and S = base.S + add.S * F (an additive pose that holds rest scales adds them: the
+ *     reference's behaviour, kept); R = normalize(slerp(base.R, base.R * normalize(add.R), F)), slerp taking F as it
+ *     is, also outside [0, 1]. p * q is glm's quaternion product, each line left to right:
+ *       w = p.w*q.w - p.x*q.x - p.y*q.y - p.z*q.z      x = p.w*q.x + p.x*q.w + p.y*q.z - p.z*q.y
+ *       y = p.w*q.y + p.y*q.w + p.z*q.x - p.x*q.z      z = p.w*q.z + p.z*q.w + p.x*q.y - p.y*q.x
+ *   A mask holds one weight per bone; a bone beyond its weights weighs 1.0 (AnimationMask::GetWeight).
+ *   Compose (ComposeSkinningMatrices, :227-310): the local matrix of {T, R, S} by the closed form above (with its
+ *     normalize(R)), then the hierarchy and global * inverse_bind as above. That function starts every evaluation
+ *     from identity globals, so a bone the traversal does not reach takes its fresh local matrix (identity == global
+ *     sends it there): the rule already chosen above. The traversal follows the parents.
+ *
+ * A pose program is a postfix sequence of tri_pose_op over a stack of poses, evaluated per bone:
+ *   TRI_POSE_OP_REST   push the rest pose
+ *   TRI_POSE_OP_CLIP   push the clip pose of clip `a` at time `f`
+ *   TRI_POSE_OP_BLEND  pop target; top = blend(top, target, f, mask a or TRI_POSE_NO_MASK)
+ *   TRI_POSE_OP_ADD    pop add;    top = additive(top, add, f, mask a or TRI_POSE_NO_MASK)
+ * A valid program has 1..TRI_POSE_MAX_OPS operations, never pops below one entry for a BLEND / ADD (two are needed),
+ * never holds more than TRI_POSE_STACK entries and ends with exactly one, which is composed into the palette. */
 #define TRI_POSE_MAX_BONES 256      /* bones of one skeleton (ancestors beyond the palette slice still count)      */
 #define TRI_POSE_PALETTE_BONES 128  /* an instance writes its first min(bones, 128) matrices                      *
                                      * (PrepareBonePaletteBuffer's clamp, Renderer.cpp:3168-3245)                 */
 #define TRI_POSE_BIND 0xFFFFFFFFu   /* tri_pose_instance.clip: no clip, every bone at its defaults                */
 #define TRI_POSE_MAX_INSTANCES 65536u
 #define TRI_POSE_MAX_PALETTE (1u << 24) /* matrices a palette may hold                                            */
+#define TRI_POSE_STACK 8            /* poses a program may hold at once                                           */
+#define TRI_POSE_MAX_OPS 64         /* operations of one program                                                  */
+#define TRI_POSE_NO_MASK 0xFFFFFFFFu /* tri_pose_op.a of a BLEND / ADD: every bone weighs 1.0                     */
+#define TRI_POSE_OP_REST 0u
+#define TRI_POSE_OP_CLIP 1u
+#define TRI_POSE_OP_BLEND 2u
+#define TRI_POSE_OP_ADD 3u
 
 /* One bone: its parent (negative: none), the decomposed defaults and the inverse bind matrix. */
 typedef struct tri_pose_bone {
@@ -333,6 +372,22 @@ typedef struct tri_pose_instance {
     uint32_t palette_offset; /* first matrix of the instance's slice in the context's palette  */
 } tri_pose_instance;
 
+/* One operation of a pose program (above). */
+typedef struct tri_pose_op {
+    uint32_t op;       /* TRI_POSE_OP_*                                                              */
+    uint32_t a;        /* CLIP: the clip; BLEND / ADD: the mask or TRI_POSE_NO_MASK; REST: ignored  */
+    float f;           /* CLIP: the sample time in seconds; BLEND / ADD: the weight; REST: ignored  */
+    uint32_t reserved;
+} tri_pose_op;
+
+/* One instance of tri_pose_graph: its program is ops[op_first .. op_first + op_count). */
+typedef struct tri_pose_graph_instance {
+    uint32_t skeleton;       /* from tri_animset_add_skeleton                                  */
+    uint32_t op_first;
+    uint32_t op_count;
+    uint32_t palette_offset; /* first matrix of the instance's slice in the context's palette  */
+} tri_pose_graph_instance;
+
 /* A device-resident, append-only store of skeletons and clips on one device (-1: the current one). Adding validates
  * on the host, derives the traversal's level order and completes its upload before it returns; a destroy only after
  * every context that posed from the set is synchronised. Without a HIP device tri_animset_create is TRI_E_HIP. */
@@ -350,6 +405,11 @@ int tri_animset_add_clip(tri_animset* set, uint32_t skeleton, const tri_pose_cha
                          const float* vec_times, const float* vec_values, uint32_t vec_count,
                          const float* quat_times, const float* quat_values, uint32_t quat_count, float duration,
                          uint32_t* out_clip);
+/* Per-bone mask weights for a skeleton, append-only and uploaded like a clip. weight_count may differ from the bone
+ * count: bones beyond it weigh 1.0, weights beyond the bones are dropped (weights may be NULL when it is 0).
+ * TRI_E_INVALID: an unknown skeleton. */
+int tri_animset_add_mask(tri_animset* set, uint32_t skeleton, const float* weights, uint32_t weight_count,
+                         uint32_t* out_mask);
 
 /* Evaluate `count` instances on the context's stream (k_pose), each writing its min(bones, TRI_POSE_PALETTE_BONES)
  * matrices at palette_offset of the context's bone palette. The palette is then the uploaded prefix (what the last
@@ -361,6 +421,14 @@ int tri_animset_add_clip(tri_animset* set, uint32_t skeleton, const tri_pose_cha
  * TRI_POSE_MAX_PALETTE, two instances that overlap, an unknown skeleton or clip, a clip of another skeleton, a set
  * on another device, count above TRI_POSE_MAX_INSTANCES. */
 int tri_pose_palette(tri_ctx* ctx, tri_animset* set, const tri_pose_instance* instances, uint32_t count);
+/* tri_pose_palette with a pose program per instance (k_pose_graph): the same palette contract (the call replaces the
+ * posed suffix, never writes the uploaded prefix, count 0 drops the suffix), the same stream order (instances and
+ * operations travel through a pinned ring; both arrays may be overwritten when the call returns). Programs of several
+ * instances may share or overlap ranges of `ops`. TRI_E_INVALID, before anything is enqueued: whatever
+ * tri_pose_palette refuses, an op range outside `ops`, an invalid program (see the rules above), an unknown op, a
+ * clip or mask that is unknown or belongs to another skeleton. */
+int tri_pose_graph(tri_ctx* ctx, tri_animset* set, const tri_pose_graph_instance* instances, uint32_t count,
+                   const tri_pose_op* ops, uint32_t op_count);
 /* Blocking read of the palette's first matrix_count matrices (at most its current extent), for tests and tools. */
 int tri_read_bone_palette(tri_ctx* ctx, float* out_matrices, uint32_t matrix_count);
 
@@ -736,6 +804,10 @@ int tri_group_set_text(tri_group* group, tri_font* const* fonts, const tri_text_
  * posed). count == 0 drops every band's posed suffix. */
 int tri_group_pose_palette(tri_group* group, tri_animset* const* sets, const tri_pose_instance* instances,
                            uint32_t count);
+/* tri_pose_graph on every band with the same instances and operations, under tri_group_pose_palette's terms: the
+ * sets also hold the same masks under the same indices, and every band's check passes before any band enqueues. */
+int tri_group_pose_graph(tri_group* group, tri_animset* const* sets, const tri_pose_graph_instance* instances,
+                         uint32_t count, const tri_pose_op* ops, uint32_t op_count);
 /* Enqueue every band, then the assembly onto the display device (asynchronous). */
 int tri_group_render(tri_group* group);
 /* Wait for every band and the assembly; TRI_E_OVERFLOW as tri_synchronize (re-render the frame). */
@@ -788,6 +860,8 @@ static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
 static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
 static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
 static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
+static_assert(sizeof(tri_pose_op) == 16, "tri_pose_op layout");
+static_assert(sizeof(tri_pose_graph_instance) == 16, "tri_pose_graph_instance layout");
 #endif
 
 #endif /* TRI_RASTER_H */
