@@ -161,6 +161,19 @@ hipError_t tri_launch_bgra_to_yuv444(const void* src, uint32_t width, uint32_t h
 hipError_t tri_launch_bgra_to_rgba_f32(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, float* dst,
                                        hipStream_t stream);
 
+// The frame generator (nn_conv.hip, frame_generator.hip; include/tri_raster.h "the frame generator").
+// One checked layer on the current device: every pointer device memory, res1 / res2 may be null.
+hipError_t tri_launch_nn_conv(const tri_nn_conv_desc& desc, const float* in, const float* packed_weights,
+                              const float* scale, const float* shift, const float* res1, const float* res2, float* out,
+                              hipStream_t stream);
+// k_ai_pack: pixels x channels (1..4) floats -> pixels R8G8B8A8 dwords (tri_upload_ai_frame_device's rules).
+hipError_t tri_launch_ai_pack(const float* src, uint64_t pixels, uint32_t channels, uint32_t* dst, hipStream_t stream);
+int tri_internal_framegen_device(const tri_framegen* gen);
+// Recorded on the generator's stream behind its last submitted job (null before the first).
+hipEvent_t tri_internal_framegen_done(const tri_framegen* gen);
+// The generator's stream waits for `read`, recorded behind a reader of its output on another stream.
+hipError_t tri_internal_framegen_reader(tri_framegen* gen, hipEvent_t read);
+
 // The text overlay (text_overlay.hip; include/tri_raster.h "text overlay"). A wave of k_text_overlay scans its
 // bin's quad references TRI_TEXT_SCAN_CHUNK at a time (one per lane) and walks the ballot of the hits in order: the
 // ballot is the per-round list, TRI_TEXT_LIST_CAP entries; a strip under more quads takes more rounds. Screen bins are

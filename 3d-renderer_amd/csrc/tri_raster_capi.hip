@@ -124,6 +124,7 @@ struct tri_ctx {
     float* d_bones = nullptr; size_t cap_bones = 0;
     uint32_t* d_sky = nullptr; size_t cap_sky = 0;
     uint32_t* d_ai = nullptr; size_t cap_ai = 0;  // the AI blend's RGBA8 UNORM frame (tri_upload_ai_frame)
+    hipEvent_t ai_packed = nullptr;  // behind tri_upload_ai_frame_device's kernel: the generator's next job waits for it
     uint32_t ai_w = 0, ai_h = 0;
     uint32_t sky_size = 0;
     bool sky_uniform = false;  // every texel of the cubemap equal (e.g. the solid fallback)
@@ -1060,6 +1061,7 @@ int tri_destroy(tri_ctx* c) {
     }
     if (c->h_text) (void)hipHostFree(c->h_text);
     if (c->text_free) (void)hipEventDestroy(c->text_free);
+    if (c->ai_packed) (void)hipEventDestroy(c->ai_packed);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     f(c->d_args);
@@ -1086,6 +1088,12 @@ int tri_set_stream(tri_ctx* c, void* s) {
         TRI_HIP_TRY(hipEventDestroy(e));
     }
     c->stream = next;
+    return TRI_OK;
+}
+
+int tri_get_stream(tri_ctx* c, void** s) {
+    if (!c || !s) return fail(TRI_E_INVALID, "tri_get_stream: null argument");
+    *s = c->stream;
     return TRI_OK;
 }
 
@@ -1378,6 +1386,45 @@ int tri_upload_ai_frame(tri_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h
     TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->ai_w = w;
     c->ai_h = h;
+    return TRI_OK;
+}
+
+// The same texture from a tensor on the device (a generator's output): k_ai_pack on the context's stream, so the
+// frames already queued still sample the previous texels and the next tri_render samples these.
+int tri_upload_ai_frame_device(tri_ctx* c, const void* nhwc, uint32_t w, uint32_t h, uint32_t channels, tri_framegen* behind) {
+    if (!c || !nhwc) return fail(TRI_E_INVALID, "tri_upload_ai_frame_device: null argument");
+    if (w == 0 || h == 0 || w > TRI_MAX_DIM || h > TRI_MAX_DIM)
+        return fail(TRI_E_INVALID, "tri_upload_ai_frame_device: extent %ux%u outside 1..%d", w, h, TRI_MAX_DIM);
+    if (channels < 1 || channels > 4) return fail(TRI_E_INVALID, "tri_upload_ai_frame_device: %u channels outside 1..4", channels);
+    if ((uintptr_t)nhwc & 3u) return fail(TRI_E_INVALID, "tri_upload_ai_frame_device: the tensor must be 4-B aligned");
+    if (behind && tri_internal_framegen_device(behind) != c->device)
+        return fail(TRI_E_INVALID, "tri_upload_ai_frame_device: the generator is on another device");
+    int rc = make_current(c);
+    if (rc) return rc;
+    if ((size_t)w * h > c->cap_ai || !c->d_ai) {  // a queued frame may still sample the buffer that grow() frees
+        TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+        if ((rc = grow(c->d_ai, c->cap_ai, (size_t)w * h))) return rc;
+    }
+    if (behind)
+        if (hipEvent_t done = tri_internal_framegen_done(behind)) TRI_HIP_TRY(hipStreamWaitEvent(c->stream, done, 0));
+    TRI_HIP_TRY(tri_launch_ai_pack(static_cast<const float*>(nhwc), (uint64_t)w * h, channels, c->d_ai, c->stream));
+    if (behind) {  // the generator's next job overwrites the tensor: it waits for this read
+        if (!c->ai_packed) TRI_HIP_TRY(hipEventCreateWithFlags(&c->ai_packed, hipEventDisableTiming));
+        TRI_HIP_TRY(hipEventRecord(c->ai_packed, c->stream));
+        TRI_HIP_TRY(tri_internal_framegen_reader(behind, c->ai_packed));
+    }
+    c->ai_w = w;
+    c->ai_h = h;
+    return TRI_OK;
+}
+
+int tri_read_ai_frame(tri_ctx* c, uint8_t* rgba8) {
+    if (!c || !rgba8) return fail(TRI_E_INVALID, "tri_read_ai_frame: null argument");
+    if (!c->ai_w || !c->d_ai) return fail(TRI_E_STATE, "tri_read_ai_frame: no AI frame uploaded");
+    const int rc = make_current(c);
+    if (rc) return rc;
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+    TRI_HIP_TRY(hipMemcpy(rgba8, c->d_ai, (size_t)c->ai_w * c->ai_h * 4, hipMemcpyDeviceToHost));
     return TRI_OK;
 }
 

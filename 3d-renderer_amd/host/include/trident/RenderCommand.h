@@ -62,7 +62,7 @@ public:
     static std::string GetFrameDatasetCaptureDirectory() { return GetRenderer().GetFrameDatasetCaptureDirectory(); }
     static void SetFrameDatasetCaptureInterval(uint32_t interval) { GetRenderer().SetFrameDatasetCaptureInterval(interval); }
     static uint32_t GetFrameDatasetCaptureInterval() { return GetRenderer().GetFrameDatasetCaptureInterval(); }
-    // The AI loop's ends (the frame generator itself lives outside the library)
+    // The AI loop's ends, for a frame generator outside the library
     static bool SetAiReadbackEnabled(bool enabled) { return GetRenderer().SetAiReadbackEnabled(enabled); }
     static bool IsAiReadbackEnabled() { return GetRenderer().IsAiReadbackEnabled(); }
     static void SetAiThrottleIntervals(uint32_t readbackMs, uint32_t inferenceMs) {
@@ -72,6 +72,10 @@ public:
     static bool SubmitAiOutput(const float* data, size_t count, const int64_t* shape, size_t rank) {
         return GetRenderer().SubmitAiOutput(data, count, shape, rank);
     }
+    // The frame generator on the device (Renderer::LoadAiModel, GetAiDebugStats, RenderCommand.h's AI debug panel)
+    static bool LoadAiModel(const std::string& path) { return GetRenderer().LoadAiModel(path); }
+    static Renderer::AiDebugStats GetAiDebugStats() { return GetRenderer().GetAiDebugStats(); }
+    static bool FinishAiInference(uint32_t timeoutMs = 5000) { return GetRenderer().FinishAiInference(timeoutMs); }
     // Poses evaluated on the device (opt-in; Renderer::SetDevicePoseEnabled)
     static void SetDevicePoseEnabled(bool enabled) { GetRenderer().SetDevicePoseEnabled(enabled); }
     static bool IsDevicePoseEnabled() { return GetRenderer().IsDevicePoseEnabled(); }

@@ -20,6 +20,7 @@
 #include "Scene.h"
 #include "AnimationStateMachine.h"
 #include "FrameDatasetRecorder.h"
+#include "FrameGenerator.h"
 #include "VideoEncoder.h"
 #include "TextRenderer.h"
 
@@ -149,7 +150,8 @@ public:
     uint64_t GetRecordedFrameCount() const { return m_VideoEncoder.GetFrameCount(); }  // of the current or last session
     // Frame readback for AI consumers (SetReadbackEnabled / ResolvePendingReadback / TryAcquireRenderedFrame,
     // Renderer.cpp:984-995, :1111-1389). SetAiReadbackEnabled stands in for m_FrameGenerator.IsInitialised() in the
-    // reference's l_ReadbackRequired (:787): the generator lives outside the library and says so here. While enabled,
+    // reference's l_ReadbackRequired (:787) for a generator that lives outside the library and says so here (the
+    // generator inside, LoadAiModel below, turns it on itself). While enabled,
     // a DrawFrame that renders the active viewport on one device converts it on the device, behind its pass, into a
     // channels-last RGBA float tensor (tri_framegrab, one slot per frame in flight; each value float(byte) *
     // (1.0f / 255.0f)), provided the readback throttle has elapsed at submission; when a present extent is set and
@@ -182,6 +184,45 @@ public:
     // The normalisation alone, in place, on whole pixels of `channels` floats (unchanged, with a log line, for a
     // channel count <= 0 or one that does not divide the element count).
     static void NormaliseAndReorderAiOutput(std::vector<float>& data, int64_t channels);
+    // The frame generator on the device (Renderer::ProcessAiFrame, Renderer.cpp:839-982; TryInitialiseAiModel /
+    // ResolveAiModelPath, :1077-1108, :1743-1782). ResolveAiModelPath tries TRIDENT_AI_MODEL, then
+    // Assets/AI/frame_generator.trifgen under the working directory and its two parents (the reference's search with
+    // the container's extension for .onnx); "" when nothing is found. While no model is initialised the search is
+    // retried once a second from ProcessAiFrame. LoadAiModel names a container explicitly: false (GetAiModelError()
+    // says why, and names the tensor) for a missing or damaged file, and while SetDeviceCount > 1. An initialised
+    // generator turns the AI readback on, as m_FrameGenerator.IsInitialised() does in the reference (:787).
+    //
+    // ProcessAiFrame runs where a frame's fence resolves its capture (DrawFrame's fence, FinishFrame), in the
+    // reference's order: (1) a finished output is packed on the device into the blend frame of every viewport target
+    // (HasAiFrame and AiBlendConfig then behave as after SubmitAiInterpolation) and, only with dataset capture on, copied
+    // to the host, normalised and recorded; (2) when the inference throttle has elapsed, no job is in flight and a
+    // fresh tensor is held, its element count is checked against the model's input (a 6-channel model, or an extent
+    // that is no multiple of 4, warns once and skips, :957-963) and (3) the held device tensor is submitted, its host
+    // copy recorded as the sample's input when capture is on. The manual path (TryAcquireRenderedFrame, SubmitAiOutput,
+    // SubmitAiInterpolation) stays as it is; a tensor either path consumed is gone for the other.
+    struct AiDebugStats {  // Renderer.h:99-110
+        bool m_ModelInitialised = false;
+        size_t m_PendingJobCount = 0;
+        uint64_t m_CompletedInferenceCount = 0;
+        double m_LastInferenceMilliseconds = 0.0;
+        double m_AverageInferenceMilliseconds = 0.0;
+        bool m_TextureReady = false;
+        float m_BlendStrength = 0.0f;
+        struct Extent { uint32_t width = 0, height = 0; } m_TextureExtent;
+        double m_ReservedMetric = 0.0;
+    };
+    std::string ResolveAiModelPath() const;
+    bool TryInitialiseAiModel();
+    bool LoadAiModel(const std::string& path);
+    const std::string& GetAiModelError() const { return m_FrameGenerator.GetLastError(); }
+    const AI::FrameGenerator& GetFrameGenerator() const { return m_FrameGenerator; }
+    // The snapshot ProcessAiFrame and FinishAiInference last took (all zeros before the first).
+    AiDebugStats GetAiDebugStats() const { return m_AiDebugStats; }
+    // Polls until the job in flight has finished and consumes it as ProcessAiFrame's step (1) does; true at once without
+    // a job. false when timeoutMs expires first (the job stays in flight).
+    bool FinishAiInference(uint32_t timeoutMs = 5000);
+    // The blend frame of the active viewport's latest target as the device holds it: width * height R8G8B8A8 texels.
+    bool ReadAiBlendFrame(std::vector<uint8_t>& rgba, uint32_t& width, uint32_t& height);
     // Frame dataset capture (Renderer.cpp:2498-2525, :6393-6400). Init honours TRIDENT_DATASET_CAPTURE_ENABLE (any
     // non-empty value) and TRIDENT_DATASET_CAPTURE_DIR (:551-576). Disabling and Shutdown write what is queued.
     void SetFrameDatasetCaptureEnabled(bool enabled);
@@ -279,6 +320,9 @@ private:
         uint32_t m_Width = 0, m_Height = 0;
         uint64_t m_GeometryGeneration = 0, m_TextureGeneration = 0, m_MaterialGeneration = 0, m_SkyboxGeneration = 0;
         uint64_t m_AiGeneration = 0;
+        // the generator's tensor is being rewritten by the job in flight, so this target (new or resized since the
+        // output was consumed) renders without the blend until the next output is packed into it
+        bool m_AiFrameDeferred = false;
         std::vector<float> m_BonePalette;  // the palette last uploaded to this viewport's context
         bool m_HasPosedSuffix = false;     // the last tri_pose_palette on this context had instances
         tri_shadow_config m_Shadow{};      // the pre-pass configuration last set on this context
@@ -456,6 +500,21 @@ private:
     bool CaptureReadbackFrame(ViewportContext& target, uint32_t slot);
     void ResolveReadbackFrame(ViewportContext& target, uint32_t slot, bool ok, bool rerendered);
     void DropGrab();
+    // the generator on the device
+    AI::FrameGenerator m_FrameGenerator;
+    AiDebugStats m_AiDebugStats{};
+    bool m_AiFromDevice = false;  // the blend frame is the generator's output tensor (packed per target), not m_AiFrame
+    tri_ctx* m_GrabHeldCtx = nullptr;  // the context whose stream made the held tensor
+    int32_t m_GrabDevice = -1;         // the grab's device
+    static constexpr std::chrono::milliseconds s_AiModelSearchInterval{1000};
+    std::chrono::steady_clock::time_point m_AiNextModelSearchTime{};
+    bool m_AiModelMissingWarningIssued = false, m_AiModelInitialiseWarningIssued = false, m_AiShapeWarningIssued = false;
+    void ProcessAiFrame();
+    void RefreshAiDebugStats();
+    void ConsumeAiOutput();  // after TryConsumeOutput: pack into every target, record the sample's output
+    bool UploadAiFrameFromDevice(ViewportContext& target);
+    tri_global_ubo TargetUniforms(const ViewportContext& target, const tri_global_ubo& ubo) const;
+    template <typename F> void ForEachTarget(F&& f);
     // dataset capture
     FrameDatasetRecorder m_FrameDatasetRecorder;
     bool m_FrameDatasetCaptureEnabled = false;

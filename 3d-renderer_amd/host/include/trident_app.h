@@ -168,6 +168,37 @@ int trident_app_acquire_frame(trident_app* app, float* out, uint64_t capacity, u
 int trident_app_readback_device_tensor(trident_app* app, const float** device, uint32_t* width, uint32_t* height, int* got);
 /* Renderer::SubmitAiOutput: TRI_OK where it returns true, TRI_E_STATE where it returns false. */
 int trident_app_submit_ai_output(trident_app* app, const float* data, uint64_t count, const int64_t* shape, uint32_t rank);
+/* ---- the frame generator on the device (Renderer::LoadAiModel, ProcessAiFrame, GetAiDebugStats) ---- */
+/* Renderer::LoadAiModel(path): TRI_OK, or TRI_E_INVALID with Renderer::GetAiModelError() (which names the damaged
+ * tensor) copied into `message` (nullable; capacity bytes with the terminator, truncated to fit); TRI_E_STATE while
+ * SetDeviceCount > 1. No device is needed: the device generator is made for the first frame's extent. */
+int trident_app_load_ai_model(trident_app* app, const char* path, char* message, uint32_t capacity);
+/* Renderer::ResolveAiModelPath: *found = 1 and the path in `path` (TRI_E_INVALID when it does not fit), else 0. */
+int trident_app_resolve_ai_model_path(trident_app* app, char* path, uint32_t capacity, int* found);
+/* Renderer::TryInitialiseAiModel: the search, then LoadAiModel on what it found. */
+int trident_app_try_initialise_ai_model(trident_app* app, int* initialised);
+/* Renderer::GetAiDebugStats (Renderer.h:99-110): the snapshot the last ProcessAiFrame / FinishAiInference took. */
+typedef struct trident_ai_debug_stats {
+    int32_t model_initialised;
+    uint32_t pending_job_count;
+    uint64_t completed_inference_count;
+    double last_inference_ms;
+    double average_inference_ms;
+    int32_t texture_ready;
+    float blend_strength;
+    uint32_t texture_width;
+    uint32_t texture_height;
+    double reserved_metric;
+} trident_ai_debug_stats;
+int trident_app_ai_debug_stats(trident_app* app, trident_ai_debug_stats* out);
+/* AI::FrameGenerator::IsInitialised, GetPrimaryInputShape and GetPrimaryOutputShape ([1, H, W, C]; H and W are -1
+ * until the first frame fixes them; all 0 without a model). Every pointer is nullable. */
+int trident_app_ai_model_info(trident_app* app, int* initialised, int64_t input_shape[4], int64_t output_shape[4]);
+/* Renderer::FinishAiInference(timeout_ms): *finished = 0 when the deadline passed first. */
+int trident_app_finish_ai_inference(trident_app* app, uint32_t timeout_ms, int* finished);
+/* Renderer::ReadAiBlendFrame: the active viewport's blend frame as the device holds it, width * height * 4 bytes
+ * (R, G, B, A) into `rgba` (capacity in bytes; TRI_E_INVALID when too small). TRI_E_STATE without a blend frame. */
+int trident_app_read_ai_blend_frame(trident_app* app, uint8_t* rgba, uint64_t capacity, uint32_t* width, uint32_t* height);
 /* Renderer::NormaliseAndReorderAiOutput alone, in place (no app, no device). */
 int trident_ai_normalise_output(float* data, uint64_t count, int64_t channels);
 

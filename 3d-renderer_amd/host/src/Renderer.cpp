@@ -17,6 +17,7 @@
 #include <cstring>
 #include <filesystem>
 #include <limits>
+#include <thread>
 
 namespace Trident {
 
@@ -361,6 +362,8 @@ bool Renderer::SetTargetText(ViewportContext& vc, uint32_t viewportId) {
 
 void Renderer::Shutdown() {
     StopRecording();  // the frames in flight reach the file, which is finalised
+    m_FrameGenerator.Shutdown();  // (waits for a job in flight)
+    m_AiFromDevice = false;
     DestroyViewportTargets();
     m_FrameDatasetRecorder.Flush();  // every queued sample is on disk
     m_PendingFrameReadback.clear();
@@ -425,6 +428,11 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
     if (m_AiReadback && devs.size() > 1) {
         LogError("SetDeviceCount", "multi-device viewports have no AI readback: it was turned off");
         SetAiReadbackEnabled(false);
+    }
+    if (devs.size() > 1 && m_FrameGenerator.IsInitialised()) {  // ... and with it no generator
+        LogError("SetDeviceCount", "multi-device viewports have no frame generator: the model was unloaded");
+        m_FrameGenerator.Shutdown();
+        if (m_AiFromDevice) SubmitAiInterpolation(nullptr, 0, 0, 0);
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
@@ -1102,6 +1110,7 @@ void Renderer::UpdateUniformBuffer(const Camera* camera, tri_global_ubo& g) cons
 
 bool Renderer::SubmitAiInterpolation(const float* pixels, uint32_t width, uint32_t height, uint32_t channels) {
     ++m_AiGeneration;
+    m_AiFromDevice = false;
     if (!pixels || width == 0 || height == 0 || channels == 0) {  // no frame: the texture is not ready, no blend
         m_AiFrame.clear();
         m_AiWidth = m_AiHeight = 0;
@@ -1308,7 +1317,20 @@ bool Renderer::PrepareViewport(ViewportContext& vc) {
         }
         vc.m_SkyboxGeneration = m_SkyboxGeneration;
     }
-    if (vc.m_AiGeneration != m_AiGeneration) {  // the AI frame texture (UploadAiInterpolationToGpu)
+    vc.m_AiFrameDeferred = false;
+    if (vc.m_AiGeneration != m_AiGeneration && m_AiFromDevice && m_AiWidth && vc.m_Ctx) {
+        // a target that was not there when the output was consumed (new, resized): the tensor is still the generator's.
+        // While the next job is rewriting it, the frame path does not wait: this target renders without the blend and
+        // ConsumeAiOutput packs the next output into it. A generator that has lost the tensor with no job in flight (a
+        // failed submit, a device error) ends the device blend for every target, as SubmitAiInterpolation(nullptr) does.
+        if (m_FrameGenerator.HasJobInFlight()) {
+            vc.m_AiFrameDeferred = true;
+        } else if (!UploadAiFrameFromDevice(vc)) {
+            LogError("AI frame generator", "the generated frame is gone: the blend is off until the next output");
+            SubmitAiInterpolation(nullptr, 0, 0, 0);
+        }
+    }
+    if (vc.m_AiGeneration != m_AiGeneration && !vc.m_AiFrameDeferred) {  // the AI frame texture (UploadAiInterpolationToGpu)
         if (t.AiFrame(m_AiWidth ? m_AiFrame.data() : nullptr, m_AiWidth, m_AiHeight) != TRI_OK) {
             LogError("AI frame texture", tri_last_error());
             return false;
@@ -1326,6 +1348,14 @@ bool Renderer::PrepareViewport(ViewportContext& vc) {
         vc.m_TextureGeneration = m_TextureGeneration;
     }
     return true;
+}
+
+// The uniform block as one target gets it: without the blend while the target's texture waits for the generator's next
+// output (PrepareViewport), or when an earlier pass of this frame found the generated frame gone.
+tri_global_ubo Renderer::TargetUniforms(const ViewportContext& vc, const tri_global_ubo& ubo) const {
+    tri_global_ubo out = ubo;
+    if (vc.m_AiFrameDeferred || !HasAiFrame()) std::memset(out.ai_blend_config, 0, sizeof out.ai_blend_config);
+    return out;
 }
 
 bool Renderer::BuildFrameInputs(uint32_t viewportId, tri_global_ubo& ubo, std::vector<tri_draw>& draws) {
@@ -1406,7 +1436,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         tri_global_ubo ubo;
         UpdateUniformBuffer(GetActiveCamera(vc), ubo);
         if (!SetTargetText(vc, id)) LogError("DrawFrame", "the text overlay of this frame is missing");
-        if (!SubmitTarget(vc, ubo, draws, shadow, shadowOn)) return;
+        if (!SubmitTarget(vc, TargetUniforms(vc, ubo), draws, shadow, shadowOn)) return;
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
         // AI readback: the active viewport's tensor, likewise, when the readback throttle has elapsed (ResolvePending-
@@ -1442,7 +1472,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         if (PrepareViewport(m_LegacyTarget)) {
             tri_global_ubo ubo = lastUbo;
             if (submitted.empty()) UpdateUniformBuffer(GetActiveCamera(), ubo);
-            if (SubmitTarget(m_LegacyTarget, ubo, draws, shadow, shadowOn)) {
+            if (SubmitTarget(m_LegacyTarget, TargetUniforms(m_LegacyTarget, ubo), draws, shadow, shadowOn)) {
                 legacy = &m_LegacyTarget;
                 submitted.push_back(legacy);
             }
@@ -1536,6 +1566,7 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
         m_PresentedWidth = p.m_BlitWidth;  // the blit's destination extent
         m_PresentedHeight = p.m_BlitHeight;
     }
+    ProcessAiFrame();  // (Renderer.cpp:789: after the readback has resolved)
 }
 
 // Renderer.cpp:6171-6284. The session starts before anything is resized, so a refused start changes nothing.
@@ -1689,6 +1720,7 @@ void Renderer::ReleaseHeldReadbackSlot(bool keepPending) {
     m_GrabHeldSlot = -1;
     m_GrabDeviceTensor = nullptr;
     m_GrabHostTensor = nullptr;
+    m_GrabHeldCtx = nullptr;
 }
 
 // The active viewport's frame -> grab slot `slot` (asynchronous). The grab is made here, once the target exists: one
@@ -1705,6 +1737,7 @@ bool Renderer::CaptureReadbackFrame(ViewportContext& vc, uint32_t slot) {
             return false;
         }
         m_GrabWidth = vc.m_Width;
+        m_GrabDevice = vc.m_Image.device;
         m_GrabHeight = vc.m_Height;
     }
     if (tri_framegrab_capture(m_Grab, slot, vc.m_Ctx) != TRI_OK) {
@@ -1737,6 +1770,7 @@ void Renderer::ResolveReadbackFrame(ViewportContext& vc, uint32_t slot, bool ok,
     m_GrabHeldSlot = (int32_t)slot;
     m_GrabDeviceTensor = device;
     m_GrabHostTensor = host;
+    m_GrabHeldCtx = vc.m_Ctx;
     m_PendingInSlot = true;
 }
 
@@ -1798,6 +1832,208 @@ bool Renderer::SubmitAiOutput(const float* data, size_t count, const int64_t* sh
         return false;
     }
     return SubmitAiInterpolation(output.data(), (uint32_t)canonical[2], (uint32_t)canonical[1], (uint32_t)canonical[3]);
+}
+
+// Renderer.cpp:1743-1782, with the container's extension.
+std::string Renderer::ResolveAiModelPath() const {
+    namespace fs = std::filesystem;
+    std::error_code ec;
+    const char* env = std::getenv("TRIDENT_AI_MODEL");
+    if (env && *env) {
+        const fs::path candidate{env};
+        if (fs::exists(candidate, ec)) return fs::absolute(candidate, ec).string();
+        LogError("TRIDENT_AI_MODEL names a file that does not exist; trying the default search paths", env);
+    }
+    const fs::path cwd = fs::current_path(ec);
+    if (ec) return {};
+    for (const fs::path& root : {cwd, cwd.parent_path(), cwd.parent_path().parent_path()}) {
+        if (root.empty()) continue;
+        const fs::path candidate = root / "Assets" / "AI" / "frame_generator.trifgen";
+        if (fs::exists(candidate, ec)) return fs::absolute(candidate, ec).string();
+    }
+    return {};
+}
+
+bool Renderer::TryInitialiseAiModel() {  // Renderer.cpp:1077-1108
+    const std::string path = ResolveAiModelPath();
+    if (path.empty()) {
+        if (!m_AiModelMissingWarningIssued) {
+            LogError("AI frame generator", "no model found: rendering continues without AI augmentation until one is provided");
+            m_AiModelMissingWarningIssued = true;
+            m_AiModelInitialiseWarningIssued = false;
+        }
+        return false;
+    }
+    if (LoadAiModel(path)) {
+        m_AiModelMissingWarningIssued = m_AiModelInitialiseWarningIssued = false;
+        return true;
+    }
+    if (!m_AiModelInitialiseWarningIssued) {
+        LogError("AI frame generator failed to initialise; frames skip AI processing until a valid model is supplied",
+                 (path + ": " + m_FrameGenerator.GetLastError()).c_str());
+        m_AiModelInitialiseWarningIssued = true;
+    }
+    return false;
+}
+
+bool Renderer::LoadAiModel(const std::string& path) {
+    if (m_Devices.size() > 1) {
+        LogError("AI frame generator", "multi-device viewports (SetDeviceCount > 1) have no frame generator");
+        return false;
+    }
+    // a file that is refused leaves the running model, its job in flight and its output alone; one that is accepted
+    // waits for that job and drops it with the old generator (FrameGenerator::Initialise)
+    if (!m_FrameGenerator.Initialise(path)) return false;
+    if (m_AiFromDevice) SubmitAiInterpolation(nullptr, 0, 0, 0);  // the old model's tensor went with it
+    m_AiShapeWarningIssued = false;
+    return SetAiReadbackEnabled(true);  // l_ReadbackRequired (Renderer.cpp:787)
+}
+
+void Renderer::RefreshAiDebugStats() {
+    m_AiDebugStats.m_ModelInitialised = m_FrameGenerator.IsInitialised();
+    m_AiDebugStats.m_BlendStrength = m_AiBlendStrength;
+    m_AiDebugStats.m_TextureReady = HasAiFrame();
+    m_AiDebugStats.m_TextureExtent.width = m_AiWidth;
+    m_AiDebugStats.m_TextureExtent.height = m_AiHeight;
+    m_AiDebugStats.m_PendingJobCount = m_FrameGenerator.GetPendingJobCount();
+    m_AiDebugStats.m_CompletedInferenceCount = m_FrameGenerator.GetCompletedInferenceCount();
+    m_AiDebugStats.m_LastInferenceMilliseconds = m_FrameGenerator.GetLastInferenceMilliseconds();
+    m_AiDebugStats.m_AverageInferenceMilliseconds = m_FrameGenerator.GetAverageInferenceMilliseconds();
+}
+
+template <typename F>
+void Renderer::ForEachTarget(F&& f) {
+    for (auto& it : m_Viewports) f(it.second);
+    for (auto& it : m_RingTargets)
+        for (ViewportContext& vc : it.second) f(vc);
+    f(m_LegacyTarget);
+}
+
+bool Renderer::UploadAiFrameFromDevice(ViewportContext& vc) {
+    const float* tensor = nullptr;
+    uint32_t w = 0, h = 0;
+    if (!vc.m_Ctx || !m_FrameGenerator.GetOutputDevice(&tensor, w, h)) return false;
+    if (tri_upload_ai_frame_device(vc.m_Ctx, tensor, w, h, 3, m_FrameGenerator.GetHandle()) != TRI_OK) return false;
+    vc.m_AiGeneration = m_AiGeneration;
+    return true;
+}
+
+// A finished output becomes the blend frame: packed on the device into every single-device target there is, on the
+// target's own stream behind the frames it has queued (a target made later fetches it in PrepareViewport).
+void Renderer::ConsumeAiOutput() {
+    const float* tensor = nullptr;
+    uint32_t w = 0, h = 0;
+    if (!m_FrameGenerator.GetOutputDevice(&tensor, w, h)) return;
+    ++m_AiGeneration;
+    m_AiFrame.clear();
+    m_AiWidth = w;
+    m_AiHeight = h;
+    m_AiFromDevice = true;
+    ForEachTarget([&](ViewportContext& vc) {
+        if (vc.m_Ctx && !UploadAiFrameFromDevice(vc)) LogError("AI frame texture", tri_last_error());
+    });
+    if (m_FrameDatasetCaptureEnabled) {  // the normalised tensor, as SubmitAiOutput records it (Renderer.cpp:917-924)
+        std::vector<float> output;
+        if (m_FrameGenerator.ReadOutput(output)) {
+            NormaliseAndReorderAiOutput(output, 3);
+            const int64_t shape[4] = {1, (int64_t)h, (int64_t)w, 3};
+            m_FrameDatasetRecorder.RecordAiOutput(output.data(), output.size(), shape, 4);
+        } else {
+            LogError("AI output", tri_last_error());
+        }
+    }
+    RefreshAiDebugStats();
+}
+
+void Renderer::ProcessAiFrame() {  // Renderer.cpp:839-982
+    if (!m_FrameGenerator.IsInitialised()) {
+        m_AiDebugStats.m_ModelInitialised = false;
+        m_AiDebugStats.m_BlendStrength = m_AiBlendStrength;
+        m_AiDebugStats.m_TextureReady = HasAiFrame();
+        m_AiDebugStats.m_TextureExtent.width = m_AiWidth;
+        m_AiDebugStats.m_TextureExtent.height = m_AiHeight;
+        const auto now = std::chrono::steady_clock::now();
+        if (now >= m_AiNextModelSearchTime) {  // a model dropped on disk starts the AI path without a restart
+            TryInitialiseAiModel();
+            m_AiNextModelSearchTime = now + s_AiModelSearchInterval;
+        }
+        if (!m_FrameGenerator.IsInitialised()) {
+            m_AiDebugStats.m_PendingJobCount = 0;
+            m_AiDebugStats.m_CompletedInferenceCount = 0;
+            m_AiDebugStats.m_LastInferenceMilliseconds = m_AiDebugStats.m_AverageInferenceMilliseconds = 0.0;
+        } else {
+            RefreshAiDebugStats();
+        }
+        return;
+    }
+    // (1) a finished output first, so that the blend reacts at once
+    if (m_FrameGenerator.TryConsumeOutput()) ConsumeAiOutput();
+    RefreshAiDebugStats();
+    // (2) one job at a time: while one is in flight the held tensor stays pending and the throttle is not armed
+    if (m_FrameGenerator.HasJobInFlight()) return;
+    if (!AiInferenceThrottleElapsed()) return;
+    if (!m_PendingInSlot || !m_GrabDeviceTensor || !m_GrabHeldCtx) return;  // no fresh tensor: the last output stays
+    m_PendingInSlot = false;  // acquired (TryAcquireRenderedFrame, :943)
+    const size_t expected = (size_t)m_FrameReadbackWidth * m_FrameReadbackHeight * m_FrameGenerator.GetInputChannels();
+    if (FrameReadbackCount() != expected) {  // :957-963
+        if (!m_AiShapeWarningIssued) {
+            const std::string msg = "the frame has " + std::to_string(FrameReadbackCount()) + " elements, the model expects " +
+                                    std::to_string(expected) + ": inference is skipped";
+            LogError("AI frame generator", msg.c_str());
+            m_AiShapeWarningIssued = true;
+        }
+        return;
+    }
+    void* stream = nullptr;
+    if (tri_get_stream(m_GrabHeldCtx, &stream) != TRI_OK) return;
+    // (3) the tensor where the grab made it; the copy is ordered on the stream that made it, so the slot may serve again
+    if (!m_FrameGenerator.ProcessFrame(m_GrabDevice, m_GrabDeviceTensor, m_FrameReadbackWidth, m_FrameReadbackHeight,
+                                       s_FrameReadbackChannelCount, stream)) {
+        if (!m_AiShapeWarningIssued) {
+            LogError("AI frame generator rejected the frame; the previous output stays", m_FrameGenerator.GetLastError().c_str());
+            m_AiShapeWarningIssued = true;
+        }
+        RefreshAiDebugStats();
+        return;
+    }
+    if (m_FrameDatasetCaptureEnabled && m_GrabHostTensor) {  // the exact tensor the generator got (:973-977)
+        const int64_t shape[4] = {1, (int64_t)m_FrameReadbackHeight, (int64_t)m_FrameReadbackWidth,
+                                  (int64_t)s_FrameReadbackChannelCount};
+        m_FrameDatasetRecorder.RecordInputFrame(m_GrabHostTensor, FrameReadbackCount(), m_FrameReadbackWidth,
+                                                m_FrameReadbackHeight, s_FrameReadbackChannelCount, shape, 4);
+    }
+    RefreshAiDebugStats();
+}
+
+bool Renderer::FinishAiInference(uint32_t timeoutMs) {
+    if (!m_FrameGenerator.HasJobInFlight()) return true;
+    const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(timeoutMs);
+    for (;;) {
+        if (m_FrameGenerator.TryConsumeOutput()) {
+            ConsumeAiOutput();
+            return true;
+        }
+        if (!m_FrameGenerator.HasJobInFlight()) {  // a device error lost the job
+            RefreshAiDebugStats();
+            return false;
+        }
+        if (std::chrono::steady_clock::now() >= deadline) return false;
+        std::this_thread::sleep_for(std::chrono::microseconds(100));
+    }
+}
+
+bool Renderer::ReadAiBlendFrame(std::vector<uint8_t>& rgba, uint32_t& width, uint32_t& height) {
+    FinishFrame();
+    const ViewportContext* vc = LatestTarget(m_ActiveViewportId);
+    if (!vc || !vc->m_Ctx || !HasAiFrame() || vc->m_AiGeneration != m_AiGeneration) return false;
+    rgba.resize((size_t)m_AiWidth * m_AiHeight * 4);
+    if (tri_read_ai_frame(vc->m_Ctx, rgba.data()) != TRI_OK) {
+        LogError("AI frame texture", tri_last_error());
+        return false;
+    }
+    width = m_AiWidth;
+    height = m_AiHeight;
+    return true;
 }
 
 void Renderer::SetFrameDatasetCaptureEnabled(bool enabled) {

@@ -815,6 +815,95 @@ int trident_app_submit_ai_output(trident_app* app, const float* data, uint64_t c
     return Guard(app, [&] { return app->renderer.SubmitAiOutput(data, (size_t)count, shape, rank) ? TRI_OK : TRI_E_STATE; });
 }
 
+int trident_app_load_ai_model(trident_app* app, const char* path, char* message, uint32_t capacity) {
+    return Guard(app, [&] {
+        if (message && capacity) message[0] = '\0';
+        if (!path) return TRI_E_INVALID;
+        const bool multi = app->renderer.GetDeviceCount() > 1;  // refused before the file is looked at
+        if (app->renderer.LoadAiModel(path)) return TRI_OK;
+        if (multi) return TRI_E_STATE;
+        const std::string& err = app->renderer.GetAiModelError();
+        if (message && capacity) {
+            const size_t n = std::min<size_t>(err.size(), capacity - 1);
+            std::memcpy(message, err.data(), n);
+            message[n] = '\0';
+        }
+        return TRI_E_INVALID;
+    });
+}
+
+int trident_app_resolve_ai_model_path(trident_app* app, char* path, uint32_t capacity, int* found) {
+    return Guard(app, [&] {
+        const std::string p = app->renderer.ResolveAiModelPath();
+        if (found) *found = p.empty() ? 0 : 1;
+        if (path && capacity) path[0] = '\0';
+        if (p.empty() || !path) return TRI_OK;
+        if (p.size() + 1 > capacity) return TRI_E_INVALID;
+        std::memcpy(path, p.c_str(), p.size() + 1);
+        return TRI_OK;
+    });
+}
+
+int trident_app_try_initialise_ai_model(trident_app* app, int* initialised) {
+    return Guard(app, [&] {
+        const bool ok = app->renderer.TryInitialiseAiModel();
+        if (initialised) *initialised = ok ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_ai_debug_stats(trident_app* app, trident_ai_debug_stats* out) {
+    return Guard(app, [&] {
+        if (!out) return TRI_E_INVALID;
+        const Renderer::AiDebugStats s = app->renderer.GetAiDebugStats();
+        out->model_initialised = s.m_ModelInitialised ? 1 : 0;
+        out->pending_job_count = (uint32_t)s.m_PendingJobCount;
+        out->completed_inference_count = s.m_CompletedInferenceCount;
+        out->last_inference_ms = s.m_LastInferenceMilliseconds;
+        out->average_inference_ms = s.m_AverageInferenceMilliseconds;
+        out->texture_ready = s.m_TextureReady ? 1 : 0;
+        out->blend_strength = s.m_BlendStrength;
+        out->texture_width = s.m_TextureExtent.width;
+        out->texture_height = s.m_TextureExtent.height;
+        out->reserved_metric = s.m_ReservedMetric;
+        return TRI_OK;
+    });
+}
+
+int trident_app_ai_model_info(trident_app* app, int* initialised, int64_t input_shape[4], int64_t output_shape[4]) {
+    return Guard(app, [&] {
+        const AI::FrameGenerator& g = app->renderer.GetFrameGenerator();
+        if (initialised) *initialised = g.IsInitialised() ? 1 : 0;
+        const std::vector<int64_t> in = g.GetPrimaryInputShape(), out = g.GetPrimaryOutputShape();
+        for (size_t i = 0; i < 4; ++i) {
+            if (input_shape) input_shape[i] = i < in.size() ? in[i] : 0;
+            if (output_shape) output_shape[i] = i < out.size() ? out[i] : 0;
+        }
+        return TRI_OK;
+    });
+}
+
+int trident_app_finish_ai_inference(trident_app* app, uint32_t timeout_ms, int* finished) {
+    return Guard(app, [&] {
+        const bool ok = app->renderer.FinishAiInference(timeout_ms);
+        if (finished) *finished = ok ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_read_ai_blend_frame(trident_app* app, uint8_t* rgba, uint64_t capacity, uint32_t* width, uint32_t* height) {
+    return Guard(app, [&] {
+        std::vector<uint8_t> px;
+        uint32_t w = 0, h = 0;
+        if (!app->renderer.ReadAiBlendFrame(px, w, h)) return TRI_E_STATE;
+        if (width) *width = w;
+        if (height) *height = h;
+        if (!rgba || capacity < px.size()) return TRI_E_INVALID;
+        std::memcpy(rgba, px.data(), px.size());
+        return TRI_OK;
+    });
+}
+
 int trident_ai_normalise_output(float* data, uint64_t count, int64_t channels) {
     if (count && !data) return TRI_E_INVALID;
     try {

@@ -212,6 +212,22 @@ TRI_XFER_ID_BYTES = 128
 TRI_GRAB_HOST_COPY = 0x1  # tri_framegrab_create
 
 
+# the frame generator (include/tri_raster.h)
+TRI_NN_CONV3X3, TRI_NN_CONVT4X4 = 0, 1
+TRI_NN_ACT_NONE, TRI_NN_ACT_RELU, TRI_NN_ACT_SIGMOID = 0, 1, 2
+TRI_NN_MAX_CHANNELS = 1024
+TRI_MAX_DIM = 8192
+
+
+class TriNnConvDesc(C.Structure):
+    _fields_ = [("op", C.c_uint32), ("stride", C.c_uint32), ("in_height", C.c_uint32), ("in_width", C.c_uint32),
+                ("in_channels", C.c_uint32), ("out_channels", C.c_uint32), ("activation", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(TriNnConvDesc) == 32
+
+
 # text overlay (include/tri_raster.h; the scan chunk, per-round list capacity and bin edge of k_text_overlay are
 # csrc/raster_launch.h's)
 TRI_MAX_TEXT_QUADS = 65536
@@ -348,6 +364,21 @@ CABI_FUNCTIONS = [
     ("tri_framegrab_capture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("tri_framegrab_wait", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("tri_framegrab_release", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("tri_nn_pack_weights", C.c_int, [C.POINTER(TriNnConvDesc), C.c_void_p, C.c_void_p]),
+    ("tri_nn_conv", C.c_int, [C.POINTER(TriNnConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("tri_framegen_create", C.c_int, [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_framegen_destroy", C.c_int, [C.c_void_p]),
+    ("tri_framegen_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("tri_framegen_submit", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("tri_framegen_poll", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    ("tri_framegen_wait", C.c_int, [C.c_void_p]),
+    ("tri_framegen_output", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("tri_framegen_read_output", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tri_framegen_last_ms", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("tri_upload_ai_frame_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    ("tri_read_ai_frame", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tri_get_stream", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     ("tri_font_create", C.c_int, [C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("tri_font_destroy", C.c_int, [C.c_void_p]),
     ("tri_set_text", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),

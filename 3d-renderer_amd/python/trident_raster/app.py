@@ -94,6 +94,14 @@ _APP_FUNCTIONS = [
                                                      C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     ("trident_app_submit_ai_output", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32]),
     ("trident_ai_normalise_output", C.c_int, [C.c_void_p, C.c_uint64, C.c_int64]),
+    ("trident_app_load_ai_model", C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_uint32]),
+    ("trident_app_resolve_ai_model_path", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_int)]),
+    ("trident_app_try_initialise_ai_model", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    ("trident_app_ai_debug_stats", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("trident_app_ai_model_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64 * 4), C.POINTER(C.c_int64 * 4)]),
+    ("trident_app_finish_ai_inference", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    ("trident_app_read_ai_blend_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_uint32)]),
     ("trident_dataset_create", C.c_int, [C.POINTER(C.c_void_p)]),
     ("trident_dataset_destroy", None, [C.c_void_p]),
     ("trident_dataset_set_directory", C.c_int, [C.c_void_p, C.c_char_p]),
@@ -167,6 +175,13 @@ _APP_FUNCTIONS = [
     ("trident_sm_layer_state", C.c_int, [C.c_uint64, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32, C.POINTER(C.c_float),
                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 ]
+
+class AiDebugStats(C.Structure):  # trident_ai_debug_stats
+    _fields_ = [("model_initialised", C.c_int32), ("pending_job_count", C.c_uint32),
+                ("completed_inference_count", C.c_uint64), ("last_inference_ms", C.c_double),
+                ("average_inference_ms", C.c_double), ("texture_ready", C.c_int32), ("blend_strength", C.c_float),
+                ("texture_width", C.c_uint32), ("texture_height", C.c_uint32), ("reserved_metric", C.c_double)]
+
 
 _lib = None
 
@@ -569,6 +584,54 @@ class TridentApp:
         _check(self._lib.trident_app_readback_device_tensor(self._h, C.byref(p), C.byref(w), C.byref(h), C.byref(got)),
                "readback_device_tensor")
         return (p.value, w.value, h.value) if got.value else None
+
+    # ---- the frame generator on the device ----
+    def load_ai_model(self, path):
+        """Renderer::LoadAiModel: raises TriError (TRI_E_INVALID, with the parser's message) for a damaged container."""
+        buf = C.create_string_buffer(512)
+        rc = self._lib.trident_app_load_ai_model(self._h, os.fsencode(path), buf, len(buf))
+        if rc != abi.TRI_OK:
+            raise TriError(rc, "load_ai_model: " + buf.value.decode(errors="replace"))
+
+    def resolve_ai_model_path(self):
+        """Renderer::ResolveAiModelPath: the path, or None."""
+        buf, found = C.create_string_buffer(4096), C.c_int()
+        _check(self._lib.trident_app_resolve_ai_model_path(self._h, buf, len(buf), C.byref(found)), "resolve_ai_model_path")
+        return os.fsdecode(buf.value) if found.value else None
+
+    def try_initialise_ai_model(self):
+        ok = C.c_int()
+        _check(self._lib.trident_app_try_initialise_ai_model(self._h, C.byref(ok)), "try_initialise_ai_model")
+        return bool(ok.value)
+
+    def ai_debug_stats(self):
+        """Renderer::GetAiDebugStats as a dict."""
+        s = AiDebugStats()
+        _check(self._lib.trident_app_ai_debug_stats(self._h, C.byref(s)), "ai_debug_stats")
+        return {name: getattr(s, name) for name, _ in AiDebugStats._fields_}
+
+    def ai_model_info(self):
+        """(initialised, input shape, output shape) of the frame generator."""
+        ok, i, o = C.c_int(), (C.c_int64 * 4)(), (C.c_int64 * 4)()
+        _check(self._lib.trident_app_ai_model_info(self._h, C.byref(ok), C.byref(i), C.byref(o)), "ai_model_info")
+        return bool(ok.value), list(i), list(o)
+
+    def finish_ai_inference(self, timeout_ms=5000):
+        """Renderer::FinishAiInference: False when the deadline passed first."""
+        ok = C.c_int()
+        _check(self._lib.trident_app_finish_ai_inference(self._h, timeout_ms, C.byref(ok)), "finish_ai_inference")
+        return bool(ok.value)
+
+    def read_ai_blend_frame(self):
+        """The active viewport's blend frame on the device, uint8 [h, w, 4] (R, G, B, A), or None without one."""
+        w, h = C.c_uint32(), C.c_uint32()
+        rc = self._lib.trident_app_read_ai_blend_frame(self._h, None, 0, C.byref(w), C.byref(h))
+        if rc == abi.TRI_E_STATE:
+            return None
+        out = np.empty((h.value, w.value, 4), np.uint8)
+        _check(self._lib.trident_app_read_ai_blend_frame(self._h, out.ctypes.data, out.size, C.byref(w), C.byref(h)),
+               "read_ai_blend_frame")
+        return out
 
     def submit_ai_output(self, data, shape):
         """Renderer::SubmitAiOutput: the generator's output (any float array) with its tensor shape -> accepted."""

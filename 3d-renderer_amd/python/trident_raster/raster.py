@@ -157,6 +157,18 @@ class TriRaster:
             raise ValueError("AI frame must be uint8 [h, w, 4]")
         _check(_lib.tri_upload_ai_frame(self._ctx, _ptr(f), f.shape[1], f.shape[0]))
 
+    def upload_ai_frame_device(self, tensor_ptr, width, height, channels, behind=None):
+        """tri_upload_ai_frame_device: pack a [height, width, channels] float32 tensor on this context's device into the
+        blend frame, on the context's stream (`behind`: a FrameGenerator whose last job the stream waits for)."""
+        _check(_lib.tri_upload_ai_frame_device(self._ctx, C.c_void_p(tensor_ptr) if tensor_ptr else None, width, height,
+                                               channels, behind._g if behind is not None else None))
+
+    def read_ai_frame(self, width, height):
+        """The blend frame as uint8 [height, width, 4] (R, G, B, A), after the context's stream has drained."""
+        out = np.empty((height, width, 4), dtype=np.uint8)
+        _check(_lib.tri_read_ai_frame(self._ctx, _ptr(out)))
+        return out
+
     def upload_skybox(self, faces):
         """faces: uint8 [6, n, n, 4] sRGB (+X,-X,+Y,-Y,+Z,-Z), or None to remove the skybox."""
         if faces is None:
@@ -558,6 +570,78 @@ def copy_device_to_host(ptr, nbytes, device=0):
     assert hip.hipSetDevice(device) == 0
     assert hip.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), nbytes, 2) == 0  # hipMemcpyDeviceToHost
     return out
+
+
+def nn_pack_weights(desc, torch_weights):
+    """tri_nn_pack_weights: torch's Conv2d / ConvTranspose2d weights (float32 array) in tri_nn_conv's layout."""
+    load_library()
+    src = np.ascontiguousarray(torch_weights, dtype=np.float32)
+    out = np.empty(src.size, dtype=np.float32)
+    _check(_lib.tri_nn_pack_weights(C.byref(desc), _ptr(src), _ptr(out)))
+    return out
+
+
+class FrameGenerator:
+    """tri_framegen: the interpolation network for one frozen extent on one device, from a weights container (bytes).
+    One job at a time, asynchronous on the generator's own stream."""
+
+    def __init__(self, container, width, height, device=-1):
+        lib = load_library()
+        g = C.c_void_p()
+        blob = bytes(container)
+        _check(lib.tri_framegen_create(device, blob, len(blob), width, height, C.byref(g)))
+        self._g = g
+        self.width, self.height = width, height
+        cin = C.c_uint32()
+        _check(lib.tri_framegen_info(g, C.byref(cin), None, None))
+        self.input_channels = cin.value
+
+    def close(self):
+        if self._g:
+            _lib.tri_framegen_destroy(self._g)  # waits for a job in flight
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def submit(self, input_ptr, stream_ptr=None):
+        """input_ptr: [height, width, input_channels] float32 on the device; copied on stream_ptr (None: the null stream)."""
+        _check(_lib.tri_framegen_submit(self._g, C.c_void_p(input_ptr) if input_ptr else None,
+                                        C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def poll(self):
+        """True once per job, when it has finished; never blocks."""
+        done = C.c_int32()
+        _check(_lib.tri_framegen_poll(self._g, C.byref(done)))
+        return bool(done.value)
+
+    def wait(self):
+        _check(_lib.tri_framegen_wait(self._g))
+
+    def output_pointer(self):
+        p = C.c_void_p()
+        _check(_lib.tri_framegen_output(self._g, C.byref(p)))
+        return p.value
+
+    def read_output(self):
+        """The last finished job's output, float32 [height, width, 3]."""
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        _check(_lib.tri_framegen_read_output(self._g, _ptr(out)))
+        return out
+
+    def last_ms(self):
+        ms = C.c_float()
+        _check(_lib.tri_framegen_last_ms(self._g, C.byref(ms)))
+        return ms.value
 
 
 class TriGroup:

@@ -616,6 +616,92 @@ int tri_framegrab_capture(tri_framegrab* grab, uint32_t slot, tri_ctx* ctx);
 int tri_framegrab_wait(tri_framegrab* grab, uint32_t slot, const float** host, const float** device);
 int tri_framegrab_release(tri_framegrab* grab, uint32_t slot);
 
+/* ---- the frame generator (AI::FrameGenerator's InterpolationUNet, Renderer::ProcessAiFrame, Renderer.cpp:839-982) ----
+ * The reference runs the network in an ONNX Runtime session on the host side of a readback. Here its 20 convolutions
+ * are HIP kernels on the f32-input matrix cores, float32 throughout, on channels-last ([H, W, C]) device tensors.
+ *
+ * tri_nn_conv is one layer: an implicit GEMM (M = the output pixels of a spatial tile, N = output channels,
+ * K = taps x input channels) with the epilogue
+ *     y = act(acc * scale[c] + shift[c] + res1) + res2
+ * where res1 and res2 (output-shaped tensors) may be NULL. A bias is scale 1, shift = bias; an eval-mode BatchNorm is
+ * scale = gamma / sqrt(var + 1e-5), shift = beta - mean * scale.
+ *   TRI_NN_CONV3X3   3 x 3, padding 1, stride 1 or 2: the output is ceil(H / stride) x ceil(W / stride).
+ *   TRI_NN_CONVT4X4  torch's ConvTranspose2d(kernel 4, stride 2, padding 1): the output is 2H x 2W; stride must be 2.
+ * packed_weights is what tri_nn_pack_weights (host only, no device) makes of torch's layout — Conv2d
+ * [Cout][Cin][3][3], ConvTranspose2d [Cin][Cout][4][4] — the same number of floats: [ky][kx][ci][co], and for the
+ * transposed convolution [output parity y][x][tap a][b][ci][co] with ky = 1 - py + 2a, kx = 1 - px + 2b (no flip).
+ * Every pointer of tri_nn_conv is device memory of the current device, 4-B aligned; the launch is stream-ordered on
+ * hip_stream (NULL = the null stream). TRI_E_INVALID: a null or misaligned pointer, an unknown op, stride or
+ * activation, an extent outside 1..TRI_MAX_DIM, channels outside 1..TRI_NN_MAX_CHANNELS. */
+#define TRI_NN_CONV3X3 0u
+#define TRI_NN_CONVT4X4 1u
+#define TRI_NN_ACT_NONE 0u
+#define TRI_NN_ACT_RELU 1u
+#define TRI_NN_ACT_SIGMOID 2u
+#define TRI_NN_MAX_CHANNELS 1024
+typedef struct tri_nn_conv_desc {
+    uint32_t op;           /* TRI_NN_CONV3X3 / TRI_NN_CONVT4X4 */
+    uint32_t stride;       /* 1 or 2 (the transposed convolution: 2) */
+    uint32_t in_height;
+    uint32_t in_width;
+    uint32_t in_channels;
+    uint32_t out_channels;
+    uint32_t activation;   /* TRI_NN_ACT_* */
+    uint32_t reserved;     /* 0 */
+} tri_nn_conv_desc;
+int tri_nn_pack_weights(const tri_nn_conv_desc* desc, const float* torch_weights, float* packed_weights);
+int tri_nn_conv(const tri_nn_conv_desc* desc, const void* input, const void* packed_weights, const void* scale,
+                const void* shift, const void* res1, const void* res2, void* output, void* hip_stream);
+
+/* A generator owns the network's weights and every activation for one frozen extent on one device (-1 = current),
+ * and a stream of its own at the device's lowest priority (the job runs behind the frames: their kernels do not queue
+ * behind its workgroups). `weights` is a weights container (tools/export_frame_generator.py writes it from
+ * a checkpoint) in host memory. width and height are multiples of 4 within 4..TRI_MAX_DIM (two stride-2 levels with
+ * additive skips); the container's input channels are 1..8; the output is [height][width][3].
+ *   tri_framegen_submit   copies device_input_nhwc ([height][width][input channels] floats on the generator's device)
+ *                         into the generator's own buffer on producer_stream (NULL = the null stream), so later work on
+ *                         that stream may reuse the source, then runs the 20 layers on the generator's stream behind an
+ *                         event. One job at a time: TRI_E_STATE while a job is in flight, which it is from the submit
+ *                         until tri_framegen_poll reports it done or tri_framegen_wait returns.
+ *   tri_framegen_poll     never blocks. *done = 1 once per job, when it has finished; 0 otherwise (also before any
+ *                         submit).
+ *   tri_framegen_wait     blocks until the job in flight has finished. TRI_E_STATE when nothing was ever submitted.
+ *                         A device error in poll or wait (TRI_E_HIP) loses the job: the generator's stream is drained,
+ *                         there is no output, and the next submit is accepted.
+ *   tri_framegen_output   the device tensor of the last finished job; TRI_E_STATE before one has finished or while a
+ *   tri_framegen_read_output   job is in flight (the layers are writing it). read_output copies it to the host.
+ *   tri_framegen_last_ms  device time of the last finished job, between events around its 20 launches.
+ * TRI_E_INVALID: a bad extent, a damaged container (the message names the tensor); TRI_E_OOM: an allocation failed.
+ * tri_framegen_destroy waits for a job in flight; NULL is TRI_OK. One host thread per generator. */
+typedef struct tri_framegen tri_framegen;
+int tri_framegen_create(int32_t device, const void* weights, uint64_t bytes, uint32_t width, uint32_t height,
+                        tri_framegen** out);
+int tri_framegen_destroy(tri_framegen* gen);
+int tri_framegen_info(const tri_framegen* gen, uint32_t* input_channels, uint32_t* width, uint32_t* height);
+int tri_framegen_submit(tri_framegen* gen, const void* device_input_nhwc, void* producer_stream);
+int tri_framegen_poll(tri_framegen* gen, int32_t* done);
+int tri_framegen_wait(tri_framegen* gen);
+int tri_framegen_output(tri_framegen* gen, const float** device_hw3);
+int tri_framegen_read_output(tri_framegen* gen, float* host_hw3);
+int tri_framegen_last_ms(tri_framegen* gen, float* ms);
+
+/* tri_upload_ai_frame for a tensor that is already on the context's device: [height][width][channels] floats in
+ * [0, 1], channels 1..4. A kernel on the context's stream (behind the frames already queued, which still sample the
+ * previous texture) packs it into the R8G8B8A8 blend frame by the rules of the host path
+ * (NormaliseAndReorderAiOutput + UploadAiInterpolationToGpu's packing, Renderer.cpp:358-415, :1572-1590), bit for bit:
+ * channels 0 and 2 swapped when there are at least 3, clamp to [0, 1], round(v * 255.0f) half away from zero, alpha
+ * 255 (and the other missing channels 0) when absent. The host path's 1/255 rescale of tensors beyond [0, 1] is not
+ * applied. With `behind` non-NULL the context's stream first waits for that generator's last submitted job (the
+ * tensor is usually its output), and the generator's next job waits for this kernel before it overwrites the tensor.
+ * tri_read_ai_frame copies the blend frame (width * height * 4 bytes) to the host after the context's stream has
+ * drained; TRI_E_STATE without one. */
+int tri_upload_ai_frame_device(tri_ctx* ctx, const void* device_nhwc, uint32_t width, uint32_t height,
+                               uint32_t channels, tri_framegen* behind);
+int tri_read_ai_frame(tri_ctx* ctx, uint8_t* rgba8);
+/* The stream the context currently enqueues on (its own, or tri_set_stream's) as a hipStream_t: what a producer hands
+ * to tri_framegen_submit so that the copy of a tensor the context made is ordered with the context's later frames. */
+int tri_get_stream(tri_ctx* ctx, void** hip_stream);
+
 /* ---- text overlay (Renderer::SubmitText -> TextRenderer::QueueText / RecordViewport, Text.vert / Text.frag) ----
  * The reference draws queued text inside the viewport's render pass, after the sprites: one textured quad per glyph
  * (6 vertices of TextVertex), cull NONE, no depth test or write, blend SRC_ALPHA / ONE_MINUS_SRC_ALPHA for colour and
