@@ -1350,14 +1350,15 @@ struct SkyTex {
     }
 };
 
-// BGRA8 sky colour of pixel (px, py), or the clear colour where the skybox does not cover it.
-// Inlined into its own pass of k_raster (a call here costs the whole kernel a scratch stack and the
-// callee-saved register set: measured 5x slower at C3).
-__device__ __forceinline__ uint32_t sky_bgra(const TriFrameParams& fp, const TriDeviceBuffers& b, int32_t px, int32_t py,
-                                          const float* lut) {
-    const float xn = (float)(2 * px + 1) / (float)fp.W - 1.0f;
-    const float yn = (float)(2 * py + 1) / (float)fp.H - 1.0f;
-    const float* m = fp.sky_ip;
+// The sky ray of pixel (px, py), shared by k_raster's sky pass (sky_bgra) and k_sky_fill (sky_fill.hip): unproject
+// both clip planes (m: sky_ip), intersect the 20-unit cube in view space (R: sky_R) and return hit(h) for the point h
+// where the ray leaves it, or miss() where the ray misses the cube or h has w <= 0 (pw: sky_pw). Continuations, not a
+// result the caller tests: inlined, sky_bgra is the code it was before the direction had a second user.
+template <class Miss, class Hit>
+__device__ __forceinline__ auto sky_ray(int32_t W, int32_t H, const float* m, const float* R, const float* pw, int32_t px,
+                                        int32_t py, Miss miss, Hit hit) {
+    const float xn = (float)(2 * px + 1) / (float)W - 1.0f;
+    const float yn = (float)(2 * py + 1) / (float)H - 1.0f;
     auto unproject = [&](float zn) {
         const float x = ((m[0] * xn + m[4] * yn) + m[8] * zn) + m[12];
         const float y = ((m[1] * xn + m[5] * yn) + m[9] * zn) + m[13];
@@ -1367,7 +1368,6 @@ __device__ __forceinline__ uint32_t sky_bgra(const TriFrameParams& fp, const Tri
     };
     const f3 o = unproject(0.0f), o1 = unproject(1.0f);
     const f3 r = sub3(o1, o);
-    const float* R = fp.sky_R;
     const float oa[3] = {(R[0] * o.x + R[1] * o.y) + R[2] * o.z, (R[3] * o.x + R[4] * o.y) + R[5] * o.z,
                          (R[6] * o.x + R[7] * o.y) + R[8] * o.z};
     const float ra[3] = {(R[0] * r.x + R[1] * r.y) + R[2] * r.z, (R[3] * r.x + R[4] * r.y) + R[5] * r.z,
@@ -1381,28 +1381,43 @@ __device__ __forceinline__ uint32_t sky_bgra(const TriFrameParams& fp, const Tri
             t_in = fmaxf(t_in, fminf(t0, t1));
             t_out = fminf(t_out, fmaxf(t0, t1));
         } else if (oa[a] < -half || oa[a] > half) {
-            return fp.clear_bgra;
+            return miss();
         }
     }
-    if (!(t_out >= t_in)) return fp.clear_bgra;
+    if (!(t_out >= t_in)) return miss();
     const f3 h = mk(o.x + r.x * t_out, o.y + r.y * t_out, o.z + r.z * t_out);
-    const float w = ((fp.sky_pw[0] * h.x + fp.sky_pw[1] * h.y) + fp.sky_pw[2] * h.z) + fp.sky_pw[3];
-    if (!(w > 0.0f)) return fp.clear_bgra;
-    const SkyTex sky{b.sky, (int32_t)fp.sky_size, lut};
-    const f3 c = sky.sample(norm3(h));
-    return unorm8(c.z) | (unorm8(c.y) << 8) | (unorm8(c.x) << 16) | (255u << 24);
+    const float w = ((pw[0] * h.x + pw[1] * h.y) + pw[2] * h.z) + pw[3];
+    if (!(w > 0.0f)) return miss();
+    return hit(h);
+}
+
+// BGRA8 sky colour of pixel (px, py), or the clear colour where the skybox does not cover it.
+// Inlined into its own pass of k_raster (a call here costs the whole kernel a scratch stack and the
+// callee-saved register set: measured 5x slower at C3).
+__device__ __forceinline__ uint32_t sky_bgra(const TriFrameParams& fp, const TriDeviceBuffers& b, int32_t px, int32_t py,
+                                          const float* lut) {
+    return sky_ray(
+        fp.W, fp.H, fp.sky_ip, fp.sky_R, fp.sky_pw, px, py, [&]() { return fp.clear_bgra; },
+        [&](f3 h) {
+            const SkyTex sky{b.sky, (int32_t)fp.sky_size, lut};
+            const f3 c = sky.sample(norm3(h));
+            return unorm8(c.z) | (unorm8(c.y) << 8) | (unorm8(c.x) << 16) | (255u << 24);
+        });
 }
 
 // TRI_SKY_PERSP (fast build): the ray of a pixel starts at the eye, the centre of the skybox cube,
 // so it always leaves the cube and its exit point has the direction of the far-plane point; cube
-// sampling only uses direction ratios, so no normalisation and no cube intersection is needed.
-__device__ __forceinline__ uint32_t sky_bgra_persp(const TriFrameParams& fp, const TriDeviceBuffers& b, int32_t px,
-                                                   int32_t py, const float* lut) {
-    const float xn = (float)(2 * px + 1) / (float)fp.W - 1.0f;
-    const float yn = (float)(2 * py + 1) / (float)fp.H - 1.0f;
-    const float* m = fp.sky_far;
+// sampling only uses direction ratios, so no normalisation and no cube intersection is needed. (m: sky_far)
+__device__ __forceinline__ f3 sky_persp_dir(int32_t W, int32_t H, const float* m, int32_t px, int32_t py) {
+    const float xn = (float)(2 * px + 1) / (float)W - 1.0f;
+    const float yn = (float)(2 * py + 1) / (float)H - 1.0f;
     f3 d = mk(m[0] * xn + m[1] * yn + m[2], m[4] * xn + m[5] * yn + m[6], m[8] * xn + m[9] * yn + m[10]);
     if (m[12] * xn + m[13] * yn + m[14] < 0.0f) d = mk(-d.x, -d.y, -d.z);  // homogeneous w < 0
+    return d;
+}
+__device__ __forceinline__ uint32_t sky_bgra_persp(const TriFrameParams& fp, const TriDeviceBuffers& b, int32_t px,
+                                                   int32_t py, const float* lut) {
+    const f3 d = sky_persp_dir(fp.W, fp.H, fp.sky_far, px, py);
     const SkyTex sky{b.sky, (int32_t)fp.sky_size, lut};
     const f3 c = sky.sample<true>(d);
     return unorm8(c.z) | (unorm8(c.y) << 8) | (unorm8(c.x) << 16) | (255u << 24);
@@ -1870,9 +1885,10 @@ __device__ __forceinline__ void raster_bin(const TriFrameParams& fp, const TriDe
 #ifdef TRI_PHASE_TIMING
     __syncthreads();
     TRI_STAMP(4);
-    if (!sky_queue) { TRI_STAMP(5); return; }
+    if (!sky_queue || fp.sky_mode == TRI_SKY_PREFILLED) { TRI_STAMP(5); return; }
 #endif
-    if (!sky_queue) return;
+    // (TRI_SKY_PREFILLED: k_sky_fill wrote every background pixel ahead of this kernel, and the loop above stored none)
+    if (!sky_queue || fp.sky_mode == TRI_SKY_PREFILLED) return;
     __syncthreads();
     const uint32_t ns = nsky;
     if (fp.sky_lut && !fp.need_lut && ns > 0) {  // uniform: only bins showing sky stage the LUT

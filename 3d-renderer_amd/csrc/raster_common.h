@@ -52,6 +52,7 @@ static_assert(TRI_MAX_CLIP_POLY <= TRI_MAX_CLIP_VERTS, "clip polygon buffers");
 #define TRI_SKY_RAY 0u
 #define TRI_SKY_PERSP 1u
 #define TRI_SKY_UNIFORM 2u
+#define TRI_SKY_PREFILLED 3u
 
 // overflow flag bits (TriCounters.flags)
 #define TRI_OVF_CLIP_RECORDS 0x1u
@@ -225,6 +226,8 @@ struct TriFrameParams {
     //                  point's homogeneous xyz: 3 dot products per pixel
     //  TRI_SKY_UNIFORM TRI_SKY_PERSP over a cubemap whose texels are all equal: LINEAR filtering of
     //                  equal taps returns that texel, so the sky is the constant sky_bgra
+    //  TRI_SKY_PREFILLED (either build) k_sky_fill (sky_fill.hip) wrote every pixel's sky or clear colour ahead of
+    //                  the frame's raster kernel, which then stores no background colour
     uint32_t sky_mode;
     uint32_t sky_bgra;
     uint32_t need_lut;  // some texture larger than 1x1: every k_raster workgroup stages the sRGB LUT

@@ -131,6 +131,22 @@ enum TriStage { kStageVertex = 0, kStageShadow, kStageSetup, kStageRaster, kStag
 hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, TriLaunchArgs* d_args,
                         hipStream_t stream, hipEvent_t* events);
 
+// k_sky_fill (sky_fill.hip): the skybox pass ahead of a TRI_SKY_PREFILLED frame's raster kernel. By value: the pass
+// runs in front of the frame's first kernel, which publishes the frame's own arguments.
+struct TriSkyFillArgs {
+    int32_t W, H, y0, y1;          // the frame and the context's rows
+    uint32_t clear_bgra;
+    uint32_t mode;                 // TRI_SKY_RAY or TRI_SKY_PERSP
+    uint32_t format, size, mips;   // TRI_SKY_FMT_*, the level 0 face edge, the level count
+    uint32_t pad;
+    float ip[16], R[9], pw[4], far[16];  // TriFrameParams::sky_ip, sky_R, sky_pw, sky_far
+    uint32_t level_texel[16];      // each level's first texel (level-major, then face, then rows)
+    TRI_G const uint32_t* texels;
+    TRI_G const float* lut;        // TriDeviceBuffers::srgb_lut
+    TRI_G uint32_t* color;         // the context's first row
+};
+hipError_t tri_launch_sky_fill(const TriSkyFillArgs& args, hipStream_t stream);
+
 // Presentation blit (tri_blit_linear): src W x H B8G8R8A8 -> dst dw x dh, linear, clamp-to-edge.
 hipError_t tri_launch_blit(const uint32_t* src, int32_t w, int32_t h, uint32_t* dst, int32_t dw, int32_t dh,
                            const float* unorm_lut, hipStream_t stream);

@@ -307,6 +307,9 @@ int tri_group_upload_ai_frame(tri_group* g, const uint8_t* rgba8, uint32_t w, ui
 int tri_group_upload_skybox(tri_group* g, const uint8_t* faces, uint32_t size) {
     return each(g, [&](tri_ctx* c) { return tri_upload_skybox(c, faces, size); });
 }
+int tri_group_upload_skybox_ex(tri_group* g, const tri_skybox_desc* desc) {
+    return each(g, [&](tri_ctx* c) { return tri_upload_skybox_ex(c, desc); });
+}
 int tri_group_set_shadow(tri_group* g, const tri_shadow_config* s) {
     return each(g, [&](tri_ctx* c) { return tri_set_shadow(c, s); });
 }

@@ -127,6 +127,9 @@ struct tri_ctx {
     hipEvent_t ai_packed = nullptr;  // behind tri_upload_ai_frame_device's kernel: the generator's next job waits for it
     uint32_t ai_w = 0, ai_h = 0;
     uint32_t sky_size = 0;
+    // tri_upload_skybox_ex: a cubemap k_sky_fill draws (another format, a mip chain, or TRI_SKYBOX_PREFILL)
+    bool sky_prefill = false;
+    uint32_t sky_format = TRI_SKY_FMT_RGBA8_SRGB, sky_mips = 1;
     bool sky_uniform = false;  // every texel of the cubemap equal (e.g. the solid fallback)
     uint32_t sky_uniform_bgra = 0;
     uint32_t nbones = 0;         // the palette's extent: the uploaded prefix and the posed suffix behind it
@@ -1353,6 +1356,9 @@ int tri_upload_skybox(tri_ctx* c, const uint8_t* faces, uint32_t n) {
     TRI_HIP_TRY(hipMemcpy(c->d_sky, faces, texels * 4, hipMemcpyHostToDevice));
     TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
     c->sky_size = n;
+    c->sky_prefill = false;
+    c->sky_format = TRI_SKY_FMT_RGBA8_SRGB;
+    c->sky_mips = 1;
     const uint32_t* t = reinterpret_cast<const uint32_t*>(faces);
     uint32_t t0;
     std::memcpy(&t0, faces, 4);
@@ -1365,6 +1371,53 @@ int tri_upload_skybox(tri_ctx* c, const uint8_t* faces, uint32_t n) {
     // Skybox.frag writes the decoded linear colour, alpha 1, to the UNORM target
     c->sky_uniform_bgra = unorm8_host(srgb_decode((t0 >> 16) & 0xFF)) | (unorm8_host(srgb_decode((t0 >> 8) & 0xFF)) << 8) |
                           (unorm8_host(srgb_decode(t0 & 0xFF)) << 16) | (255u << 24);
+    return TRI_OK;
+}
+
+// Each level's first texel and the chain's texel count (level l: 6 faces of max(1, n >> l) squared)
+static uint64_t sky_chain_texels(uint32_t n, uint32_t mips, uint32_t* level_texel) {
+    uint64_t at = 0;
+    for (uint32_t l = 0; l < mips; ++l) {
+        const uint64_t e = std::max(1u, n >> l);
+        if (level_texel) level_texel[l] = (uint32_t)at;
+        at += 6ull * e * e;
+    }
+    return at;
+}
+
+int tri_upload_skybox_ex(tri_ctx* c, const tri_skybox_desc* d) {
+    if (!c || !d) return fail(TRI_E_INVALID, "tri_upload_skybox_ex: null argument");
+    if (!d->texels || d->size == 0) {
+        if (d->texels) return fail(TRI_E_INVALID, "tri_upload_skybox_ex: face size 0");
+        c->sky_size = 0;
+        return TRI_OK;
+    }
+    const uint32_t n = d->size;
+    if (n > 16384) return fail(TRI_E_INVALID, "tri_upload_skybox_ex: face size %u too large", n);
+    if (d->format > TRI_SKY_FMT_RGBA16F) return fail(TRI_E_INVALID, "tri_upload_skybox_ex: unknown format %u", d->format);
+    if (d->flags & ~TRI_SKYBOX_PREFILL) return fail(TRI_E_INVALID, "tri_upload_skybox_ex: unknown flags 0x%x", d->flags);
+    uint32_t max_mips = 1;
+    while ((n >> max_mips) != 0u) ++max_mips;  // floor(log2(n)) + 1
+    if (d->mip_count == 0 || d->mip_count > max_mips)
+        return fail(TRI_E_INVALID, "tri_upload_skybox_ex: %u levels for a face size of %u (1..%u)", d->mip_count, n, max_mips);
+    const uint64_t texels = sky_chain_texels(n, d->mip_count, nullptr);
+    const uint64_t bpt = d->format == TRI_SKY_FMT_RGBA16F ? 8u : 4u;
+    if (d->bytes != texels * bpt)
+        return fail(TRI_E_INVALID, "tri_upload_skybox_ex: %llu bytes, the chain holds %llu", (unsigned long long)d->bytes,
+                    (unsigned long long)(texels * bpt));
+    if (d->format == TRI_SKY_FMT_RGBA8_SRGB && d->mip_count == 1 && !(d->flags & TRI_SKYBOX_PREFILL))
+        return tri_upload_skybox(c, static_cast<const uint8_t*>(d->texels), n);
+    int rc = make_current(c);
+    if (rc) return rc;
+    TRI_HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = grow(c->d_sky, c->cap_sky, (size_t)(d->bytes / 4)))) return rc;
+    TRI_HIP_TRY(hipMemcpy(c->d_sky, d->texels, (size_t)d->bytes, hipMemcpyHostToDevice));
+    TRI_HIP_TRY(hipStreamSynchronize(nullptr));  // complete before the next frame on the non-blocking stream
+    c->sky_size = n;
+    c->sky_prefill = true;
+    c->sky_format = d->format;
+    c->sky_mips = d->mip_count;
+    c->sky_uniform = false;
     return TRI_OK;
 }
 
@@ -1720,6 +1773,10 @@ int tri_render(tri_ctx* c) {
         fp.sky_mode = !persp ? TRI_SKY_RAY : (c->sky_uniform ? TRI_SKY_UNIFORM : TRI_SKY_PERSP);
         fp.sky_bgra = c->sky_uniform_bgra;
         fp.sky_lut = fp.sky_mode != TRI_SKY_UNIFORM || fp.exact_shading ? 1u : 0u;
+        if (c->sky_prefill) {  // k_sky_fill draws the sky (below): the raster kernel stores no background colour
+            fp.sky_mode = TRI_SKY_PREFILLED;
+            fp.sky_lut = 0u;
+        }
         for (int r = 0; r < 4; ++r) {  // inverse(P) * (xn, yn, 1, 1), row r
             fp.sky_far[4 * r + 0] = fp.sky_ip[0 * 4 + r];
             fp.sky_far[4 * r + 1] = fp.sky_ip[1 * 4 + r];
@@ -1822,6 +1879,21 @@ int tri_render(tri_ctx* c) {
     if (c->diag_frames++ > 0) tri_diag_front_plan(plan);
 #endif
     TRI_HSTAMP(3);
+    if (fp.sky_size && fp.sky_mode == TRI_SKY_PREFILLED) {
+        TriSkyFillArgs sa{};
+        sa.W = fp.W; sa.H = fp.H; sa.y0 = fp.y0; sa.y1 = fp.y1;
+        sa.clear_bgra = fp.clear_bgra;
+        // as the raster kernels' own pass: the exact build always takes the oracle's ray / cube path
+        sa.mode = fp.sky_pw[3] == 0.0f && !fp.exact_shading ? TRI_SKY_PERSP : TRI_SKY_RAY;
+        sa.format = c->sky_format; sa.size = c->sky_size; sa.mips = c->sky_mips;
+        std::memcpy(sa.ip, fp.sky_ip, sizeof sa.ip);
+        std::memcpy(sa.R, fp.sky_R, sizeof sa.R);
+        std::memcpy(sa.pw, fp.sky_pw, sizeof sa.pw);
+        std::memcpy(sa.far, fp.sky_far, sizeof sa.far);
+        sky_chain_texels(c->sky_size, c->sky_mips, sa.level_texel);
+        sa.texels = c->d_sky; sa.lut = c->d_lut; sa.color = c->d_color;
+        TRI_HIP_TRY(tri_launch_sky_fill(sa, c->stream));
+    }
     TRI_HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev));
     c->launched = true;
     // the text pass (TextRenderer::RecordViewport, after the mesh / sky pass): only when quads are set. A

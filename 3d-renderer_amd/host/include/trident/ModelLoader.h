@@ -77,20 +77,42 @@ public:
     static TextureData Load(const std::string& filePath);
 };
 
-// SkyboxTextureLoader (TextureLoader.h / TextureLoader.cpp:334-830), LDR faces: every face decoded to
-// RGBA8 without the vertical flip, all faces of one size, stored +X,-X,+Y,-Y,+Z,-Z. An invalid (empty)
-// result and a logged error when a face is missing, fails to decode or differs in size. EXR and KTX
-// need tinyexr / a KTX parser that are not restated: such inputs load as invalid.
+// SkyboxTextureLoader (TextureLoader.h / TextureLoader.cpp:334-830). An invalid (empty) result and a logged error when
+// a file is missing, fails to decode, is truncated or differs in size from the other faces.
+//   LDR faces: every face decoded to RGBA8 sRGB without the vertical flip, stored +X,-X,+Y,-Y,+Z,-Z.
+//   EXR faces (all six paths end in .exr, LoadFromFileList :738-767): R16G16B16A16_SFLOAT, every channel through
+//     FloatToHalf; single-part scanline files with HALF or FLOAT channels at sampling 1, compression NONE, RLE, ZIPS or
+//     ZIP, either line order, rows top to bottom. Tiled, multi-part and deep files, UINT channels, PIZ and the later
+//     codecs are refused by name (PIZ is a deviation from tinyexr: DESIGN.md §5l). A mix of .exr and other faces takes
+//     the LDR loader, where the .exr face fails to decode, as in the reference.
+//   KTX 1 (LoadFromKtx :417-563): little-endian, 6 faces; UNSIGNED_BYTE + SRGB8_ALPHA8 -> sRGB, UNSIGNED_BYTE + RGBA ->
+//     UNORM, HALF_FLOAT or FLOAT + RGBA16F -> 8 bytes per texel (the FLOAT case is the reference's quirk, kept); the
+//     key/value data is skipped; per level a size word (0 refused, otherwise ignored), six faces each padded to 4
+//     bytes, the level padded to 4 bytes; dimensions halve with a floor of 1. Deviation: faces that are not square or
+//     are wider than 16384 are refused (Vulkan would reject them; the reference never checks).
 class SkyboxTextureLoader {
 public:
     static CubemapTextureData LoadFromFaces(const std::array<std::string, 6>& facePaths);
     // TryMatchFaceIndex (:140-160) per file of the directory (sorted order): the first face whose
-    // token (posx/px, negx/nx, ...) the lower-case stem contains; the first candidate per face wins.
+    // token (posx/px, negx/nx, ...) the lower-case stem contains; per face the first .exr candidate,
+    // otherwise the first candidate (:384-411).
     static CubemapTextureData LoadFromDirectory(const std::string& directoryPath);
+    static CubemapTextureData LoadFromKtx(const std::string& filePath);
+    static CubemapTextureData LoadFromExrFaces(const std::array<std::string, 6>& facePaths);
+    // The parsers over bytes in memory (`name` only labels the log): what the files' loaders call, and what
+    // `make sky-check` runs over damaged files.
+    static CubemapTextureData LoadKtxFromMemory(const uint8_t* data, size_t size, const std::string& name);
+    static bool DecodeExrFaceFromMemory(const uint8_t* data, size_t size, const std::string& name, uint32_t& width,
+                                        uint32_t& height, std::vector<uint16_t>& rgbaHalf);
 };
+// FloatToHalf (TextureLoader.cpp:162-204): drops 13 mantissa bits and adds one when the highest dropped bit is set (a
+// tie rounds away from zero, not to even); a rebiased exponent below -10 gives a signed zero, subnormals come from the
+// same shift-and-add, 31 or more gives infinity and a NaN keeps one mantissa bit.
+uint16_t FloatToHalf(float value);
 
 // Renderer::CreateSkyboxCubemap's discovery (Renderer.cpp:3830-3927) under `assetsDir` (the reference
-// uses "Assets", relative to the working directory): Skyboxes/DefaultSkybox.ktx, else the
+// uses "Assets", relative to the working directory): Skyboxes/DefaultSkybox.ktx (when the file exists the search
+// ends there, valid or not, like the reference's if / else at :3833-3921), else the
 // Skyboxes/Default directory, else loose PNG faces in Skyboxes/ matched by the px/nx/... tokens (a
 // file may fill every still-missing face whose token its stem contains), else invalid. `source`
 // names what was used ("DefaultSkybox.ktx", "Default directory", "PNG fallback" or "").

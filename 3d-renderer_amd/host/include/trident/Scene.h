@@ -5,6 +5,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <limits>
 #include <memory>
@@ -60,15 +61,39 @@ struct TextureData {  // TextureLoader output: RGBA8 (forced 4 channels), rows a
     int Channels = 4;
     std::vector<uint8_t> Pixels;
 };
-// CubemapTextureData (Loader/TextureLoader.h:30-48), LDR subset: 6 faces +X,-X,+Y,-Y,+Z,-Z of
-// m_Width x m_Height RGBA8 sRGB texels, one mip, stored face after face.
+// CubemapTextureData (Loader/TextureLoader.h:30-48): 6 faces +X,-X,+Y,-Y,+Z,-Z of m_Width x m_Height texels and their
+// mip chain, stored level after level, face after face, rows top to bottom (the layout tri_upload_skybox_ex takes).
+// m_Format is the reference's VkFormat reduced to the three it uploads; m_FaceRegions[level][face] is where each face
+// lies in m_PixelData (filled by the KTX and EXR loaders; the one-level LDR producers may leave it empty).
+enum class CubemapFormat : uint32_t { Rgba8Srgb = 0, Rgba8Unorm = 1, Rgba16Sfloat = 2 };  // TRI_SKY_FMT_*
+struct CubemapFaceRegion {
+    size_t m_Offset = 0;
+    size_t m_Size = 0;
+};
 struct CubemapTextureData {
+    static constexpr uint32_t kMaxSize = 16384;
     uint32_t m_Width = 0;
     uint32_t m_Height = 0;
     uint32_t m_MipCount = 1;
+    uint32_t m_BytesPerPixel = 4;
+    bool m_IsHdr = false;
+    CubemapFormat m_Format = CubemapFormat::Rgba8Srgb;
     std::vector<uint8_t> m_PixelData;
+    std::vector<std::array<CubemapFaceRegion, 6>> m_FaceRegions;
+    // bytes of the whole chain: level l is max(1, m_Width >> l) square
+    uint64_t ChainBytes() const {
+        uint64_t texels = 0;
+        for (uint32_t l = 0; l < m_MipCount; ++l) {
+            const uint64_t e = (m_Width >> l) ? (m_Width >> l) : 1u;
+            texels += 6ull * e * e;
+        }
+        return texels * m_BytesPerPixel;
+    }
     bool IsValid() const {
-        return m_Width > 0 && m_Width == m_Height && m_PixelData.size() >= 6ull * m_Width * m_Height * 4;
+        if (m_Width == 0 || m_Width != m_Height || m_Width > kMaxSize || m_MipCount == 0 || m_MipCount > 15) return false;
+        if (m_MipCount > 1 && (m_Width >> (m_MipCount - 1)) == 0) return false;
+        if (m_BytesPerPixel != (m_Format == CubemapFormat::Rgba16Sfloat ? 8u : 4u)) return false;
+        return m_PixelData.size() >= ChainBytes();
     }
     static CubemapTextureData CreateSolidColor(uint32_t rgba8888) {  // TextureLoader.cpp:309-330
         CubemapTextureData d;

@@ -89,6 +89,26 @@ int trident_load_image(const char* path, int flip, uint8_t* rgba, uint64_t capac
 int trident_load_default_skybox(const char* assets_dir, uint8_t* faces, uint64_t capacity, uint32_t* size,
                                 char* source, uint32_t source_cap);
 
+/* The same discovery for every cubemap it can return (KTX 1 files, EXR faces, mip chains): *info describes the result
+ * (size 0: nothing valid was found), texels = NULL queries it; else capacity must hold info->bytes, the chain as
+ * tri_upload_skybox_ex takes it. trident_load_default_skybox itself is TRI_E_UNSUPPORTED for a cubemap that is not
+ * one level of RGBA8 sRGB when it is asked for the faces. */
+typedef struct {
+    uint32_t format;          /* TRI_SKY_FMT_* */
+    uint32_t size;            /* level 0 face edge */
+    uint32_t mip_count;
+    uint32_t bytes_per_pixel;
+    uint32_t is_hdr;
+    uint32_t region_levels;   /* levels with recorded face regions (m_FaceRegions.size()) */
+    uint64_t bytes;           /* the whole chain */
+} trident_cubemap_info;
+int trident_load_default_skybox_ex(const char* assets_dir, trident_cubemap_info* info, uint8_t* texels, uint64_t capacity,
+                                   char* source, uint32_t source_cap);
+/* SkyboxTextureLoader::LoadFromKtx (kind 0: path is the file) or LoadFromDirectory (kind 1: path is the directory). */
+int trident_load_skybox(const char* path, int kind, trident_cubemap_info* info, uint8_t* texels, uint64_t capacity);
+/* Loader::FloatToHalf over count values. */
+int trident_float_to_half(const float* values, uint16_t* halves, uint32_t count);
+
 /* Model import as Forge's drop handler (ModelLoader: .obj/.mtl, .gltf, .glb): entities per mesh
  * instance. Up to `capacity` spawned entity ids go to `entities`; *count gets how many were spawned. */
 int trident_app_import_model(trident_app* app, const char* path, uint32_t* entities, uint32_t capacity,

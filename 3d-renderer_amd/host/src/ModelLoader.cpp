@@ -978,14 +978,19 @@ TextureData TextureLoader::Load(const std::string& filePath) {
 CubemapTextureData SkyboxTextureLoader::LoadFromFaces(const std::array<std::string, 6>& faces) {
     static const char* names[6] = {"+X", "-X", "+Y", "-Y", "+Z", "-Z"};
     CubemapTextureData out;
+    // LoadFromFileList (TextureLoader.cpp:738-767): the EXR loader only when all six faces are .exr
+    if (std::all_of(faces.begin(), faces.end(), [](const std::string& p) {
+            return !p.empty() && Lower(fs::path(p).extension().string()) == ".exr";
+        }))
+        return LoadFromExrFaces(faces);
     for (int f = 0; f < 6; ++f) {
         if (faces[f].empty()) {
             LogError("cubemap face has an empty path", names[f]);
             return {};
         }
         const std::string ext = Lower(fs::path(faces[f]).extension().string());
-        if (ext == ".exr") {
-            LogError("EXR cubemap faces need tinyexr (not linked)", faces[f]);
+        if (ext == ".exr") {  // (stb_image does not decode EXR either)
+            LogError("an EXR face among LDR cubemap faces fails to decode", faces[f]);
             return {};
         }
         const TextureData t = DecodeImageFile(faces[f]);  // stbi_set_flip_vertically_on_load(false)
@@ -1039,7 +1044,11 @@ CubemapTextureData SkyboxTextureLoader::LoadFromDirectory(const std::string& dir
             LogError("missing cubemap face in directory", dir);
             return {};
         }
-        faces[f] = candidates[f].front();  // no EXR candidates are usable here, so the first match
+        // the first .exr candidate, otherwise the first candidate (TextureLoader.cpp:384-411)
+        const auto exr = std::find_if(candidates[f].begin(), candidates[f].end(), [](const std::string& p) {
+            return Lower(fs::path(p).extension().string()) == ".exr";
+        });
+        faces[f] = exr != candidates[f].end() ? *exr : candidates[f].front();
     }
     return LoadFromFaces(faces);
 }
@@ -1049,9 +1058,8 @@ CubemapTextureData DiscoverDefaultSkybox(const std::string& assetsDir, std::stri
     const fs::path root = fs::path(assetsDir) / "Skyboxes";
     std::error_code ec;
     if (fs::exists(root / "DefaultSkybox.ktx", ec)) {  // Renderer.cpp:3831-3837
-        LogError("KTX cubemaps are not restated; DefaultSkybox.ktx loads as invalid", (root / "DefaultSkybox.ktx").string());
-        source = "DefaultSkybox.ktx";
-        return {};
+        source = "DefaultSkybox.ktx";  // (valid or not: the search does not go on)
+        return SkyboxTextureLoader::LoadFromKtx((root / "DefaultSkybox.ktx").string());
     }
     if (fs::exists(root / "Default", ec)) {  // :3840-3845
         source = "Default directory";

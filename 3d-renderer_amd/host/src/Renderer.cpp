@@ -179,7 +179,11 @@ struct Target {
     int Materials(const tri_material_record* r, uint32_t n) const {
         return g ? tri_group_upload_materials(g, r, n) : tri_upload_materials(c, r, n);
     }
-    int Skybox(const uint8_t* f, uint32_t n) const { return g ? tri_group_upload_skybox(g, f, n) : tri_upload_skybox(c, f, n); }
+    // (a one-level sRGB cubemap is tri_upload_skybox itself; desc = nullptr removes the skybox)
+    int Skybox(const tri_skybox_desc* d) const {
+        if (!d) return g ? tri_group_upload_skybox(g, nullptr, 0) : tri_upload_skybox(c, nullptr, 0);
+        return g ? tri_group_upload_skybox_ex(g, d) : tri_upload_skybox_ex(c, d);
+    }
     int AiFrame(const uint8_t* p, uint32_t w, uint32_t h) const {
         return g ? tri_group_upload_ai_frame(g, p, w, h) : tri_upload_ai_frame(c, p, w, h);
     }
@@ -492,7 +496,7 @@ void Renderer::SetAssetsDirectory(const std::string& directory) {
 
 bool Renderer::SetSkyboxCubemap(const Loader::CubemapTextureData& cubemap) {
     if (!cubemap.IsValid()) {
-        LogError("SetSkyboxCubemap", "cubemap needs 6 square RGBA8 faces");
+        LogError("SetSkyboxCubemap", "cubemap needs 6 square faces of one of the three formats and their whole mip chain");
         return false;
     }
     m_SkyboxCubemap = cubemap;
@@ -1311,7 +1315,14 @@ bool Renderer::PrepareViewport(ViewportContext& vc) {
     }
     if (vc.m_SkyboxGeneration != m_SkyboxGeneration) {
         const bool ok = m_SkyboxCubemap.IsValid();
-        if (t.Skybox(ok ? m_SkyboxCubemap.m_PixelData.data() : nullptr, ok ? m_SkyboxCubemap.m_Width : 0) != TRI_OK) {
+        // format, size and the whole mip chain as loaded (CreateSkyboxCubemap, Renderer.cpp:3965-4097)
+        tri_skybox_desc desc{};
+        desc.format = (uint32_t)m_SkyboxCubemap.m_Format;
+        desc.size = m_SkyboxCubemap.m_Width;
+        desc.mip_count = m_SkyboxCubemap.m_MipCount;
+        desc.texels = m_SkyboxCubemap.m_PixelData.data();
+        desc.bytes = ok ? m_SkyboxCubemap.ChainBytes() : 0;
+        if (t.Skybox(ok ? &desc : nullptr) != TRI_OK) {
             LogError("skybox cubemap", tri_last_error());
             return false;
         }

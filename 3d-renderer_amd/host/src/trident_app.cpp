@@ -315,12 +315,59 @@ int trident_load_default_skybox(const char* assets_dir, uint8_t* faces, uint64_t
         CopySource(src, source, source_cap);
         *size = c.IsValid() ? c.m_Width : 0;
         if (!faces || !c.IsValid()) return TRI_OK;
+        if (c.m_Format != Loader::CubemapFormat::Rgba8Srgb || c.m_MipCount != 1) return TRI_E_UNSUPPORTED;
         if (capacity < c.m_PixelData.size()) return TRI_E_OVERFLOW;
         std::memcpy(faces, c.m_PixelData.data(), c.m_PixelData.size());
         return TRI_OK;
     } catch (...) {
         return TRI_E_INVALID;
     }
+}
+
+static int ReturnCubemap(const Loader::CubemapTextureData& c, trident_cubemap_info* info, uint8_t* texels, uint64_t capacity) {
+    *info = trident_cubemap_info{};
+    if (!c.IsValid()) return TRI_OK;
+    info->format = (uint32_t)c.m_Format;
+    info->size = c.m_Width;
+    info->mip_count = c.m_MipCount;
+    info->bytes_per_pixel = c.m_BytesPerPixel;
+    info->is_hdr = c.m_IsHdr ? 1u : 0u;
+    info->region_levels = (uint32_t)c.m_FaceRegions.size();
+    info->bytes = c.ChainBytes();
+    if (!texels) return TRI_OK;
+    if (capacity < info->bytes) return TRI_E_OVERFLOW;
+    std::memcpy(texels, c.m_PixelData.data(), (size_t)info->bytes);
+    return TRI_OK;
+}
+
+int trident_load_default_skybox_ex(const char* assets_dir, trident_cubemap_info* info, uint8_t* texels, uint64_t capacity,
+                                   char* source, uint32_t source_cap) {
+    if (!assets_dir || !info) return TRI_E_INVALID;
+    try {
+        std::string src;
+        const Loader::CubemapTextureData c = Loader::DiscoverDefaultSkybox(assets_dir, src);
+        CopySource(src, source, source_cap);
+        return ReturnCubemap(c, info, texels, capacity);
+    } catch (...) {
+        return TRI_E_INVALID;
+    }
+}
+
+int trident_load_skybox(const char* path, int kind, trident_cubemap_info* info, uint8_t* texels, uint64_t capacity) {
+    if (!path || !info || kind < 0 || kind > 1) return TRI_E_INVALID;
+    try {
+        return ReturnCubemap(kind == 0 ? Loader::SkyboxTextureLoader::LoadFromKtx(path)
+                                       : Loader::SkyboxTextureLoader::LoadFromDirectory(path),
+                             info, texels, capacity);
+    } catch (...) {
+        return TRI_E_INVALID;
+    }
+}
+
+int trident_float_to_half(const float* values, uint16_t* halves, uint32_t count) {
+    if (count && (!values || !halves)) return TRI_E_INVALID;
+    for (uint32_t i = 0; i < count; ++i) halves[i] = Loader::FloatToHalf(values[i]);
+    return TRI_OK;
 }
 
 int trident_app_set_entity_bones(trident_app* app, uint32_t entity, const float* matrices, uint32_t count) {

@@ -178,6 +178,16 @@ def make_shadow(light_view_proj, size=2048, depth_bias=0.001, slope_bias=2.0):
     return s
 
 
+# tri_upload_skybox_ex
+TRI_SKY_FMT_RGBA8_SRGB, TRI_SKY_FMT_RGBA8_UNORM, TRI_SKY_FMT_RGBA16F = 0, 1, 2
+TRI_SKYBOX_PREFILL = 0x1
+
+
+class TriSkyboxDesc(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("size", C.c_uint32), ("mip_count", C.c_uint32), ("flags", C.c_uint32),
+                ("texels", C.c_void_p), ("bytes", C.c_uint64)]
+
+
 TRI_FORMAT_B8G8R8A8_UNORM = 44
 
 
@@ -319,6 +329,7 @@ CABI_FUNCTIONS = [
     ("tri_upload_texture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("tri_upload_bone_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("tri_upload_skybox", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("tri_upload_skybox_ex", C.c_int, [C.c_void_p, C.POINTER(TriSkyboxDesc)]),
     ("tri_upload_ai_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("tri_set_frame", C.c_int, [C.c_void_p, C.POINTER(TriGlobalUbo), C.POINTER(C.c_float * 4)]),
     ("tri_set_draws", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
@@ -417,6 +428,7 @@ CABI_FUNCTIONS = [
     ("tri_group_upload_texture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("tri_group_upload_bone_palette", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("tri_group_upload_skybox", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    ("tri_group_upload_skybox_ex", C.c_int, [C.c_void_p, C.POINTER(TriSkyboxDesc)]),
     ("tri_group_upload_ai_frame", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     ("tri_group_set_shadow", C.c_int, [C.c_void_p, C.POINTER(TriShadowConfig)]),
     ("tri_group_set_frame", C.c_int, [C.c_void_p, C.POINTER(TriGlobalUbo), C.POINTER(C.c_float * 4)]),

@@ -45,6 +45,9 @@ _APP_FUNCTIONS = [
                                      C.POINTER(C.c_uint32)]),
     ("trident_load_default_skybox", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_char_p,
                                               C.c_uint32]),
+    ("trident_load_default_skybox_ex", C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint32]),
+    ("trident_load_skybox", C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("trident_float_to_half", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     ("trident_app_add_light", C.c_int, [C.c_void_p, C.c_int, _f3, _f3, _f3, C.c_float, C.c_float, C.c_int,
                                         C.POINTER(C.c_uint32)]),
     ("trident_app_set_camera", C.c_int, [C.c_void_p, C.c_int, _f3, _f3, C.c_float, C.c_float, C.c_float, C.c_int]),
@@ -874,6 +877,52 @@ def load_default_skybox(assets_dir):
     _check(lib.trident_load_default_skybox(os.fsencode(assets_dir), faces.ctypes.data, faces.nbytes, C.byref(n), src, 64),
            "load_default_skybox")
     return faces, src.value.decode()
+
+
+class CubemapInfo(C.Structure):  # trident_cubemap_info
+    _fields_ = [("format", C.c_uint32), ("size", C.c_uint32), ("mip_count", C.c_uint32), ("bytes_per_pixel", C.c_uint32),
+                ("is_hdr", C.c_uint32), ("region_levels", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+def _load_cubemap(call, what):
+    """(info dict, the chain's bytes as uint8 [bytes]) or (None, None): `call(info, texels, capacity)` twice."""
+    info = CubemapInfo()
+    _check(call(C.byref(info), None, 0), what)
+    if info.size == 0:
+        return None, None
+    texels = np.empty(info.bytes, np.uint8)
+    _check(call(C.byref(info), texels.ctypes.data, texels.nbytes), what)
+    return {k: getattr(info, k) for k, _ in CubemapInfo._fields_}, texels
+
+
+def load_default_skybox_ex(assets_dir):
+    """DiscoverDefaultSkybox for every cubemap it can return: (info, texels, source); info None when nothing valid."""
+    lib = load_library()
+    src = C.create_string_buffer(64)
+    info, texels = _load_cubemap(lambda i, t, c: lib.trident_load_default_skybox_ex(os.fsencode(assets_dir), i, t, c, src, 64),
+                                 "load_default_skybox_ex")
+    return info, texels, src.value.decode()
+
+
+def load_skybox_ktx(path):
+    """SkyboxTextureLoader::LoadFromKtx: (info, texels), or (None, None) for a file it refuses."""
+    lib = load_library()
+    return _load_cubemap(lambda i, t, c: lib.trident_load_skybox(os.fsencode(path), 0, i, t, c), "load_skybox_ktx")
+
+
+def load_skybox_directory(path):
+    """SkyboxTextureLoader::LoadFromDirectory: (info, texels), or (None, None)."""
+    lib = load_library()
+    return _load_cubemap(lambda i, t, c: lib.trident_load_skybox(os.fsencode(path), 1, i, t, c), "load_skybox_directory")
+
+
+def float_to_half(values):
+    """Loader::FloatToHalf (the reference's routine: ties round away from zero) over float32 values -> uint16."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, np.float32)
+    out = np.empty(v.shape, np.uint16)
+    _check(lib.trident_float_to_half(v.ctypes.data, out.ctypes.data, v.size), "float_to_half")
+    return out
 
 
 # ---- skeletal animation on the CPU (trident_anim_*): the asset service and the float32 player, no GPU ----

@@ -59,6 +59,14 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
 
 
+def _skybox_desc(texels, fmt, size, mip_count, flags):
+    """(abi.TriSkyboxDesc, the array it points into): no conversion of the texels, only their bytes."""
+    t = None if texels is None else np.ascontiguousarray(texels)
+    d = abi.TriSkyboxDesc(int(fmt), int(size), int(mip_count), int(flags), t.ctypes.data if t is not None and t.size else None,
+                          t.nbytes if t is not None else 0)
+    return d, t
+
+
 def shadow_fit_ortho(light_dir, aabb_min, aabb_max):
     """tri_shadow_fit_ortho (host-only): column-major light ortho * light view, as numpy [col][row]."""
     lib = load_library()
@@ -178,6 +186,14 @@ class TriRaster:
         if f.ndim != 4 or f.shape[0] != 6 or f.shape[1] != f.shape[2] or f.shape[3] != 4:
             raise ValueError("skybox faces must be uint8 [6, n, n, 4]")
         _check(_lib.tri_upload_skybox(self._ctx, _ptr(f), f.shape[1]))
+
+    def upload_skybox_ex(self, texels, fmt, size, mip_count=1, flags=0):
+        """tri_upload_skybox_ex: `texels` is the whole chain as one contiguous array (level-major, then face, then rows;
+        uint8 RGBA for the 8-bit formats, float16 or uint16 RGBA for abi.TRI_SKY_FMT_RGBA16F), or None to remove the
+        skybox."""
+        desc, keep = _skybox_desc(texels, fmt, size, mip_count, flags)  # (keep: the bytes the descriptor points at)
+        _check(_lib.tri_upload_skybox_ex(self._ctx, C.byref(desc)))
+        del keep
 
     def set_shadow(self, cfg):
         """tri_set_shadow: an abi.TriShadowConfig, or None to switch the shadow pre-pass off."""
@@ -710,6 +726,11 @@ class TriGroup:
             return
         f = np.ascontiguousarray(faces, dtype=np.uint8)
         _check(_lib.tri_group_upload_skybox(self._g, _ptr(f), f.shape[1]))
+
+    def upload_skybox_ex(self, texels, fmt, size, mip_count=1, flags=0):
+        desc, keep = _skybox_desc(texels, fmt, size, mip_count, flags)
+        _check(_lib.tri_group_upload_skybox_ex(self._g, C.byref(desc)))
+        del keep
 
     def set_shadow(self, cfg):
         _check(_lib.tri_group_set_shadow(self._g, C.byref(cfg) if cfg is not None else None))

@@ -439,6 +439,34 @@ int tri_read_bone_palette(tri_ctx* ctx, float* out_matrices, uint32_t matrix_cou
  * faces = NULL or size = 0 removes the skybox. */
 int tri_upload_skybox(tri_ctx* ctx, const uint8_t* faces_rgba8_srgb, uint32_t size);
 
+/* The other cubemaps CreateSkyboxCubemap uploads (Renderer.cpp:3965-4097): R8G8B8A8_UNORM (no sRGB decode),
+ * R16G16B16A16_SFLOAT, and a mip chain sampled with mipmapMode LINEAR, minLod 0, maxLod = mip_count.
+ * texels: level-major, then face (+X,-X,+Y,-Y,+Z,-Z), then rows top to bottom; level l is max(1, size >> l) square; a
+ * texel is 4 bytes (the two 8-bit formats) or 8 bytes (four binary16 values); alpha is ignored (Skybox.frag writes 1).
+ * bytes must be the chain's exact size. A one-level TRI_SKY_FMT_RGBA8_SRGB cubemap without TRI_SKYBOX_PREFILL is
+ * tri_upload_skybox itself. Every other cubemap is drawn by a pass of its own ahead of the frame's raster kernel
+ * (k_sky_fill): per level the filtering of tri_upload_skybox (major-axis face, LINEAR, taps across edges from the
+ * adjacent face, a corner tap the mean of the three texels meeting there); the level of detail by Vulkan's rules from
+ * fine quad differences of the normalised direction (quads at even frame coordinates; a neighbour the sky does not
+ * cover gives a zero derivative), the cube map derivative transformation on the pixel's own face,
+ * lambda = clamp(log2 rho_max, 0, mip_count), d = min(lambda, mip_count - 1), a linear blend of levels floor(d) and
+ * floor(d) + 1; clamp(c, 0, 1) is stored (no tone mapping). TRI_SKYBOX_PREFILL takes that pass for a one-level sRGB
+ * cubemap too. texels = NULL removes the skybox. TRI_E_INVALID: a byte count that is not the chain's, a size of 0
+ * or above 16384, more than floor(log2(size)) + 1 levels or none, an unknown format or flag. */
+#define TRI_SKY_FMT_RGBA8_SRGB 0u
+#define TRI_SKY_FMT_RGBA8_UNORM 1u
+#define TRI_SKY_FMT_RGBA16F 2u
+#define TRI_SKYBOX_PREFILL 0x1u
+typedef struct {
+    uint32_t format;    /* TRI_SKY_FMT_* */
+    uint32_t size;      /* level 0 face edge */
+    uint32_t mip_count; /* 1 .. floor(log2(size)) + 1 */
+    uint32_t flags;     /* TRI_SKYBOX_PREFILL */
+    const void* texels;
+    uint64_t bytes;
+} tri_skybox_desc;
+int tri_upload_skybox_ex(tri_ctx* ctx, const tri_skybox_desc* desc);
+
 /* Default.frag's AI frame-generation blend (Default.frag:182-191). The texture is what UploadAiInterpolationToGpu
  * (Renderer.cpp:1560-1700) fills and EnsureAiTextureResources (:1390-1500) creates: width x height R8G8B8A8_UNORM
  * texels (no sRGB decode), rows top to bottom, sampled LINEAR with CLAMP_TO_EDGE at level 0. A frame whose UBO has
@@ -875,6 +903,7 @@ int tri_group_upload_texture(tri_group* group, uint32_t slot, const uint8_t* rgb
                              uint32_t height);
 int tri_group_upload_bone_palette(tri_group* group, const float* matrices, uint32_t matrix_count);
 int tri_group_upload_skybox(tri_group* group, const uint8_t* faces_rgba8_srgb, uint32_t size);
+int tri_group_upload_skybox_ex(tri_group* group, const tri_skybox_desc* desc);
 int tri_group_upload_ai_frame(tri_group* group, const uint8_t* rgba8_unorm, uint32_t width, uint32_t height);
 int tri_group_set_shadow(tri_group* group, const tri_shadow_config* config);
 int tri_group_set_frame(tri_group* group, const tri_global_ubo* ubo, const float clear_rgba[4]);
