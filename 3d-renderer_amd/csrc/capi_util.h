@@ -1,7 +1,8 @@
 // capi_util.h — what the host translation units of the C-ABI (include/tri_raster.h) share: the error helper, the
 // device and argument checks of the entry points, and the accessors into a context. Host only: no kernel launcher is
 // declared here (raster_launch.h), and no RCCL type (tri_group.hip and tri_xfer.hip keep their own ncclResult_t pair).
-// The functions are defined in tri_raster_capi.hip, next to the thread's error string.
+// The functions are defined in tri_raster_capi.hip, next to the thread's error string; an accessor into a geometry or a
+// font in the unit that owns the object (tri_geometry.hip, tri_resources.hip). The objects themselves: tri_ctx.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -96,7 +96,7 @@ def test_sampler_sweep(oracle, flags, case):
     path = stats["path"]
     assert not path & abi.TRI_PATH_ONE_DRAW, hex(path)  # a filtered texture: never the solid instantiation
     assert bool(path & abi.TRI_PATH_SHADOW) == (form == "shadow"), hex(path)
-    # uvs in the thousands of texels: the oracle's operation order in either build (tri_raster_capi.hip kUvFastTexels)
+    # uvs in the thousands of texels: the oracle's operation order in either build (frame_select.h kUvFastTexels)
     assert bool(path & abi.TRI_PATH_EXACT) == (name in sc.SAMPLER_LARGE or bool(flags)), hex(path)
     if name == "3x5_identity":  # the identity uv transform keeps object-space varyings
         assert path & abi.TRI_PATH_OBJ48, hex(path)

@@ -197,6 +197,23 @@ def test_calls_queue_without_waiting_and_the_last_one_stands(world):
     _assert_bits(pal[130:], _cpu(rig, "rest", progs["rest"]), "second instance")
 
 
+def test_ring_wraps_and_regrows_a_used_stage(world):
+    """Six calls alternating 1 and 300 instances on a fresh context, behind three single-instance calls that put every
+    later call on a stage already used and fenced: 300 instances and their operations are more records than a
+    stage's first 512, so the first and the third stage of the ring of four are regrown after use, and the ring wraps
+    twice. Every call's palette equals the shim interpreter's, bit for bit."""
+    _, aset, rigs = world
+    rig = rigs["graph_chain3"][0]
+    progs = list(G.programs(rig, exact=True).items())
+    rng = np.random.default_rng(11)
+    with raster.TriRaster(64, 64, device=0) as c2:
+        for count in (1, 1, 1, 1, 300, 1, 300, 1, 300):
+            pick = [progs[i % len(progs)] for i in range(count)]
+            assert count == 1 or count + sum(len(ops) for _, ops in pick) > 512
+            for got, (pname, ops) in zip(_run(c2, aset, rigs, [(rig, ops) for _, ops in pick], rng), pick):
+                _assert_bits(got, _cpu(rig, "exact:" + pname, ops), f"{count} instances, {pname}")
+
+
 def test_refusals_enqueue_nothing(world):
     ctx, aset, rigs = world
     a, b = rigs["graph_chain3"], rigs["graph_forest"]
