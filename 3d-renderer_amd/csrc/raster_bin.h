@@ -586,6 +586,20 @@ __device__ __forceinline__ f3 fvcol(const Frag& f) { return mk(f.cx, f.cy, f.cz)
 __device__ __forceinline__ f3 ftex(const Frag& f) { return mk(f.sx, f.sy, f.sz); }
 __device__ __forceinline__ f3 ftint(const Frag& f) { return mk(f.tx, f.ty, f.tz); }
 
+// Default.frag's max(x, 0.0) is "0.0 if x < 0.0, otherwise x", which keeps a NaN, where fmaxf (v_max_f32) drops it. A
+// fragment whose N.V is NaN (an interpolated normal that cannot be normalised: normalize(0) of a vertex that no bone
+// skins, reaching a pixel through a clipped sliver) gets a NaN from every light Default.frag evaluates: the sun if
+// there is one, whatever its visibility, and each point light farther than 1e-4, whatever its range. The colour is
+// then NaN and the UNORM store writes 0. True when some light is evaluated for a fragment at wp.
+__device__ __forceinline__ bool nan_reaches_colour(const TriShadeConst& sc, f3 wp) {
+    bool lit = sc.has_sun != 0u;
+    for (uint32_t i = 0; i < sc.npt && !lit; ++i) {
+        const f3 to = sub3(mk(sc.pl[i].pos[0], sc.pl[i].pos[1], sc.pl[i].pos[2]), wp);
+        lit = !(sqrtf(dot3(to, to)) <= 1e-4f);
+    }
+    return lit;
+}
+
 // ---- EXACT build: Default.frag with IEEE div/sqrt/powf in the oracle's operation order ----------
 __device__ __forceinline__ float schlick_ggx(float NdotV, float roughness) {
     const float r = roughness + 1.0f;
@@ -661,6 +675,8 @@ __device__ __forceinline__ float4 fs_exact(const TriFrameParams& fp, const Frag&
                             albedo),
                         amb_s);
     f3 col = add(amb, direct);
+    const float NdotV = dot3(N, V);
+    if (NdotV != NdotV && nan_reaches_colour(fp.sc, fworld(f))) col.x = col.y = col.z = NdotV;  // NaN: stored as 0
     col = mk(col.x / (col.x + 1.0f), col.y / (col.y + 1.0f), col.z / (col.z + 1.0f));
     const float gamma = 1.0f / 2.2f;
     col = mk(powf(col.x, gamma), powf(col.y, gamma), powf(col.z, gamma));
@@ -813,6 +829,9 @@ __device__ __forceinline__ float4 fs_fast(const TriShadeConst& sc, const Frag& f
         eval_pbr_fast_p(sc, px, fdot(px.N, to) * inv, fdot(to, px.V) * inv, f2v{sc.pl[i].rad[0], sc.pl[i].rad[1]},
                         sc.pl[i].rad[2], att0 * att0, cxy, cz);
     }
+    if (__builtin_expect(__ballot(px.NdotVr != px.NdotVr) != 0ull, 0)) {  // (see below)
+        if (px.NdotVr != px.NdotVr && nan_reaches_colour(sc, wp)) { cxy = splat(0.0f); cz = 0.0f; }
+    }
     const f2v c1 = cxy + splat(1.0f);
     const f2v txy = cxy * f2v{frcp(c1.x), frcp(c1.y)};
     const float tz = cz * frcp(cz + 1.0f);
@@ -883,9 +902,21 @@ __device__ __forceinline__ float4 fs_fast(const TriShadeConst& sc, const Frag& f
         // L = to / |to| is never formed: N.L and L.V are the dot products with `to`, scaled once
         eval_pbr_fast(a2m1, kgo, px, fdot(px.N, to) * inv, fdot(to, px.V) * inv, mk(lp[4], lp[5], lp[6]), att0 * att0, c);
     }
+    // A NaN colour in Default.frag (nan_reaches_colour) is stored as 0: so is a zero colour here (tone_out(0) = 0). The
+    // test is wave-uniform, so a wave without such a fragment pays one compare and a scalar branch.
+    if (__builtin_expect(__ballot(px.NdotVr != px.NdotVr) != 0ull, 0)) {
+        if (px.NdotVr != px.NdotVr && nan_reaches_colour(sc, wp)) c = mk(0.0f, 0.0f, 0.0f);
+    }
     const f3 t = mk(c.x * frcp(c.x + 1.0f), c.y * frcp(c.y + 1.0f), c.z * frcp(c.z + 1.0f));
     return make_float4(tone_out(t.x), tone_out(t.y), tone_out(t.z), ONE ? sc.sbt[3] : (sc.base[3] * f.tw) * f.sw);
 #endif
+}
+
+// fs_fast's own test again, for the AI blend (which must not mix a colour that Default.frag has as NaN)
+__device__ __forceinline__ bool fs_fast_nan(const TriShadeConst& sc, const Frag& f) {
+#pragma clang fp contract(fast)
+    const float NdotV = fdot(fnorm(fnrm(f)), fnorm(sub3(mk(sc.cam[0], sc.cam[1], sc.cam[2]), fworld(f))));
+    return NdotV != NdotV && nan_reaches_colour(sc, fworld(f));
 }
 
 __device__ __forceinline__ float interp_exact(float w0, float w1, float w2, float x0, float x1, float x2) {
@@ -1526,6 +1557,7 @@ __device__ __forceinline__ uint32_t shade_bgra(const TriFrameParams& fp, const T
         const float4 ai = sample_ai(fp, b, px, py);
         const float w = fp.ai_wgt;
         const float alpha = ONE ? fp.sc.sbt[3] : c.w;
+        if (fs_fast_nan(fp.sc, f)) return unorm8(mix_ai(alpha, ai.w, w)) << 24;  // mix(NaN, ., w) is NaN: stored as 0
         return fast_bgra(mix_ai(c.x, 255.0f * ai.x, w), mix_ai(c.y, 255.0f * ai.y, w), mix_ai(c.z, 255.0f * ai.z, w),
                          unorm8(mix_ai(alpha, ai.w, w)));
     }

@@ -846,3 +846,136 @@ def sampler_grid(tex_wh, scale, offset, tiling, w=320, h=180, n=30, seed=7):
 
 def sampler_case(name, **kw):
     return sampler_grid(*{**SAMPLER_MODERATE, **SAMPLER_LARGE}[name], **kw)
+
+
+# ---- skinned-vertex sweep: normals, palettes, several draws ------------------------------------------------------------
+# each rig with a material that shows it (under the metallic, ambient-free material 1 the touch rig leaves most of
+# the sphere black, and a wrong normal moved under 1 % of its pixels)
+SKIN_RIG_MATERIALS = (("headon", 3), ("eight", 0), ("touch", 5))
+SKIN_FORMS = ("one", "nonunit0.6", "nonunit1.5", "skips", "short_palette", "multi", "shadow")
+SKIN_MODEL = ((0.1, -0.2, 0.0), (10.0, -15.0, 5.0), (1.0, 0.9, 1.1))  # non-conformal: the normal matrix is not a rotation
+SKIN_BONES = (((0.4, 0.2, 0.3), (20.0, 35.0, 25.0), (1.2, 0.8, 1.1)),
+              ((-0.3, 0.0, 0.2), (-40.0, 10.0, 0.0), (0.9, 1.1, 1.3)))  # palette rows 2 and 3; row 1 is the identity
+SKIN_BONES_2 = (((0.2, -0.3, 0.4), (-25.0, 20.0, 30.0), (1.1, 1.2, 0.8)),
+                ((-0.4, 0.3, 0.1), (30.0, -20.0, 15.0), (0.8, 1.0, 1.2)))  # rows 4 and 5: multi's second skinned draw
+SKIN_SPARE_ROW = ((0.5, 0.5, 0.6), (0.0, 60.0, 0.0), (1.4, 1.4, 1.4))  # skips: the row behind the draw's three bones
+SKIN_SENTINEL = 99.0  # row 0, below every draw's bone_offset: no draw may read it
+SKIN_PATCH = (range(17, 24), range(11, 20))  # skips: (rings, segments) of the patch, facing the camera
+SKIN_DEAD = ((10, 15), (30, 15), (20, 5), (20, 25), (28, 21))  # skips: (ring, segment) of the vertices with no influence
+SKIN_MULTI_MODELS = (((-3.3, -0.2, 0.0), SKIN_MODEL[1], (0.8, 0.72, 0.88)),
+                     ((3.2, 2.3, 0.0), (-20.0, 30.0, 10.0), (0.5, 0.45, 0.55)),
+                     ((3.2, -2.3, 0.0), (15.0, -25.0, 0.0), (0.5, 0.55, 0.45)))
+SKIN_SMALL_SPHERE = (16, 24)  # multi's second mesh: rings, segments (radius 3 like the first)
+SKIN_GROUND_Z = -4.2  # shadow: the receiver's plane, behind the skinned sphere as the head-on sun sees it
+
+
+def smooth_skin_weights(y):
+    """Three bones blended along y in [-3, 3]: ((1 - t)(1 - w2), t (1 - w2), w2, 0) on indices (0, 1, 2, 0), with
+    t = clip((y + 3) / 6, 0, 1) and w2 = 0.25 * 4 t (1 - t). Smooth in y, so the skinned surface does not fold."""
+    t = np.clip((np.asarray(y, np.float64) + 3.0) / 6.0, 0.0, 1.0)
+    w2 = 0.25 * 4.0 * t * (1.0 - t)
+    w = np.stack([(1.0 - t) * (1.0 - w2), t * (1.0 - w2), w2, np.zeros_like(t)], -1)
+    idx = np.tile(np.array([0, 1, 2, 0], np.int32), (len(t), 1))
+    return idx, w, t
+
+
+def skin_palette(*groups):
+    """The sentinel row, the identity, then compose_transform of every (position, rotation, scale) of the groups."""
+    rows = [np.full(16, SKIN_SENTINEL, F), np.eye(4, dtype=F).reshape(16)]
+    rows += [scenes.compose_transform(*trs).reshape(16) for g in groups for trs in g]
+    return np.stack(rows).astype(F)
+
+
+def skinned_dead_vertices(segments=60):
+    return [r * (segments + 1) + s for r, s in SKIN_DEAD]
+
+
+def skinned_world_f64(scene):
+    """World positions (x, y, z of the undivided model * skin * p) of every vertex a draw references, float64."""
+    import test_oracle_clip_f64 as f64
+
+    out = []
+    for d in scene.draws:
+        m = scene.meshes[d.mesh_index]
+        idx = scene.indices[int(m["first_index"]):int(m["first_index"]) + int(m["index_count"])]
+        used = np.unique(idx.astype(np.int64) + int(m["base_vertex"]))
+        sp, _ = f64.f64_skin(scene, d)
+        out.append((sp[used] @ np.array(d.pc.model, np.float64).reshape(4, 4))[:, :3])
+    return np.concatenate(out)
+
+
+def skinned_sphere(rig, material, form, w=320, h=240):
+    """shading_sphere(rig, material, "one_vcol") (2501 vertex slots: ten 256-slot vertex blocks) skinned by three bones
+    at palette offset 1 (smooth_skin_weights, skin_palette(SKIN_BONES)) under the non-conformal model SKIN_MODEL.
+
+    Forms: one = that single draw; nonunit0.6 / nonunit1.5 = its weights multiplied by 1 + (k - 1) t, so they sum to
+    1 .. k and a w != 1 reaches the clip stage; skips = a patch of vertices carries one skip rule each on its fourth
+    influence (a negative weight, a zero weight, index -1, index == bone_count; the palette has a spare row behind the
+    draw's bones, so only the draw's own bone_count keeps that last read out) and the five SKIN_DEAD vertices have every
+    influence skipped, each by another rule; short_palette = one with the palette uploaded one row short (bone 2 lies
+    past it for every vertex); multi = three draws (the sphere skinned from rows 1..3; a smaller sphere unskinned under
+    its own affine model; that sphere again, skinned with bone_offset 4 and bone_count 2, so its index 2 is out of
+    range), apart from one another on screen; shadow = one plus an unskinned ground quad behind the sphere under the
+    pre-pass, the light box fitted to the skinned float64 positions."""
+    s = shading_sphere(rig, material, "one_vcol", w, h)
+    v = s.vertices.copy()
+    idx, wgt, t = smooth_skin_weights(v["position"][:, 1])
+    bones = skin_palette(SKIN_BONES)
+    model = scenes.compose_transform(*SKIN_MODEL)
+    s.draws = [abi.make_draw(0, model, material_index=0, bone_offset=1, bone_count=3)]
+    if form.startswith("nonunit"):
+        wgt = wgt * (1.0 + (float(form[len("nonunit"):]) - 1.0) * t)[:, None]
+    elif form == "skips":
+        bones = skin_palette(SKIN_BONES, (SKIN_SPARE_ROW,))
+        row = 61
+        rules = ((0, -0.4), (1, 0.0), (-1, 0.5), (3, 0.5))  # (index, weight) of the fourth influence, by vertex
+        for n, (r, sg) in enumerate((r, sg) for r in SKIN_PATCH[0] for sg in SKIN_PATCH[1]):
+            idx[r * row + sg, 3], wgt[r * row + sg, 3] = rules[n % 4]
+        dead = ((0, 1, -1, 3), (-0.5, 0.0, 0.5, 0.5)), ((3, -1, 1, 0), (0.7, 0.3, 0.0, -1.0)), \
+            ((-1, -2, 4, 3), (0.25, 0.25, 0.25, 0.25)), ((0, 1, 2, 0), (0.0, 0.0, 0.0, 0.0)), \
+            ((0, 1, 2, 3), (-0.2, -0.3, -0.5, 1.0))
+        for vi, (di, dw) in zip(skinned_dead_vertices(), dead):
+            idx[vi], wgt[vi] = di, dw
+    elif form == "short_palette":
+        bones = bones[:3]
+    elif form not in ("one", "multi", "shadow"):
+        raise KeyError(form)
+    v["bone_indices"], v["bone_weights"] = idx, wgt.astype(F)
+    s.vertices = v
+    if form == "multi":
+        sv, si = scenes.uv_sphere_mesh(*SKIN_SMALL_SPHERE, 3.0)
+        sv["color"] = np.random.default_rng(19).uniform(0.0, 1.5, size=(sv.shape[0], 3)).astype(F)
+        sidx, swgt, _ = smooth_skin_weights(sv["position"][:, 1])
+        sv["bone_indices"], sv["bone_weights"] = sidx, swgt.astype(F)
+        small = len(s.meshes)
+        s.meshes = np.concatenate([s.meshes, np.array([(s.indices.size, si.size, v.shape[0], 0)], abi.MESH_RANGE_DTYPE)])
+        s.vertices, s.indices = np.concatenate([v, sv]), np.concatenate([s.indices, si])
+        bones = skin_palette(SKIN_BONES, SKIN_BONES_2)
+        m = [scenes.compose_transform(*trs) for trs in SKIN_MULTI_MODELS]
+        s.draws = [abi.make_draw(0, m[0], material_index=0, bone_offset=1, bone_count=3),
+                   abi.make_draw(small, m[1], material_index=0, tint=(0.8, 1.0, 0.7, 1.0)),
+                   abi.make_draw(small, m[2], material_index=0, tint=(1.0, 0.7, 0.9, 1.0), bone_offset=4, bone_count=2)]
+        ends = np.cumsum([v.shape[0], sv.shape[0], sv.shape[0]])
+        # a 64-lane wave of k_vertex then holds slots of a skinned and of an unskinned draw
+        assert any(e % 64 for e in ends[:2]), ends
+    elif form == "shadow":
+        g = np.zeros(4, abi.VERTEX_DTYPE)
+        g["position"] = [(-9, -7, SKIN_GROUND_Z), (9, -7, SKIN_GROUND_Z), (9, 7, SKIN_GROUND_Z), (-9, 7, SKIN_GROUND_Z)]
+        g["normal"] = (0, 0, 1)
+        g["color"] = (0.9, 0.9, 0.9)
+        g["texcoord"] = [(0, 0), (1, 0), (1, 1), (0, 1)]
+        ground = len(s.meshes)
+        s.meshes = np.concatenate([s.meshes, np.array([(s.indices.size, 6, v.shape[0], 0)], abi.MESH_RANGE_DTYPE)])
+        s.vertices = np.concatenate([v, g])
+        s.indices = np.concatenate([s.indices, np.array([0, 1, 2, 0, 2, 3], np.uint32)])
+        s.draws = s.draws + [abi.make_draw(ground, np.eye(4, dtype=F), material_index=0)]
+    s.bones = bones
+    s.name = f"skinned_{rig}_m{material}_{form}"
+    if form == "shadow":  # the box of the skinned positions, not of the bind pose: no caster leaves the map
+        from trident_raster import raster
+
+        world = skinned_world_f64(s)
+        lvp = raster.shadow_fit_ortho(list(s.ubo.directional_light_direction)[:3], world.min(0).astype(F),
+                                      world.max(0).astype(F))
+        s.shadow = abi.make_shadow(lvp, 256, 0.001, 2.0)
+    return s

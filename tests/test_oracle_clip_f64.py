@@ -31,7 +31,41 @@ def _clip_polygon(poly, plane):
     return out
 
 
-def f64_depth(scene):
+# Default.vert:64-90 in float64: the skin matrix S = sum over the four influences of w_k * palette[bone_offset + idx_k],
+# an influence skipped when w <= 0, idx < 0, idx >= bone_count, or its row lies past the uploaded palette (robust buffer
+# access: such a read contributes nothing). The position is S (p, 1) with its w kept (the model, view and projection
+# carry it; outWorldPosition is the undivided xyz), the normal mat3(S) n, taken before the normal matrix. A draw with
+# bone_count <= 0 passes (p, 1) and n through untouched. `defect` restates one mistake a vertex stage could make (the
+# defect discrimination of tests/test_skinning_sweep.py); None is the shader.
+SKIN_DEFECTS = ("normals_unskinned", "mat3_transposed", "offset_ignored", "count_skip_removed")
+
+
+def f64_skin(scene, draw, defect=None):
+    """(position [n, 4], normal [n, 3]) of every vertex record as `draw` skins it, float64."""
+    assert defect is None or defect in SKIN_DEFECTS, defect
+    vx = scene.vertices
+    pos = np.c_[vx["position"].astype(np.float64), np.ones(len(vx))]
+    nrm = vx["normal"].astype(np.float64)
+    count, offset = int(draw.pc.bone_count), int(draw.pc.bone_offset)
+    if count <= 0:
+        return pos, nrm
+    palette = np.zeros((0, 16)) if scene.bones is None else np.asarray(scene.bones, np.float64).reshape(-1, 16)
+    rows = np.concatenate([palette, np.zeros((1, 16))]).reshape(-1, 4, 4).transpose(0, 2, 1)  # [row][col]; last: zero
+    idx = vx["bone_indices"].astype(np.int64)
+    w = vx["bone_weights"].astype(np.float64)
+    row = idx + (0 if defect == "offset_ignored" else offset)
+    live = (w > 0) & (idx >= 0) & (row >= 0) & (row < len(palette))
+    if defect != "count_skip_removed":
+        live &= idx < count
+    S = np.einsum("vk,vkrc->vrc", np.where(live, w, 0.0), rows[np.where(live, row, len(palette))])
+    sp = np.einsum("vrc,vc->vr", S, pos)
+    if defect == "normals_unskinned":
+        return sp, nrm
+    S3 = S[:, :3, :3].transpose(0, 2, 1) if defect == "mat3_transposed" else S[:, :3, :3]
+    return sp, np.einsum("vrc,vc->vr", S3, nrm)
+
+
+def f64_depth(scene, defect=None):
     """Depth buffer of the scene's mesh draws, float64 Vulkan rules; also the per-pixel distance (px) from the
     winning polygon's boundary, the winner's depth gradient magnitude, and whether the winner was clipped."""
     W, H = scene.width, scene.height
@@ -48,9 +82,9 @@ def f64_depth(scene):
         mvp = proj @ view @ model
         first, count, base = int(m["first_index"]), int(m["index_count"]), int(m["base_vertex"])
         tris = scene.indices[first:first + count - count % 3].reshape(-1, 3).astype(np.int64) + base
-        pos = scene.vertices["position"].astype(np.float64)
+        pos, _ = f64_skin(scene, d, defect)
         for t in tris:
-            c = [mvp @ np.append(pos[i], 1.0) for i in t]
+            c = [mvp @ pos[i] for i in t]
             poly = _clip_polygon(c, lambda v: v[3] - WMIN)
             poly = _clip_polygon(poly, lambda v: v[2])  # 0 <= z_c
             if len(poly) < 3:
@@ -194,7 +228,7 @@ def _shade(scene, draw, P, N, col, uv):
     return np.concatenate([c, alpha[:, None]], 1)
 
 
-def f64_colour(scene, fd, margin):
+def f64_colour(scene, fd, margin, defect=None):
     """Colour (float64, before the UNORM store) of every pixel with margin >= 0.5 whose winning triangle is
     found again by depth; returns (colour [H, W, 4], mask)."""
     W, H = scene.width, scene.height
@@ -212,11 +246,12 @@ def f64_colour(scene, fd, margin):
         nmat = np.linalg.inv(model[:3, :3]).T
         first, count, base = int(m["first_index"]), int(m["index_count"]), int(m["base_vertex"])
         tris = scene.indices[first:first + count - count % 3].reshape(-1, 3).astype(np.int64) + base
-        pos = np.c_[vx["position"].astype(np.float64), np.ones(len(vx))]
+        pos, skinned_normal = f64_skin(scene, d, defect)
         world = (model @ pos.T).T
         clip = (proj @ view @ world.T).T
-        nrm = (nmat @ vx["normal"].astype(np.float64).T).T
-        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        nrm = (nmat @ skinned_normal.T).T
+        with np.errstate(invalid="ignore"):  # a vertex whose every influence is skipped has no normal (0 / 0)
+            nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
         uvt = vx["texcoord"].astype(np.float64) * np.array(d.pc.texture_scale) * d.pc.tiling_factor + np.array(d.pc.texture_offset)
         colv = vx["color"].astype(np.float64)
         for t in tris:
@@ -243,7 +278,8 @@ def f64_colour(scene, fd, margin):
             b = b / np.where(ok[:, None], bs, 1.0)
             inside = ok & np.all(b >= 0, axis=1)
             bw = b @ C[:, 3]
-            z = (b @ C[:, 2]) / np.where(inside, bw, 1.0)
+            with np.errstate(invalid="ignore"):  # 0 / 0 at a vertex skinned to w = 0: never a hit
+                z = (b @ C[:, 2]) / np.where(inside, bw, 1.0)
             hit = inside & (np.abs(z - fd[sl][cand]) <= 1e-9)
             if not hit.any():
                 continue
