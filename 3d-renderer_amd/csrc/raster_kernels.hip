@@ -1039,7 +1039,7 @@ static const void* raster_kernel(const TriFrameParams& fp) {
                               : shadow_raster_kernel<6>(exact);
 }
 
-void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan) {
+void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass) {
     plan.n = 0;
     auto add = [&](const void* f, dim3 g, dim3 t, int stage) { plan.k[plan.n++] = TriKernelLaunch{f, g, t, stage}; };
     auto F = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
@@ -1061,6 +1061,9 @@ void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan) {
     }
     if (fp.shadow_on)  // the map's depth raster, before the frame's raster samples it
         add(F(k_shadow_raster), dim3(fp.s_nbins * TRI_SHADOW_PARTS), t, kStageShadow);
+    // the id pass reads the bin counts and queues the raster kernel consumes (a frame without primitives has no
+    // queues: its ids are cleared by the caller)
+    if (id_pass && fp.nchunks > 0) add(tri_id_raster_kernel(fp), dim3(fp.nbins), t, kStageId);
     add(raster_kernel(fp), dim3(fp.nbins), t, kStageRaster);
 }
 
@@ -1081,13 +1084,13 @@ void tri_diag_front_plan(TriFramePlan& plan) {
 #endif
 
 hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, TriLaunchArgs* d_args,
-                        hipStream_t stream, hipEvent_t* ev) {
+                        hipStream_t stream, hipEvent_t* ev, const TriIdArgs* id, hipEvent_t* id_ev) {
     hipError_t e = hipSuccess;
     bool setup_stamped = false;
     if (ev && (plan.n == 0 || plan.k[0].stage != kStageVertex)) (void)hipEventRecord(ev[kStageVertex], stream);
     for (uint32_t i = 0; i < plan.n; ++i) {
         const TriKernelLaunch& k = plan.k[i];
-        if (ev) {
+        if (ev && k.stage != kStageId) {
             // stamps in the order the stages run; a frame without set-up still stamps it (zero length)
             if ((k.stage == kStageRaster || k.stage == kStageShadow) && !setup_stamped) {
                 (void)hipEventRecord(ev[kStageSetup], stream);
@@ -1098,9 +1101,14 @@ hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, Tri
         }
         void* first[] = {const_cast<TriLaunchArgs*>(&args), &d_args};
         void* later[] = {&d_args};
+        void* idp[] = {&d_args, const_cast<TriIdArgs*>(id)};  // the id pass: the published arguments, then its own
+        if (k.stage == kStageId && !id) return hipErrorInvalidValue;
+        if (k.stage == kStageId && id_ev) (void)hipEventRecord(id_ev[0], stream);
         // the frame's first kernel (k_vertex's stage) takes the arguments by value and publishes them
-        e = hipLaunchKernel(k.func, k.grid, k.block, k.stage == kStageVertex ? first : later, 0, stream);
+        e = hipLaunchKernel(k.func, k.grid, k.block, k.stage == kStageVertex ? first : (k.stage == kStageId ? idp : later), 0,
+                            stream);
         if (e != hipSuccess) return e;
+        if (k.stage == kStageId && id_ev) (void)hipEventRecord(id_ev[1], stream);
     }
     if (ev) (void)hipEventRecord(ev[kStageCount], stream);
     return hipGetLastError();

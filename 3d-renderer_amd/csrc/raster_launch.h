@@ -92,9 +92,19 @@ struct TriKernelLaunch {
 };
 struct TriFramePlan {
     uint32_t n = 0;
-    TriKernelLaunch k[4];
+    TriKernelLaunch k[5];
 };
-void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan);
+// The id pass's own arguments (id_pass.hip), by value behind the frame's published arguments: the frame's
+// TriLaunchArgs stay as they are, so no other kernel of the frame sees the pass.
+struct TriIdArgs {
+    TRI_G uint32_t* ids;  // W x (y1 - y0) draw ids of the context's rows
+};
+constexpr int kStageId = -1;  // the id pass's launch: none of tri_timing's stamps (its layout is fixed); two of its own
+// id_pass: with the context's id output on, k_id_raster between the set-up (and the shadow map's raster) and the
+// frame's raster kernel, which re-zeroes the bin counts the pass reads; off, the plan is launch for launch the same.
+void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass = false);
+// k_id_raster at the frame's bin size (id_pass.hip)
+const void* tri_id_raster_kernel(const TriFrameParams& fp);
 #ifdef TRI_DIAG_FRONT
 void tri_diag_front_plan(TriFramePlan& plan);  // diagnostics build only (raster_kernels.hip)
 #endif
@@ -115,8 +125,20 @@ enum TriStage { kStageVertex = 0, kStageShadow, kStageSetup, kStageRaster, kStag
 // One frame = 3 dependent launches on `stream` (k_vertex, k_setup with in-wave clipping, k_raster), 4 with the
 // shadow pre-pass (k_shadow_raster after k_setup<shadow>); `events` (may be null) gets kStageCount + 1 stamps
 // (the kStageShadow stamp only when the pre-pass runs).
+// `id`: the id pass's arguments when the plan holds its launch (kStageId); `id_events` (may be null): two stamps of the
+// pass's own, in front of and behind that launch.
 hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, TriLaunchArgs* d_args,
-                        hipStream_t stream, hipEvent_t* events);
+                        hipStream_t stream, hipEvent_t* events, const TriIdArgs* id = nullptr,
+                        hipEvent_t* id_events = nullptr);
+
+// The id pass's other kernels (id_pass.hip; include/tri_raster.h "entity ids"). ids: W x rows.
+// k_id_collect: ORs bit id - 1 of `bits` (nwords words, cleared by the caller) for every id >= 1 inside columns
+// [x0, x0 + w) of local rows [row0, row0 + h).
+hipError_t tri_launch_id_collect(const uint32_t* ids, int32_t W, int32_t x0, int32_t row0, int32_t w, int32_t h,
+                                 uint32_t* bits, uint32_t nwords, hipStream_t stream);
+// k_id_outline: composites rgba over the outline pixels of the draws flagged in sel (ndraws words), width r in 1..8.
+hipError_t tri_launch_id_outline(const uint32_t* ids, const uint32_t* sel, uint32_t ndraws, uint32_t* color, int32_t W,
+                                 int32_t rows, int32_t r, const float rgba[4], hipStream_t stream);
 
 // k_sky_fill (sky_fill.hip): the skybox pass ahead of a TRI_SKY_PREFILLED frame's raster kernel. By value: the pass
 // runs in front of the frame's first kernel, which publishes the frame's own arguments.

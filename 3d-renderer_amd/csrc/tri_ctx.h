@@ -1,6 +1,7 @@
 // tri_ctx.h — the context, geometry and font objects behind the C-ABI handles, and the owning holders their members
 // are made of. Internal to the units that implement the entry points over a context (tri_raster_capi.hip: lifecycle,
-// frame and readback; tri_geometry.hip: geometry; tri_resources.hip: every other upload); the other units keep to the
+// frame and readback; tri_geometry.hip: geometry; tri_resources.hip: every other upload; tri_ids.hip: the entity-id
+// entry points); the other units keep to the
 // accessors of capi_util.h.
 //
 // Ownership: a DevBuf, PinBuf, Event or Staged member frees what it holds when its object is deleted (with the
@@ -43,6 +44,14 @@ struct DevBuf {
         p = nullptr;
         cap = std::max<size_t>(need, 1);
         TRI_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), cap * sizeof(T)));
+        return TRI_OK;
+    }
+    // Free the memory now (nothing queued may still use it); the buffer is empty again.
+    int release() {
+        T* q = p;
+        p = nullptr;
+        cap = 0;
+        if (q) TRI_HIP_TRY(hipFree(q));
         return TRI_OK;
     }
     operator T*() const { return p; }
@@ -110,6 +119,8 @@ struct Staged {
 struct TimingSet {
     Event ev[kStageCount + 1];
     bool shadow = false;  // the frame ran the shadow pre-pass (ev[kStageShadow] was recorded)
+    Event id[2];          // round k_id_raster, made at the first timed frame with the id pass
+    bool has_id = false;  // ... and recorded on this frame
 };
 
 // Geometry (UploadMeshFromCache, Renderer.cpp:1965-2116): one concatenated vertex buffer, one index
@@ -230,6 +241,19 @@ struct tri_ctx {
     bool text_dirty = false;
     Staged text_stage;
 
+    // entity ids (tri_set_id_output, tri_set_outline; tri_ids.hip): the id image of the context's rows, whether the
+    // last tri_render wrote it, the outline's draws as the caller gave them and their per-draw flags on the device
+    // (sel_stage's twin, rebuilt when the outline or the draw count changes), tri_pick_rect's bitmap
+    bool id_on = false, ids_rendered = false;
+    DevBuf<uint32_t> d_ids;
+    bool outline_on = false, sel_dirty = false;
+    std::vector<uint32_t> outline_draws;
+    float outline_rgba[4] = {};
+    uint32_t outline_width = 0, sel_ndraws = 0;
+    Staged sel_stage;
+    DevBuf<uint32_t> d_pick_bits;
+    PinBuf<uint32_t> h_pick;
+
     DevBuf<uint32_t> d_color_own;
     DevBuf<float> d_depth_own;
     DevBuf<uint32_t> d_present;  // tri_blit_linear's owned target
@@ -251,7 +275,13 @@ struct tri_ctx {
     std::vector<TimingSet> pending;
     std::vector<TimingSet> free_sets;
     tri_timing acc{};
+    double acc_id_ms = 0.0;     // tri_get_id_timing: the id pass's own stamps over the timed frames that ran it
+    uint64_t acc_id_frames = 0;
 };
+
+// tri_render's outline pass (tri_ids.hip): the per-draw flags to the device when they changed, then k_id_outline on
+// the context's stream.
+int tri_ids_outline_pass(tri_ctx* c);
 
 inline int make_current(tri_ctx* c) {
     TRI_HIP_TRY(hipSetDevice(c->device));

@@ -587,6 +587,24 @@ int tri_group_readback(tri_group* g, uint8_t* bgra, uint32_t* depth) {
     return TRI_OK;
 }
 
+int tri_group_set_id_output(tri_group* g, int enable) {
+    return each(g, [&](tri_ctx* c) { return tri_set_id_output(c, enable); });
+}
+
+int tri_group_read_ids(tri_group* g, uint32_t* ids) {
+    if (!g || !ids) return tri_internal_fail(TRI_E_INVALID, "tri_group_read_ids: null argument");
+    for (uint32_t r = 0; r < g->n; ++r)  // each band's rows from its own device
+        if (const int rc = tri_read_ids(g->ctx[r], ids + (size_t)g->y0[r] * g->W)) return rc;
+    return TRI_OK;
+}
+
+int tri_group_pick(tri_group* g, int32_t x, int32_t y, tri_pick_result* out) {
+    if (!g || !out) return tri_internal_fail(TRI_E_INVALID, "tri_group_pick: null argument");
+    for (uint32_t r = 0; r < g->n; ++r)
+        if (y >= (int32_t)g->y0[r] && y < (int32_t)g->y1[r]) return tri_pick(g->ctx[r], x, y, out);
+    return tri_internal_fail(TRI_E_INVALID, "tri_group_pick: row outside the frame");
+}
+
 int tri_group_frame(tri_group* g, void** ptr, int32_t* device) {
     if (!g || !ptr || !device) return tri_internal_fail(TRI_E_INVALID, "tri_group_frame: null argument");
     *ptr = g->frame[last_parity(g)];

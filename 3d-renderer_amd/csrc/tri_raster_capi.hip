@@ -144,6 +144,15 @@ int collect_timing(tri_ctx* c) {
         if (t.shadow) TRI_HIP_TRY(hipEventElapsedTime(&ms[kStageShadow], t.ev[kStageShadow].e, t.ev[kStageRaster].e));
         TRI_HIP_TRY(hipEventElapsedTime(&ms[kStageRaster], t.ev[kStageRaster].e, t.ev[kStageCount].e));
         TRI_HIP_TRY(hipEventElapsedTime(&tot, t.ev[0].e, t.ev[kStageCount].e));
+        if (t.has_id) {
+            // the id pass runs between the set-up (or shadow) stamp and the raster stamp: its own stamps take it out
+            // of that stage, so tri_timing's stages mean what they mean with the output off; ms_frame keeps it
+            float id_ms = 0.0f;
+            TRI_HIP_TRY(hipEventElapsedTime(&id_ms, t.id[0].e, t.id[1].e));
+            ms[t.shadow ? kStageShadow : kStageSetup] -= id_ms;
+            c->acc_id_ms += id_ms;
+            c->acc_id_frames += 1;
+        }
         c->acc.ms_vertex += ms[kStageVertex];
         c->acc.ms_setup += ms[kStageSetup];
         c->acc.ms_shadow += ms[kStageShadow];
@@ -366,6 +375,7 @@ int tri_frame_alpha(tri_ctx* c, int32_t* alpha) {
         uniform = (int32_t)unorm8_host((c->mat0.base_color_factor[3] * d.pc.tint[3]) * t) == a;
     }
     if (c->text_font && !c->text_quads.empty()) uniform = false;  // the text pass blends into the alpha channel
+    if (c->outline_on && !c->outline_draws.empty()) uniform = false;  // so does the selection outline
     *alpha = uniform ? a : -1;
     return TRI_OK;
 }
@@ -510,7 +520,16 @@ int tri_render(tri_ctx* c) {
     }
     ts.shadow = fp.shadow_on != 0;
     TriFramePlan plan;
-    tri_plan_frame(fp, plan);
+    tri_plan_frame(fp, plan, c->id_on);
+    hipEvent_t id_stamps[2], *id_ev = nullptr;
+    ts.has_id = timed && c->id_on && fp.nchunks > 0;  // (the plan holds the id pass)
+    if (ts.has_id) {
+        for (int i = 0; i < 2; ++i) {
+            if ((rc = ts.id[i].ensure(hipEventDefault))) return rc;
+            id_stamps[i] = ts.id[i].e;
+        }
+        id_ev = id_stamps;
+    }
     if (const int kind = tri_raster_kind(fp); kind >= 0)  // the frame-kind kernel the plan took
         c->last_path |= TRI_PATH_KIND | ((uint32_t)kind << TRI_PATH_KIND_SHIFT);
 #ifdef TRI_DIAG_FRONT
@@ -532,8 +551,16 @@ int tri_render(tri_ctx* c) {
         sa.texels = c->d_sky; sa.lut = c->d_lut; sa.color = c->d_color;
         TRI_HIP_TRY(tri_launch_sky_fill(sa, c->stream));
     }
-    TRI_HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev));
+    // the id pass (tri_set_id_output): in the plan ahead of the raster kernel; a frame without primitives has no queues
+    // to walk and takes an all-background image
+    const TriIdArgs ida{c->d_ids.p};
+    if (c->id_on && fp.nchunks == 0)
+        TRI_HIP_TRY(hipMemsetAsync(c->d_ids, 0, (size_t)c->W * (size_t)(c->y1 - c->y0) * 4, c->stream));
+    TRI_HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev, c->id_on ? &ida : nullptr, id_ev));
     c->launched = true;
+    c->ids_rendered = c->id_on;
+    // the selection outline (tri_set_outline): over the frame, under the text
+    if (c->id_on && c->outline_on && (rc = tri_ids_outline_pass(c))) return rc;
     // the text pass (TextRenderer::RecordViewport, after the mesh / sky pass): only when quads are set. A
     // TRI_E_OVERFLOW re-render restarts from the clear, so the overlay is reapplied by construction.
     if (c->text_font && !c->text_quads.empty()) {
@@ -634,6 +661,8 @@ int tri_set_timing(tri_ctx* c, int enable) {
     c->timing_period = enable > 0 ? (uint32_t)enable : 1u;
     c->timing_counter = 0;
     c->acc = tri_timing{};
+    c->acc_id_ms = 0.0;
+    c->acc_id_frames = 0;
     return TRI_OK;
 }
 
@@ -642,6 +671,15 @@ int tri_get_timing(tri_ctx* c, tri_timing* out) {
     int rc = collect_timing(c);
     if (rc) return rc;
     *out = c->acc;
+    return TRI_OK;
+}
+
+int tri_get_id_timing(tri_ctx* c, double* ms_id, uint64_t* frames) {
+    if (!c || !ms_id || !frames) return fail(TRI_E_INVALID, "tri_get_id_timing: null argument");
+    int rc = collect_timing(c);
+    if (rc) return rc;
+    *ms_id = c->acc_id_ms;
+    *frames = c->acc_id_frames;
     return TRI_OK;
 }
 

@@ -42,6 +42,21 @@ public:
     static void SubmitText(uint32_t viewportId, const glm::vec2& position, const glm::vec4& color, const std::string& text) {
         GetRenderer().SubmitText(viewportId, position, color, text);
     }
+    // Entity ids: picking, rectangle selection, the per-pixel entity image and the selection outline
+    static void SetSelectedEntity(ECS::Entity entity) { GetRenderer().SetSelectedEntity(entity); }
+    static void SetEntityIdOutputEnabled(uint32_t viewportId, bool enabled) { GetRenderer().SetEntityIdOutputEnabled(viewportId, enabled); }
+    static bool PickEntity(uint32_t viewportId, int32_t x, int32_t y, ECS::Entity& out, float* depth01 = nullptr) {
+        return GetRenderer().PickEntity(viewportId, x, y, out, depth01);
+    }
+    static std::vector<ECS::Entity> PickEntitiesInRect(uint32_t viewportId, int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
+        return GetRenderer().PickEntitiesInRect(viewportId, x0, y0, x1, y1);
+    }
+    static bool ReadViewportEntityIds(uint32_t viewportId, std::vector<uint32_t>& out, uint32_t background = 0xFFFFFFFFu) {
+        return GetRenderer().ReadViewportEntityIds(viewportId, out, background);
+    }
+    static void SetSelectionOutline(bool enabled, const glm::vec4& colour = glm::vec4(1.0f, 0.6f, 0.0f, 1.0f), uint32_t widthPx = 2) {
+        GetRenderer().SetSelectionOutline(enabled, colour, widthPx);
+    }
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }

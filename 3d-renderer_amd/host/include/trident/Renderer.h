@@ -255,6 +255,31 @@ public:
     std::vector<Geometry::Material>& GetMaterials() { return m_Materials; }
     const std::vector<Geometry::Material>& GetMaterials() const { return m_Materials; }
 
+    // Entity ids (tri_set_id_output and its readers): which entity a pixel of a viewport shows, for clicks in a viewport
+    // panel, rectangle selection, segmentation masks beside the colour tensor, and the selection outline.
+    // SetSelectedEntity has the reference's name and meaning (Renderer.cpp:6053: it stores the entity); kNoEntity
+    // selects nothing. Every frame keeps, per target, the draw index -> entity table of the draw list it submitted
+    // (mesh commands, then sprites), so the readers answer for the latest finished frame of the viewport: they fence
+    // like ReadViewportPixels, and each ring target (SetFramesInFlight) carries its own id image and table.
+    static constexpr ECS::Entity kNoEntity = 0xFFFFFFFFu;
+    void SetSelectedEntity(ECS::Entity entity) { m_SelectedEntity = entity; }
+    ECS::Entity GetSelectedEntity() const { return m_SelectedEntity; }
+    // From the viewport's next DrawFrame on, its frames carry ids (off: they stop, unless the outline needs them).
+    void SetEntityIdOutputEnabled(uint32_t viewportId, bool enabled);
+    // The entity at pixel (x, y) of the viewport's latest frame and, optionally, its depth in [0, 1]. false on
+    // background, outside the viewport, for a viewport that does not exist or whose latest frame carries no ids.
+    bool PickEntity(uint32_t viewportId, int32_t x, int32_t y, ECS::Entity& out, float* depth01 = nullptr);
+    // The distinct entities with a pixel inside the inclusive rectangle (clamped to the viewport), in draw order.
+    std::vector<ECS::Entity> PickEntitiesInRect(uint32_t viewportId, int32_t x0, int32_t y0, int32_t x1, int32_t y1);
+    // The entity of every pixel (width * height, rows top to bottom), `background` where there is none.
+    bool ReadViewportEntityIds(uint32_t viewportId, std::vector<uint32_t>& out, uint32_t background = 0xFFFFFFFFu);
+    // Outlines every draw of the selected entity in every single-device viewport that renders it (tri_set_outline: an
+    // outer outline of the visible silhouette, widthPx in 1..8, under the text), and turns the id output on for those
+    // viewports. Refused with a log line (the outline stays off) while SetDeviceCount > 1, which also turns it off:
+    // a band's halo lies in another band.
+    void SetSelectionOutline(bool enabled, const glm::vec4& colour = glm::vec4(1.0f, 0.6f, 0.0f, 1.0f), uint32_t widthPx = 2);
+    bool IsSelectionOutlineEnabled() const { return m_SelectionOutline; }
+
     // Frame readback (ResolvePendingReadback, Renderer.cpp:1299-1389): RGBA8 rows of the viewport
     // (BGRA reordered to RGBA), optionally the D32 depth.
     bool ReadViewportPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr);
@@ -328,6 +353,13 @@ private:
         tri_shadow_config m_Shadow{};      // the pre-pass configuration last set on this context
         tri_image m_Image{};               // GetViewportTexture's handle (after the first frame)
         bool m_HasImage = false;
+        // entity ids: the context's id output is on; the outline last set on it (draws and style) so that an unchanged
+        // one is not set again; the entity of each draw of the frame last submitted to this target
+        bool m_IdOutput = false, m_OutlineSet = false;
+        std::vector<uint32_t> m_OutlineDraws;
+        glm::vec4 m_OutlineColour{0.0f};
+        uint32_t m_OutlineWidth = 0;
+        std::vector<ECS::Entity> m_DrawEntities;
     };
 
     void CreateSkyboxCubemap();
@@ -340,7 +372,11 @@ private:
     void GatherDraws();  // GatherMeshDraws + GatherSpriteDraws (adds the sprite quad to the geometry once)
     void PrepareBonePaletteBuffer();
     void UpdateUniformBuffer(const Camera* camera, tri_global_ubo& out) const;
-    void BuildDrawList(std::vector<tri_draw>& out) const;
+    void BuildDrawList(std::vector<tri_draw>& out, std::vector<ECS::Entity>* entities = nullptr) const;
+    // before the target's tri_render: the id output and the outline this frame wants on it
+    bool SetTargetIds(ViewportContext& target, uint32_t viewportId, const std::vector<tri_draw>& draws,
+                      const std::vector<ECS::Entity>& entities);
+    const ViewportContext* IdTarget(uint32_t viewportId);  // fenced; null unless the latest frame carries ids
     const Camera* GetActiveCamera(const ViewportContext& context) const;
     bool PrepareViewport(ViewportContext& context);
     // One viewport pass: pre-pass / palette / UBO / draws, then tri_render (asynchronous); false on error.
@@ -426,6 +462,11 @@ private:
     std::vector<TextureSlot> m_TextureSlots;
     std::unordered_map<std::string, uint32_t> m_TextureSlotLookup;
 
+    ECS::Entity m_SelectedEntity = kNoEntity;
+    std::map<uint32_t, bool> m_IdOutputViewports;  // SetEntityIdOutputEnabled, by viewport id
+    bool m_SelectionOutline = false;
+    glm::vec4 m_OutlineColour{1.0f, 0.6f, 0.0f, 1.0f};
+    uint32_t m_OutlineWidth = 2;
     std::map<uint32_t, ViewportContext> m_Viewports;
     ViewportInfo m_LastViewport{};
     uint32_t m_ActiveViewportId = 0;

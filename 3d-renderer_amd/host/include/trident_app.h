@@ -242,6 +242,25 @@ int trident_dataset_state(trident_dataset* dataset, int* enabled, uint32_t* inte
 /* FrameDatasetRecorder::WriteNpyFile alone: TRI_OK, or TRI_E_STATE where it refuses (no file is written then). */
 int trident_dataset_write_npy(const char* path, const float* data, uint64_t count, const int64_t* shape, uint32_t rank);
 
+/* ---- entity ids: picking, rectangle selection, the entity image, the selection outline ---- */
+/* Renderer::SetEntityIdOutputEnabled: from the viewport's next draw_frame on. */
+int trident_app_set_entity_id_output(trident_app* app, uint32_t viewport_id, int enabled);
+/* Renderer::PickEntity on the viewport's latest frame (fences): *hit 1 with the entity and its depth in [0, 1]
+ * (depth01 nullable), 0 on background, outside the viewport or without ids. */
+int trident_app_pick_entity(trident_app* app, uint32_t viewport_id, int32_t x, int32_t y, int* hit, uint32_t* entity,
+                            float* depth01);
+/* Renderer::PickEntitiesInRect: *count distinct entities in draw order, the first min(capacity, *count) written. */
+int trident_app_pick_entities_in_rect(trident_app* app, uint32_t viewport_id, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                                      uint32_t* entities, uint32_t capacity, uint32_t* count);
+/* Renderer::ReadViewportEntityIds: width * height entities (`background` where none); TRI_E_STATE where it returns
+ * false, TRI_E_INVALID when capacity (in pixels) is short. */
+int trident_app_read_entity_ids(trident_app* app, uint32_t viewport_id, uint32_t* entities, uint64_t capacity,
+                                uint32_t background);
+/* Renderer::SetSelectedEntity (0xFFFFFFFF: none) and Renderer::SetSelectionOutline; the latter is TRI_E_STATE where
+ * the renderer refuses (SetDeviceCount > 1, a width outside 1..8): the outline is then as it was, or off. */
+int trident_app_set_selected_entity(trident_app* app, uint32_t entity);
+int trident_app_set_selection_outline(trident_app* app, int enabled, const float rgba[4], uint32_t width_px);
+
 /* ---- text overlay ---- */
 /* Renderer::SubmitText: `bytes` bytes of UTF-8 (no terminator needed) at `position` (viewport pixels) in `color`
  * (RGBA) for the viewport's next draw_frame. */

@@ -212,6 +212,9 @@ struct Target {
     int Readback(uint8_t* bgra, uint32_t* depth) const {
         return g ? tri_group_readback(g, bgra, depth) : tri_readback(c, bgra, depth);
     }
+    int IdOutput(bool on) const { return g ? tri_group_set_id_output(g, on ? 1 : 0) : tri_set_id_output(c, on ? 1 : 0); }
+    int ReadIds(uint32_t* ids) const { return g ? tri_group_read_ids(g, ids) : tri_read_ids(c, ids); }
+    int Pick(int32_t x, int32_t y, tri_pick_result* out) const { return g ? tri_group_pick(g, x, y, out) : tri_pick(c, x, y, out); }
 };
 
 }  // namespace
@@ -437,6 +440,10 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         LogError("SetDeviceCount", "multi-device viewports have no frame generator: the model was unloaded");
         m_FrameGenerator.Shutdown();
         if (m_AiFromDevice) SubmitAiInterpolation(nullptr, 0, 0, 0);
+    }
+    if (m_SelectionOutline && devs.size() > 1) {
+        LogError("SetDeviceCount", "multi-device viewports draw no selection outline: it was turned off");
+        m_SelectionOutline = false;
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
@@ -1000,8 +1007,9 @@ bool Renderer::SubmitPoseGraph(ViewportContext& vc, const std::vector<int32_t>& 
     return true;
 }
 
-void Renderer::BuildDrawList(std::vector<tri_draw>& out) const {  // Renderer.cpp:5110-5151
+void Renderer::BuildDrawList(std::vector<tri_draw>& out, std::vector<ECS::Entity>* entities) const {  // Renderer.cpp:5110-5151
     out.clear();
+    if (entities) entities->clear();  // the draw index -> entity table of this list (entity ids)
     for (const MeshDrawCommand& cmd : m_MeshDrawCommands) {
         if (!cmd.m_Component || cmd.m_Component->m_MeshIndex >= m_MeshDrawInfo.size()) continue;
         const MeshDrawInfo& info = m_MeshDrawInfo[cmd.m_Component->m_MeshIndex];
@@ -1024,6 +1032,7 @@ void Renderer::BuildDrawList(std::vector<tri_draw>& out) const {  // Renderer.cp
         pc.bone_offset = static_cast<int32_t>(cmd.m_BoneOffset);  // :5145-5146
         pc.bone_count = static_cast<int32_t>(cmd.m_BoneCount);
         out.push_back(d);
+        if (entities) entities->push_back(cmd.m_Entity);
     }
     if (!m_HasSpriteGeometry) return;
     for (const SpriteDrawCommand& cmd : m_SpriteDrawList) {  // DrawSprites, Renderer.cpp:3044-3089
@@ -1045,6 +1054,7 @@ void Renderer::BuildDrawList(std::vector<tri_draw>& out) const {  // Renderer.cp
                               ? cmd.m_TextureComponent->m_TextureSlot : 0;
         pc.material_index = -1;  // RenderablePushConstant default (RenderData.h:25)
         out.push_back(d);
+        if (entities) entities->push_back(cmd.m_Entity);
     }
 }
 
@@ -1269,6 +1279,8 @@ bool Renderer::PrepareViewport(ViewportContext& vc) {
         vc.m_Shadow = tri_shadow_config{};  // a fresh context starts without the pre-pass and bones
         vc.m_BonePalette.clear();
         vc.m_HasPosedSuffix = false;
+        vc.m_IdOutput = vc.m_OutlineSet = false;  // ... and without the id output and the outline (SetTargetIds)
+        vc.m_DrawEntities.clear();
     }
     const Target t{vc.m_Ctx, vc.m_Group};
     if (vc.m_GeometryGeneration != m_GeometryGeneration && multi) {
@@ -1431,7 +1443,8 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     GatherDraws();
     PrepareBonePaletteBuffer();
     std::vector<tri_draw> draws;
-    BuildDrawList(draws);
+    std::vector<ECS::Entity> drawEntities;
+    BuildDrawList(draws, &drawEntities);
     tri_shadow_config shadow;
     const bool shadowOn = BuildShadowConfig(shadow);
     std::vector<ViewportContext*> submitted;
@@ -1447,6 +1460,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         tri_global_ubo ubo;
         UpdateUniformBuffer(GetActiveCamera(vc), ubo);
         if (!SetTargetText(vc, id)) LogError("DrawFrame", "the text overlay of this frame is missing");
+        if (!SetTargetIds(vc, id, draws, drawEntities)) LogError("DrawFrame", "the entity ids of this frame are missing");
         if (!SubmitTarget(vc, TargetUniforms(vc, ubo), draws, shadow, shadowOn)) return;
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
@@ -2093,6 +2107,144 @@ void Renderer::RecordFrameTiming(double ms) {  // Renderer.cpp:6286-6343
     st.AverageMilliseconds = sumMs / (double)m_PerformanceSampleCount;
     st.AverageFPS = sumFps / (double)m_PerformanceSampleCount;
     m_PerformanceStats = st;
+}
+
+// ---- entity ids ---------------------------------------------------------------------------------------------------
+void Renderer::SetEntityIdOutputEnabled(uint32_t viewportId, bool enabled) { m_IdOutputViewports[viewportId] = enabled; }
+
+void Renderer::SetSelectionOutline(bool enabled, const glm::vec4& colour, uint32_t widthPx) {
+    if (enabled && m_Devices.size() > 1) {
+        LogError("selection outline", "multi-device viewports (SetDeviceCount > 1) draw no outline: a band's halo lies in another band");
+        m_SelectionOutline = false;
+        return;
+    }
+    if (enabled && (widthPx < 1 || widthPx > 8)) {
+        LogError("selection outline", "the width must be 1..8 pixels");
+        return;
+    }
+    m_SelectionOutline = enabled;
+    if (enabled) {
+        m_OutlineColour = colour;
+        m_OutlineWidth = widthPx;
+    }
+}
+
+// The id output follows SetEntityIdOutputEnabled or the outline's need of it; the outline is the selected entity's
+// draws of this frame's list. Both are context state that stays set, so only changes are sent (ring targets are
+// separate contexts: each is brought up to date when its turn comes).
+bool Renderer::SetTargetIds(ViewportContext& vc, uint32_t viewportId, const std::vector<tri_draw>& draws,
+                            const std::vector<ECS::Entity>& entities) {
+    const Target t{vc.m_Ctx, vc.m_Group};
+    std::vector<uint32_t> selected;
+    const bool outline = m_SelectionOutline && vc.m_Ctx && m_SelectedEntity != kNoEntity;
+    if (outline)
+        for (uint32_t d = 0; d < entities.size(); ++d)
+            if (entities[d] == m_SelectedEntity) selected.push_back(d);
+    auto want = m_IdOutputViewports.find(viewportId);
+    const bool ids = (want != m_IdOutputViewports.end() && want->second) || !selected.empty();
+    bool ok = true;
+    if (ids != vc.m_IdOutput) {
+        if (t.IdOutput(ids) != TRI_OK) {
+            LogError("entity ids", tri_last_error());
+            ok = false;
+        } else {
+            vc.m_IdOutput = ids;
+            if (!ids) vc.m_OutlineSet = false;  // (switching the output off removes the context's outline)
+        }
+    }
+    vc.m_DrawEntities = vc.m_IdOutput ? entities : std::vector<ECS::Entity>();
+    if (!vc.m_Ctx) return ok;
+    if (selected.empty() || !vc.m_IdOutput) {
+        if (vc.m_OutlineSet && tri_set_outline(vc.m_Ctx, nullptr) != TRI_OK) ok = false;
+        vc.m_OutlineSet = false;
+        return ok;
+    }
+    const glm::vec4 &a = vc.m_OutlineColour, &b = m_OutlineColour;
+    if (vc.m_OutlineSet && vc.m_OutlineDraws == selected && a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w &&
+        vc.m_OutlineWidth == m_OutlineWidth)
+        return ok;
+    // (tri_set_outline checks the indices against the context's current draw list: this frame's goes in first;
+    // SubmitTarget's own tri_set_draws of the same list then changes nothing)
+    tri_outline o{};
+    o.draws = selected.data();
+    o.draw_count = (uint32_t)selected.size();
+    o.rgba[0] = m_OutlineColour.x; o.rgba[1] = m_OutlineColour.y; o.rgba[2] = m_OutlineColour.z; o.rgba[3] = m_OutlineColour.w;
+    o.width_px = m_OutlineWidth;
+    if (tri_set_draws(vc.m_Ctx, draws.data(), (uint32_t)draws.size()) != TRI_OK || tri_set_outline(vc.m_Ctx, &o) != TRI_OK) {
+        LogError("selection outline", tri_last_error());
+        return false;
+    }
+    vc.m_OutlineSet = true;
+    vc.m_OutlineDraws = selected;
+    vc.m_OutlineColour = m_OutlineColour;
+    vc.m_OutlineWidth = m_OutlineWidth;
+    return ok;
+}
+
+const Renderer::ViewportContext* Renderer::IdTarget(uint32_t viewportId) {
+    FinishFrame();
+    const ViewportContext* vc = LatestTarget(viewportId);
+    if (!vc || (!vc->m_Ctx && !vc->m_Group) || !vc->m_IdOutput) return nullptr;
+    return vc;
+}
+
+bool Renderer::PickEntity(uint32_t viewportId, int32_t x, int32_t y, ECS::Entity& out, float* depth01) {
+    const ViewportContext* vc = IdTarget(viewportId);
+    if (!vc || x < 0 || y < 0 || x >= (int32_t)vc->m_Width || y >= (int32_t)vc->m_Height) return false;
+    tri_pick_result r{};
+    if (Target{vc->m_Ctx, vc->m_Group}.Pick(x, y, &r) != TRI_OK) {
+        LogError("entity pick", tri_last_error());
+        return false;
+    }
+    if (r.id == 0 || r.id > vc->m_DrawEntities.size()) return false;
+    out = vc->m_DrawEntities[r.id - 1];
+    if (depth01) {
+        float z = 1.0f;
+        if (r.has_depth) std::memcpy(&z, &r.depth_bits, 4);
+        *depth01 = z;
+    }
+    return true;
+}
+
+std::vector<ECS::Entity> Renderer::PickEntitiesInRect(uint32_t viewportId, int32_t x0, int32_t y0, int32_t x1, int32_t y1) {
+    std::vector<ECS::Entity> found;
+    const ViewportContext* vc = IdTarget(viewportId);
+    if (!vc || x1 < x0 || y1 < y0) return found;
+    const uint32_t n = (uint32_t)vc->m_DrawEntities.size();
+    std::vector<uint32_t> bits((n + 31u) / 32u + 1u, 0u);
+    if (vc->m_Ctx) {
+        if (tri_pick_rect(vc->m_Ctx, x0, y0, x1, y1, bits.data(), (uint32_t)bits.size(), nullptr) != TRI_OK) {
+            LogError("entity pick", tri_last_error());
+            return found;
+        }
+    } else {  // a multi-device viewport: from the bands' ids on the host
+        std::vector<uint32_t> ids((size_t)vc->m_Width * vc->m_Height);
+        if (tri_group_read_ids(vc->m_Group, ids.data()) != TRI_OK) {
+            LogError("entity pick", tri_last_error());
+            return found;
+        }
+        for (int32_t y = std::max(y0, 0); y <= std::min(y1, (int32_t)vc->m_Height - 1); ++y)
+            for (int32_t x = std::max(x0, 0); x <= std::min(x1, (int32_t)vc->m_Width - 1); ++x) {
+                const uint32_t id = ids[(size_t)y * vc->m_Width + x];
+                if (id && id <= n) bits[(id - 1) / 32] |= 1u << ((id - 1) & 31u);
+            }
+    }
+    for (uint32_t d = 0; d < n; ++d)  // draw order; an entity with several draws (none today) is named once
+        if ((bits[d / 32] >> (d & 31u)) & 1u)
+            if (std::find(found.begin(), found.end(), vc->m_DrawEntities[d]) == found.end()) found.push_back(vc->m_DrawEntities[d]);
+    return found;
+}
+
+bool Renderer::ReadViewportEntityIds(uint32_t viewportId, std::vector<uint32_t>& out, uint32_t background) {
+    const ViewportContext* vc = IdTarget(viewportId);
+    if (!vc) return false;
+    out.resize((size_t)vc->m_Width * vc->m_Height);
+    if (Target{vc->m_Ctx, vc->m_Group}.ReadIds(out.data()) != TRI_OK) {
+        LogError("entity ids", tri_last_error());
+        return false;
+    }
+    for (uint32_t& v : out) v = (v == 0 || v > vc->m_DrawEntities.size()) ? background : vc->m_DrawEntities[v - 1];
+    return true;
 }
 
 void* Renderer::GetViewportTexture(uint32_t viewportId) const {

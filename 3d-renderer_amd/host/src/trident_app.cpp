@@ -633,6 +633,64 @@ int trident_app_recording_state(trident_app* app, int* recording, uint64_t* fram
     });
 }
 
+int trident_app_set_entity_id_output(trident_app* app, uint32_t viewport_id, int enabled) {
+    return Guard(app, [&] {
+        app->renderer.SetEntityIdOutputEnabled(viewport_id, enabled != 0);
+        return TRI_OK;
+    });
+}
+
+int trident_app_pick_entity(trident_app* app, uint32_t viewport_id, int32_t x, int32_t y, int* hit, uint32_t* entity,
+                            float* depth01) {
+    return Guard(app, [&] {
+        if (!hit || !entity) return TRI_E_INVALID;
+        ECS::Entity e = Renderer::kNoEntity;
+        *hit = app->renderer.PickEntity(viewport_id, x, y, e, depth01) ? 1 : 0;
+        *entity = e;
+        return TRI_OK;
+    });
+}
+
+int trident_app_pick_entities_in_rect(trident_app* app, uint32_t viewport_id, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
+                                      uint32_t* entities, uint32_t capacity, uint32_t* count) {
+    return Guard(app, [&] {
+        if (!count || (capacity && !entities)) return TRI_E_INVALID;
+        const std::vector<ECS::Entity> found = app->renderer.PickEntitiesInRect(viewport_id, x0, y0, x1, y1);
+        *count = (uint32_t)found.size();
+        for (uint32_t i = 0; i < capacity && i < found.size(); ++i) entities[i] = found[i];
+        return TRI_OK;
+    });
+}
+
+int trident_app_read_entity_ids(trident_app* app, uint32_t viewport_id, uint32_t* entities, uint64_t capacity,
+                                uint32_t background) {
+    return Guard(app, [&] {
+        if (!entities) return TRI_E_INVALID;
+        std::vector<uint32_t> ids;
+        if (!app->renderer.ReadViewportEntityIds(viewport_id, ids, background)) return TRI_E_STATE;
+        if (ids.size() > capacity) return TRI_E_INVALID;
+        std::memcpy(entities, ids.data(), ids.size() * sizeof(uint32_t));
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_selected_entity(trident_app* app, uint32_t entity) {
+    return Guard(app, [&] {
+        app->renderer.SetSelectedEntity(entity);
+        return TRI_OK;
+    });
+}
+
+int trident_app_set_selection_outline(trident_app* app, int enabled, const float rgba[4], uint32_t width_px) {
+    return Guard(app, [&] {
+        if (enabled && !rgba) return TRI_E_INVALID;
+        if (enabled) app->renderer.SetSelectionOutline(true, glm::vec4(rgba[0], rgba[1], rgba[2], rgba[3]), width_px);
+        else app->renderer.SetSelectionOutline(false);
+        const bool refused = enabled && (!app->renderer.IsSelectionOutlineEnabled() || width_px < 1 || width_px > 8);
+        return refused ? TRI_E_STATE : TRI_OK;
+    });
+}
+
 struct trident_font {
     TextRenderer text;
 };

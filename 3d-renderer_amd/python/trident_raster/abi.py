@@ -203,6 +203,23 @@ class TriImage(C.Structure):
     ]
 
 
+# entity ids (include/tri_raster.h): the id image's format, one picked pixel, the selection outline
+TRI_FORMAT_R32_UINT = 98
+TRI_MAX_OUTLINE_WIDTH = 8
+
+
+class TriPickResult(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("depth_bits", C.c_uint32), ("has_depth", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TriOutline(C.Structure):
+    _fields_ = [("draws", C.POINTER(C.c_uint32)), ("draw_count", C.c_uint32), ("rgba", C.c_float * 4),
+                ("width_px", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(TriPickResult) == 16 and C.sizeof(TriOutline) == 40
+
+
 class TriGroupConfig(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -444,6 +461,17 @@ CABI_FUNCTIONS = [
     ("tri_group_read_present", C.c_int, [C.c_void_p, C.c_void_p]),
     ("tri_group_transfer_info", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("tri_group_transfer_format", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("tri_set_id_output", C.c_int, [C.c_void_p, C.c_int]),
+    ("tri_read_ids", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tri_get_id_output", C.c_int, [C.c_void_p, C.POINTER(TriImage)]),
+    ("tri_pick", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(TriPickResult)]),
+    ("tri_pick_rect", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
+                                C.POINTER(C.c_uint32)]),
+    ("tri_set_outline", C.c_int, [C.c_void_p, C.POINTER(TriOutline)]),
+    ("tri_get_id_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("tri_group_set_id_output", C.c_int, [C.c_void_p, C.c_int]),
+    ("tri_group_read_ids", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tri_group_pick", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(TriPickResult)]),
 ]
 
 

@@ -118,6 +118,14 @@ _APP_FUNCTIONS = [
     ("trident_dataset_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint64)]),
     ("trident_dataset_write_npy", C.c_int, [C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int64), C.c_uint32]),
+    ("trident_app_set_entity_id_output", C.c_int, [C.c_void_p, C.c_uint32, C.c_int]),
+    ("trident_app_pick_entity", C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_int),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    ("trident_app_pick_entities_in_rect", C.c_int, [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                    C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("trident_app_read_entity_ids", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
+    ("trident_app_set_selected_entity", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("trident_app_set_selection_outline", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float * 4), C.c_uint32]),
     ("trident_app_submit_text", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4),
                                           C.c_char_p, C.c_uint32]),
     ("trident_app_set_font", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
@@ -403,6 +411,51 @@ class TridentApp:
         pos, col = (C.c_float * 2)(*position), (C.c_float * 4)(*color)
         _check(self._lib.trident_app_submit_text(self._h, viewport_id, C.byref(pos), C.byref(col), data, len(data)),
                "submit_text")
+
+    # ---- entity ids ----
+    NO_ENTITY = 0xFFFFFFFF
+
+    def set_entity_id_output(self, viewport_id, enabled=True):
+        """Renderer::SetEntityIdOutputEnabled."""
+        _check(self._lib.trident_app_set_entity_id_output(self._h, viewport_id, 1 if enabled else 0), "set_entity_id_output")
+
+    def pick_entity(self, viewport_id, x, y):
+        """Renderer::PickEntity: (entity, depth in [0, 1]), or None where it returns false."""
+        hit, ent, z = C.c_int(), C.c_uint32(), C.c_float()
+        _check(self._lib.trident_app_pick_entity(self._h, viewport_id, int(x), int(y), C.byref(hit), C.byref(ent), C.byref(z)),
+               "pick_entity")
+        return (ent.value, z.value) if hit.value else None
+
+    def pick_entities_in_rect(self, viewport_id, x0, y0, x1, y1, capacity=1024):
+        """Renderer::PickEntitiesInRect: the distinct entities, in draw order."""
+        out = np.zeros(capacity, np.uint32)
+        n = C.c_uint32()
+        _check(self._lib.trident_app_pick_entities_in_rect(self._h, viewport_id, int(x0), int(y0), int(x1), int(y1),
+                                                           out.ctypes.data, capacity, C.byref(n)), "pick_entities_in_rect")
+        assert n.value <= capacity
+        return out[: n.value].tolist()
+
+    def read_entity_ids(self, viewport_id, width, height, background=0xFFFFFFFF):
+        """Renderer::ReadViewportEntityIds: uint32 [height, width], or None where it returns false."""
+        out = np.zeros((height, width), np.uint32)
+        rc = self._lib.trident_app_read_entity_ids(self._h, viewport_id, out.ctypes.data, out.size, background)
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "read_entity_ids")
+        return out
+
+    def set_selected_entity(self, entity):
+        """Renderer::SetSelectedEntity (None: no selection)."""
+        _check(self._lib.trident_app_set_selected_entity(self._h, self.NO_ENTITY if entity is None else entity),
+               "set_selected_entity")
+
+    def set_selection_outline(self, enabled, colour=(1.0, 0.6, 0.0, 1.0), width_px=2):
+        """Renderer::SetSelectionOutline; False where the renderer refuses it."""
+        col = (C.c_float * 4)(*[float(c) for c in colour])
+        rc = self._lib.trident_app_set_selection_outline(self._h, 1 if enabled else 0, C.byref(col), width_px)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_selection_outline")
+        return rc == abi.TRI_OK
 
     def set_font(self, path, pixel_height=32.0):
         """Renderer::SetTextFont; returns its bool."""

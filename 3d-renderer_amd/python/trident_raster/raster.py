@@ -277,6 +277,51 @@ class TriRaster:
                 if e.code != abi.TRI_E_OVERFLOW or attempt == retries:
                     raise
 
+    # ---- entity ids ----
+    def set_id_output(self, enable=True):
+        """tri_set_id_output: every following render also writes the per-pixel draw ids."""
+        _check(_lib.tri_set_id_output(self._ctx, 1 if enable else 0))
+
+    def read_ids(self):
+        """tri_read_ids: uint32 [rows, W]; 0 = background, else the draw's index in set_draws' list + 1."""
+        out = np.empty((self.rows, self.width), dtype=np.uint32)
+        _check(_lib.tri_read_ids(self._ctx, _ptr(out)))
+        return out
+
+    def id_image(self):
+        img = abi.TriImage()
+        _check(_lib.tri_get_id_output(self._ctx, C.byref(img)))
+        return img
+
+    def pick(self, x, y):
+        """tri_pick: (id, depth bits or None under TRI_FLAG_NO_DEPTH_OUTPUT) of full-frame pixel (x, y)."""
+        p = abi.TriPickResult()
+        _check(_lib.tri_pick(self._ctx, int(x), int(y), C.byref(p)))
+        return p.id, (p.depth_bits if p.has_depth else None)
+
+    def pick_rect(self, x0, y0, x1, y1, draw_count):
+        """tri_pick_rect: the sorted draw indices with a pixel inside the inclusive rectangle."""
+        return _pick_rect(lambda *a: _lib.tri_pick_rect(self._ctx, *a), x0, y0, x1, y1, draw_count)
+
+    def set_outline(self, draws, rgba=(1.0, 0.6, 0.0, 1.0), width_px=2):
+        """tri_set_outline: outline the listed draws on every following frame; draws None removes the outline."""
+        if draws is None:
+            _check(_lib.tri_set_outline(self._ctx, None))
+            return
+        d = np.ascontiguousarray(draws, dtype=np.uint32).reshape(-1)
+        o = abi.TriOutline()
+        o.draws = d.ctypes.data_as(C.POINTER(C.c_uint32)) if d.size else None
+        o.draw_count = d.size
+        o.rgba = (C.c_float * 4)(*[float(c) for c in rgba])
+        o.width_px = int(width_px)
+        _check(_lib.tri_set_outline(self._ctx, C.byref(o)))
+
+    def id_timing(self):
+        """tri_get_id_timing: (summed ms of k_id_raster, timed frames that ran it)."""
+        ms, n = C.c_double(), C.c_uint64()
+        _check(_lib.tri_get_id_timing(self._ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def set_timing(self, enable, period=1):
         """Per-stage HIP-event timing of every `period`-th frame (enable=False: off)."""
         _check(_lib.tri_set_timing(self._ctx, int(period) if enable else 0))
@@ -290,6 +335,16 @@ class TriRaster:
         s = abi.TriFrameStats()
         _check(_lib.tri_get_frame_stats(self._ctx, C.byref(s)))
         return {k: getattr(s, k) for k, _ in abi.TriFrameStats._fields_}
+
+
+def _pick_rect(call, x0, y0, x1, y1, draw_count):
+    words = max((int(draw_count) + 31) // 32, 1)
+    bits = np.zeros(words, dtype=np.uint32)
+    n = C.c_uint32()
+    _check(call(int(x0), int(y0), int(x1), int(y1), _ptr(bits), words, C.byref(n)))
+    found = [d for d in range(int(draw_count)) if (int(bits[d // 32]) >> (d % 32)) & 1]
+    assert len(found) == n.value, (found, n.value)
+    return found
 
 
 def _text_quads(quads):
@@ -786,6 +841,20 @@ class TriGroup:
         dep = np.empty((self.height, self.width), dtype=np.uint32) if depth else None
         _check(_lib.tri_group_readback(self._g, _ptr(col), _ptr(dep) if depth else None))
         return col, dep
+
+    def set_id_output(self, enable=True):
+        _check(_lib.tri_group_set_id_output(self._g, 1 if enable else 0))
+
+    def read_ids(self):
+        """tri_group_read_ids: uint32 [H, W], every band's rows."""
+        out = np.empty((self.height, self.width), dtype=np.uint32)
+        _check(_lib.tri_group_read_ids(self._g, _ptr(out)))
+        return out
+
+    def pick(self, x, y):
+        p = abi.TriPickResult()
+        _check(_lib.tri_group_pick(self._g, int(x), int(y), C.byref(p)))
+        return p.id, (p.depth_bits if p.has_depth else None)
 
     def frame_pointer(self):
         p, d = C.c_void_p(), C.c_int32()

@@ -775,6 +775,63 @@ typedef struct tri_text_quad {
  * font on another device. */
 int tri_set_text(tri_ctx* ctx, tri_font* font, const tri_text_quad* quads, uint32_t count);
 
+/* ---- entity ids: per-pixel draw ids, picking, selection outlines ---------------------------- */
+/* With the id output on, every tri_render also writes, per pixel of the context's rows, which draw owns the pixel:
+ * 0 for background (clear colour, skybox, text), else 1 + the index, in the array passed to tri_set_draws, of the draw
+ * whose fragment won the depth test (LESS_OR_EQUAL in primitive order: among coincident fragments the last draw wins,
+ * as in the colour target). A skipped draw (bad mesh index) keeps its index and owns no pixel. The pass is a kernel
+ * of its own (k_id_raster) between the frame's set-up and its raster kernel: it re-resolves visibility from the same
+ * bin queues with the same depth keys and shades nothing; colour and depth are bit-identical with the output on or
+ * off. tri_timing's layout and meaning are unchanged: a timed frame stamps the pass with two events of its own, its
+ * time is taken out of the stage it runs in (ms_setup, or ms_shadow with the pre-pass) and reported by
+ * tri_get_id_timing; ms_frame contains it. A frame that reports TRI_E_OVERFLOW has invalid ids like its colour;
+ * re-render it.
+ * The readers synchronise (as tri_readback, TRI_E_OVERFLOW included) and answer for the last tri_render; TRI_E_STATE
+ * with the output off or before a frame was rendered with it on. Coordinates are full-frame pixels, y down. */
+#define TRI_FORMAT_R32_UINT 98u /* VK_FORMAT_R32_UINT: tri_image.format of the id image */
+/* Allocates (enable != 0) or frees width x rows uint32. Switching it off also removes the outline. */
+int tri_set_id_output(tri_ctx* ctx, int enable);
+/* width x rows ids, tightly packed. */
+int tri_read_ids(tri_ctx* ctx, uint32_t* ids);
+/* The id image in device memory (pitch width * 4, TRI_FORMAT_R32_UINT): contents are those of the last completed
+ * tri_render, valid until the next one or until the output is switched off. */
+int tri_get_id_output(tri_ctx* ctx, tri_image* out);
+typedef struct tri_pick_result {
+    uint32_t id;         /* 0 = background, else the caller's draw index + 1       */
+    uint32_t depth_bits; /* the pixel's float32 depth bits (0 without has_depth)   */
+    uint32_t has_depth;  /* 0 under TRI_FLAG_NO_DEPTH_OUTPUT                       */
+    uint32_t reserved;
+} tri_pick_result;
+/* One pixel (copies 4 + 4 bytes, not the buffers). TRI_E_INVALID outside the context's rows. */
+int tri_pick(tri_ctx* ctx, int32_t x, int32_t y, tri_pick_result* out);
+/* The distinct draws inside the inclusive rectangle (x0, y0)-(x1, y1), clamped to the context's rows: bit d of
+ * draw_bits (word d / 32, bit d % 32) is set iff some pixel there has id d + 1; *distinct (may be NULL) is their
+ * number. word_count >= ceil(draw_count / 32) of the last rendered draw list, else TRI_E_INVALID, as for reversed
+ * corners; a rectangle that misses the rows reports none. Gathered on the device (k_id_collect). */
+int tri_pick_rect(tri_ctx* ctx, int32_t x0, int32_t y0, int32_t x1, int32_t y1, uint32_t* draw_bits, uint32_t word_count,
+                  uint32_t* distinct);
+/* The selection outline: after the frame's raster kernel and before the text pass, tri_render composites `rgba` over
+ * every outline pixel. With S(p) = 1 iff id(p) >= 1 and draw id(p) - 1 is in `draws`, pixel p is an outline pixel iff
+ * S(p) = 0 and some pixel q of the context's rows with max(|dx|, |dy|) <= width_px has S(q) = 1 (an outer outline of
+ * the visible silhouette). The composite is the text pass's blend at coverage 1: src = clamp(rgba, 0, 1),
+ * out.rgb = src.rgb * src.a + dst.rgb * (1 - src.a), out.a = src.a + dst.a * (1 - src.a), rounded to UNORM8
+ * (alpha 1 stores the colour's bytes exactly); every other pixel is untouched. */
+typedef struct tri_outline {
+    const uint32_t* draws; /* indices into the tri_set_draws array (copied)     */
+    uint32_t draw_count;   /* 0: nothing selected, nothing drawn                 */
+    float rgba[4];
+    uint32_t width_px;     /* 1..8                                               */
+    uint32_t reserved;
+} tri_outline;
+/* Stays set until the next call, like tri_set_text; NULL removes it. Needs the id output (TRI_E_STATE without it).
+ * TRI_E_INVALID: width_px outside 1..8, a non-finite colour, a draw index >= the current draw count (indices that a
+ * later, shorter draw list leaves dangling select nothing). TRI_E_UNSUPPORTED on a context that renders a row band:
+ * the outline's halo lies in other bands. */
+int tri_set_outline(tri_ctx* ctx, const tri_outline* outline);
+/* The id pass's own event timing over the frames tri_set_timing timed since it was last set: *ms_id the summed
+ * milliseconds of k_id_raster, *frames how many timed frames ran it (synchronizes, like tri_get_timing). */
+int tri_get_id_timing(tri_ctx* ctx, double* ms_id, uint64_t* frames);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
@@ -959,6 +1016,12 @@ int tri_group_transfer_info(tri_group* group, uint32_t* bytes_per_pixel, uint64_
 /* The most recent frame's transfer format (TRI_GROUP_FMT_*) and, for TRI_GROUP_FMT_DBP, its slot size in bytes
  * per 4096 pixels (0 otherwise); before any frame, the format and slot the next frame would use with packing. */
 int tri_group_transfer_format(tri_group* group, uint32_t* format, uint32_t* slot_bytes);
+/* Entity ids over a group: the id output of every band context; the whole frame's ids (width * height), copied band
+ * by band from each band's device (no RCCL: the ids never travel to the display device); one pixel from the band that
+ * holds it. Outlines are single-context only (tri_set_outline). */
+int tri_group_set_id_output(tri_group* group, int enable);
+int tri_group_read_ids(tri_group* group, uint32_t* ids);
+int tri_group_pick(tri_group* group, int32_t x, int32_t y, tri_pick_result* out);
 
 #ifdef __cplusplus
 } /* extern "C" */
@@ -972,6 +1035,8 @@ static_assert(sizeof(tri_shadow_config) == 80, "tri_shadow_config layout");
 static_assert(sizeof(tri_group_config) == 32, "tri_group_config layout");
 static_assert(sizeof(tri_image) == 32, "tri_image layout");
 static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
+static_assert(sizeof(tri_pick_result) == 16, "tri_pick_result layout");
+static_assert(sizeof(tri_outline) == 40, "tri_outline layout");
 static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
 static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
 static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
