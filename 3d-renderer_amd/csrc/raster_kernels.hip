@@ -1039,7 +1039,7 @@ static const void* raster_kernel(const TriFrameParams& fp) {
                               : shadow_raster_kernel<6>(exact);
 }
 
-void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass) {
+void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass, TriMotionPass motion) {
     plan.n = 0;
     auto add = [&](const void* f, dim3 g, dim3 t, int stage) { plan.k[plan.n++] = TriKernelLaunch{f, g, t, stage}; };
     auto F = [](auto kernel) { return reinterpret_cast<const void*>(kernel); };
@@ -1065,6 +1065,10 @@ void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass) 
     // queues: its ids are cleared by the caller)
     if (id_pass && fp.nchunks > 0) add(tri_id_raster_kernel(fp), dim3(fp.nbins), t, kStageId);
     add(raster_kernel(fp), dim3(fp.nbins), t, kStageRaster);
+    if (motion != kMotionOff) {  // reads the depth the raster kernel wrote
+        const bool vec4 = motion == kMotionVec4;
+        add(tri_motion_kernel(vec4), tri_motion_grid((uint32_t)fp.W * (uint32_t)(fp.y1 - fp.y0), vec4), t, kStageMotion);
+    }
 }
 
 #ifdef TRI_DIAG_FRONT
@@ -1084,13 +1088,14 @@ void tri_diag_front_plan(TriFramePlan& plan) {
 #endif
 
 hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, TriLaunchArgs* d_args,
-                        hipStream_t stream, hipEvent_t* ev, const TriIdArgs* id, hipEvent_t* id_ev) {
+                        hipStream_t stream, hipEvent_t* ev, const TriIdArgs* id, hipEvent_t* id_ev,
+                        const TriMotionArgs* motion, hipEvent_t* motion_ev) {
     hipError_t e = hipSuccess;
     bool setup_stamped = false;
     if (ev && (plan.n == 0 || plan.k[0].stage != kStageVertex)) (void)hipEventRecord(ev[kStageVertex], stream);
     for (uint32_t i = 0; i < plan.n; ++i) {
         const TriKernelLaunch& k = plan.k[i];
-        if (ev && k.stage != kStageId) {
+        if (ev && k.stage >= 0) {
             // stamps in the order the stages run; a frame without set-up still stamps it (zero length)
             if ((k.stage == kStageRaster || k.stage == kStageShadow) && !setup_stamped) {
                 (void)hipEventRecord(ev[kStageSetup], stream);
@@ -1104,11 +1109,15 @@ hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, Tri
         void* idp[] = {&d_args, const_cast<TriIdArgs*>(id)};  // the id pass: the published arguments, then its own
         if (k.stage == kStageId && !id) return hipErrorInvalidValue;
         if (k.stage == kStageId && id_ev) (void)hipEventRecord(id_ev[0], stream);
+        void* mop[] = {const_cast<TriMotionArgs*>(motion)};  // the motion pass: its own arguments alone
+        if (k.stage == kStageMotion && !motion) return hipErrorInvalidValue;
+        if (k.stage == kStageMotion && motion_ev) (void)hipEventRecord(motion_ev[0], stream);
         // the frame's first kernel (k_vertex's stage) takes the arguments by value and publishes them
-        e = hipLaunchKernel(k.func, k.grid, k.block, k.stage == kStageVertex ? first : (k.stage == kStageId ? idp : later), 0,
-                            stream);
+        void** kargs = k.stage == kStageVertex ? first : k.stage == kStageId ? idp : k.stage == kStageMotion ? mop : later;
+        e = hipLaunchKernel(k.func, k.grid, k.block, kargs, 0, stream);
         if (e != hipSuccess) return e;
         if (k.stage == kStageId && id_ev) (void)hipEventRecord(id_ev[1], stream);
+        if (k.stage == kStageMotion && motion_ev) (void)hipEventRecord(motion_ev[1], stream);
     }
     if (ev) (void)hipEventRecord(ev[kStageCount], stream);
     return hipGetLastError();

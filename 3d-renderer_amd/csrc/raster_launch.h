@@ -92,7 +92,7 @@ struct TriKernelLaunch {
 };
 struct TriFramePlan {
     uint32_t n = 0;
-    TriKernelLaunch k[5];
+    TriKernelLaunch k[6];
 };
 // The id pass's own arguments (id_pass.hip), by value behind the frame's published arguments: the frame's
 // TriLaunchArgs stay as they are, so no other kernel of the frame sees the pass.
@@ -102,7 +102,27 @@ struct TriIdArgs {
 constexpr int kStageId = -1;  // the id pass's launch: none of tri_timing's stamps (its layout is fixed); two of its own
 // id_pass: with the context's id output on, k_id_raster between the set-up (and the shadow map's raster) and the
 // frame's raster kernel, which re-zeroes the bin counts the pass reads; off, the plan is launch for launch the same.
-void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass = false);
+// The motion pass's own arguments (motion_pass.hip), by value and alone: k_motion reads nothing of the frame's
+// TriLaunchArgs.
+struct TriMotionArgs {
+    TRI_G const uint32_t* ids;   // W x rows draw ids (the id pass's image)
+    TRI_G const float* depth;    // W x rows, the frame's depth target
+    TRI_G float* motion;         // W x rows x 2
+    TRI_G const float* table;    // (ndraws + 1) x 16: row-major R_k (motion_math.h)
+    uint32_t W, npix;            // the frame's width; W x rows pixels
+    uint32_t y0;                 // the context's first row in the frame
+    uint32_t ndraws;
+    float sx, sy, hw, hh;        // 2 / W, 2 / H, W / 2, H / 2 (float32, from the host)
+};
+constexpr int kStageMotion = -2;  // the motion pass's launch: like kStageId, two stamps of its own
+enum TriMotionPass { kMotionOff = 0, kMotionVec4, kMotionScalar };
+// motion: with the context's motion output on, k_motion behind the frame's raster kernel, whose depth it reads; four
+// pixels per lane (kMotionVec4) when every image starts on a 16-B boundary, else one. Off, the plan is launch for
+// launch the same.
+void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass = false, TriMotionPass motion = kMotionOff);
+// k_motion and its grid over W x rows pixels (motion_pass.hip)
+const void* tri_motion_kernel(bool vec4);
+dim3 tri_motion_grid(uint32_t npix, bool vec4);
 // k_id_raster at the frame's bin size (id_pass.hip)
 const void* tri_id_raster_kernel(const TriFrameParams& fp);
 #ifdef TRI_DIAG_FRONT
@@ -126,10 +146,11 @@ enum TriStage { kStageVertex = 0, kStageShadow, kStageSetup, kStageRaster, kStag
 // shadow pre-pass (k_shadow_raster after k_setup<shadow>); `events` (may be null) gets kStageCount + 1 stamps
 // (the kStageShadow stamp only when the pre-pass runs).
 // `id`: the id pass's arguments when the plan holds its launch (kStageId); `id_events` (may be null): two stamps of the
-// pass's own, in front of and behind that launch.
+// pass's own, in front of and behind that launch. `motion`, `motion_events`: the same for the motion pass (kStageMotion).
 hipError_t tri_run_plan(const TriFramePlan& plan, const TriLaunchArgs& args, TriLaunchArgs* d_args,
                         hipStream_t stream, hipEvent_t* events, const TriIdArgs* id = nullptr,
-                        hipEvent_t* id_events = nullptr);
+                        hipEvent_t* id_events = nullptr, const TriMotionArgs* motion = nullptr,
+                        hipEvent_t* motion_events = nullptr);
 
 // The id pass's other kernels (id_pass.hip; include/tri_raster.h "entity ids"). ids: W x rows.
 // k_id_collect: ORs bit id - 1 of `bits` (nwords words, cleared by the caller) for every id >= 1 inside columns

@@ -1,7 +1,7 @@
 // tri_ctx.h — the context, geometry and font objects behind the C-ABI handles, and the owning holders their members
 // are made of. Internal to the units that implement the entry points over a context (tri_raster_capi.hip: lifecycle,
 // frame and readback; tri_geometry.hip: geometry; tri_resources.hip: every other upload; tri_ids.hip: the entity-id
-// entry points); the other units keep to the
+// entry points; tri_motion.hip: the motion-vector entry points); the other units keep to the
 // accessors of capi_util.h.
 //
 // Ownership: a DevBuf, PinBuf, Event or Staged member frees what it holds when its object is deleted (with the
@@ -121,6 +121,8 @@ struct TimingSet {
     bool shadow = false;  // the frame ran the shadow pre-pass (ev[kStageShadow] was recorded)
     Event id[2];          // round k_id_raster, made at the first timed frame with the id pass
     bool has_id = false;  // ... and recorded on this frame
+    Event motion[2];          // round k_motion, likewise
+    bool has_motion = false;
 };
 
 // Geometry (UploadMeshFromCache, Renderer.cpp:1965-2116): one concatenated vertex buffer, one index
@@ -254,6 +256,16 @@ struct tri_ctx {
     DevBuf<uint32_t> d_pick_bits;
     PinBuf<uint32_t> h_pick;
 
+    // motion vectors (tri_set_motion_output, tri_set_motion_history; tri_motion.hip): the motion image of the context's
+    // rows, whether the last tri_render wrote it, the caller's history (copied; its prev_models points into
+    // motion_prev_models or is null) and the reprojection table's staging
+    bool motion_on = false, motion_rendered = false, motion_has_history = false;
+    DevBuf<float> d_motion;
+    tri_motion_history motion_history{};
+    std::vector<float> motion_prev_models;
+    std::vector<float> motion_table;
+    Staged motion_stage;
+
     DevBuf<uint32_t> d_color_own;
     DevBuf<float> d_depth_own;
     DevBuf<uint32_t> d_present;  // tri_blit_linear's owned target
@@ -277,11 +289,18 @@ struct tri_ctx {
     tri_timing acc{};
     double acc_id_ms = 0.0;     // tri_get_id_timing: the id pass's own stamps over the timed frames that ran it
     uint64_t acc_id_frames = 0;
+    double acc_motion_ms = 0.0;  // tri_get_motion_timing, likewise
+    uint64_t acc_motion_frames = 0;
 };
 
 // tri_render's outline pass (tri_ids.hip): the per-draw flags to the device when they changed, then k_id_outline on
 // the context's stream.
 int tri_ids_outline_pass(tri_ctx* c);
+// tri_render's motion pass (tri_motion.hip): checks the stored history against the frame's draws, builds and stages the
+// reprojection table on the context's stream and fills k_motion's arguments; *pass says which kernel the plan takes.
+int tri_motion_prepare(tri_ctx* c, TriMotionArgs* args, TriMotionPass* pass);
+// Switch the motion output off and free its image (tri_set_id_output(0) takes it along); the stream is idle.
+int tri_motion_release(tri_ctx* c);
 
 inline int make_current(tri_ctx* c) {
     TRI_HIP_TRY(hipSetDevice(c->device));

@@ -61,6 +61,7 @@ int tri_set_id_output(tri_ctx* c, int enable) {
     c->id_on = false;
     c->outline_on = false;
     c->outline_draws.clear();
+    if ((rc = tri_motion_release(c))) return rc;  // the motion pass reads the ids
     return c->d_ids.release();
 }
 

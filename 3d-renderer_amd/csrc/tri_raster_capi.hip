@@ -153,6 +153,13 @@ int collect_timing(tri_ctx* c) {
             c->acc_id_ms += id_ms;
             c->acc_id_frames += 1;
         }
+        if (t.has_motion) {  // k_motion runs behind the raster kernel, inside the raster stage's stamps: likewise
+            float mo_ms = 0.0f;
+            TRI_HIP_TRY(hipEventElapsedTime(&mo_ms, t.motion[0].e, t.motion[1].e));
+            ms[kStageRaster] -= mo_ms;
+            c->acc_motion_ms += mo_ms;
+            c->acc_motion_frames += 1;
+        }
         c->acc.ms_vertex += ms[kStageVertex];
         c->acc.ms_setup += ms[kStageSetup];
         c->acc.ms_shadow += ms[kStageShadow];
@@ -520,7 +527,20 @@ int tri_render(tri_ctx* c) {
     }
     ts.shadow = fp.shadow_on != 0;
     TriFramePlan plan;
-    tri_plan_frame(fp, plan, c->id_on);
+    // the motion pass (tri_set_motion_output): its table rides the stream ahead of the frame's kernels
+    TriMotionArgs moa{};
+    TriMotionPass mo_pass = kMotionOff;
+    if (c->motion_on && (rc = tri_motion_prepare(c, &moa, &mo_pass))) return rc;
+    tri_plan_frame(fp, plan, c->id_on, mo_pass);
+    hipEvent_t mo_stamps[2], *mo_ev = nullptr;
+    ts.has_motion = timed && mo_pass != kMotionOff;
+    if (ts.has_motion) {
+        for (int i = 0; i < 2; ++i) {
+            if ((rc = ts.motion[i].ensure(hipEventDefault))) return rc;
+            mo_stamps[i] = ts.motion[i].e;
+        }
+        mo_ev = mo_stamps;
+    }
     hipEvent_t id_stamps[2], *id_ev = nullptr;
     ts.has_id = timed && c->id_on && fp.nchunks > 0;  // (the plan holds the id pass)
     if (ts.has_id) {
@@ -556,9 +576,11 @@ int tri_render(tri_ctx* c) {
     const TriIdArgs ida{c->d_ids.p};
     if (c->id_on && fp.nchunks == 0)
         TRI_HIP_TRY(hipMemsetAsync(c->d_ids, 0, (size_t)c->W * (size_t)(c->y1 - c->y0) * 4, c->stream));
-    TRI_HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev, c->id_on ? &ida : nullptr, id_ev));
+    TRI_HIP_TRY(tri_run_plan(plan, ha, c->d_args, c->stream, ev, c->id_on ? &ida : nullptr, id_ev,
+                             mo_pass != kMotionOff ? &moa : nullptr, mo_ev));
     c->launched = true;
     c->ids_rendered = c->id_on;
+    c->motion_rendered = c->motion_on;
     // the selection outline (tri_set_outline): over the frame, under the text
     if (c->id_on && c->outline_on && (rc = tri_ids_outline_pass(c))) return rc;
     // the text pass (TextRenderer::RecordViewport, after the mesh / sky pass): only when quads are set. A
@@ -663,6 +685,8 @@ int tri_set_timing(tri_ctx* c, int enable) {
     c->acc = tri_timing{};
     c->acc_id_ms = 0.0;
     c->acc_id_frames = 0;
+    c->acc_motion_ms = 0.0;
+    c->acc_motion_frames = 0;
     return TRI_OK;
 }
 
@@ -680,6 +704,15 @@ int tri_get_id_timing(tri_ctx* c, double* ms_id, uint64_t* frames) {
     if (rc) return rc;
     *ms_id = c->acc_id_ms;
     *frames = c->acc_id_frames;
+    return TRI_OK;
+}
+
+int tri_get_motion_timing(tri_ctx* c, double* ms_motion, uint64_t* frames) {
+    if (!c || !ms_motion || !frames) return fail(TRI_E_INVALID, "tri_get_motion_timing: null argument");
+    int rc = collect_timing(c);
+    if (rc) return rc;
+    *ms_motion = c->acc_motion_ms;
+    *frames = c->acc_motion_frames;
     return TRI_OK;
 }
 

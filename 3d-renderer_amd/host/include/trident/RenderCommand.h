@@ -57,6 +57,10 @@ public:
     static void SetSelectionOutline(bool enabled, const glm::vec4& colour = glm::vec4(1.0f, 0.6f, 0.0f, 1.0f), uint32_t widthPx = 2) {
         GetRenderer().SetSelectionOutline(enabled, colour, widthPx);
     }
+    // Motion vectors: the per-pixel screen-space motion image of a viewport
+    static void SetMotionVectorOutputEnabled(uint32_t viewportId, bool enabled) { GetRenderer().SetMotionVectorOutputEnabled(viewportId, enabled); }
+    static bool ReadViewportMotionVectors(uint32_t viewportId, std::vector<float>& out) { return GetRenderer().ReadViewportMotionVectors(viewportId, out); }
+    static void* GetViewportMotionTexture(uint32_t viewportId) { return GetRenderer().GetViewportMotionTexture(viewportId); }
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }

@@ -6,6 +6,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdint>
 #include <deque>
@@ -280,6 +281,25 @@ public:
     void SetSelectionOutline(bool enabled, const glm::vec4& colour = glm::vec4(1.0f, 0.6f, 0.0f, 1.0f), uint32_t widthPx = 2);
     bool IsSelectionOutlineEnabled() const { return m_SelectionOutline; }
 
+    // Motion vectors (tri_set_motion_output and its readers): per pixel of a viewport, where the surface it shows lay
+    // one frame ago, minus the pixel, in pixels (x right, y down) — for frame interpolation and extrapolation, temporal
+    // reprojection and training data. From the viewport's next DrawFrame on its frames carry motion; the request also
+    // turns the viewport's id output on (the pass reads the ids), as the outline does. History is kept per VIEWPORT,
+    // not per ring target: the view and projection of the viewport's last rendered frame and an entity -> model map
+    // of that frame's draws, so frame k's history is frame k - 1's whatever SetFramesInFlight is. A viewport's first
+    // frame with the output on, and the first after a resize, have no history: their motion is all zero. An entity
+    // without an entry (new, just made visible, a sprite's first frame) takes its current model as the previous one:
+    // camera motion only. Skinned draws get the rigid motion of their model matrix; per-bone motion is not computed.
+    // Refused with a log line while SetDeviceCount > 1, which also turns the output off.
+    void SetMotionVectorOutputEnabled(uint32_t viewportId, bool enabled);
+    bool IsMotionVectorOutputEnabled(uint32_t viewportId) const;
+    // width * height * 2 floats (x then y, rows top to bottom) of the viewport's latest frame (fences); false for a
+    // viewport that does not exist or whose latest frame carries no motion.
+    bool ReadViewportMotionVectors(uint32_t viewportId, std::vector<float>& out);
+    // An opaque pointer to the tri_image of the motion image (R32G32_SFLOAT, pitch width * 8), valid like
+    // GetViewportTexture's; null where ReadViewportMotionVectors returns false.
+    void* GetViewportMotionTexture(uint32_t viewportId);
+
     // Frame readback (ResolvePendingReadback, Renderer.cpp:1299-1389): RGBA8 rows of the viewport
     // (BGRA reordered to RGBA), optionally the D32 depth.
     bool ReadViewportPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr);
@@ -360,6 +380,9 @@ private:
         glm::vec4 m_OutlineColour{0.0f};
         uint32_t m_OutlineWidth = 0;
         std::vector<ECS::Entity> m_DrawEntities;
+        // motion vectors: the context's motion output is on; its image
+        bool m_MotionOutput = false;
+        tri_image m_MotionImage{};
     };
 
     void CreateSkyboxCubemap();
@@ -377,6 +400,11 @@ private:
     bool SetTargetIds(ViewportContext& target, uint32_t viewportId, const std::vector<tri_draw>& draws,
                       const std::vector<ECS::Entity>& entities);
     const ViewportContext* IdTarget(uint32_t viewportId);  // fenced; null unless the latest frame carries ids
+    // before the target's tri_render, after SetTargetIds: the motion output this frame wants on it, the viewport's
+    // history as the context's, and this frame's camera and models as the history of the viewport's next frame
+    bool SetTargetMotion(ViewportContext& target, uint32_t viewportId, const tri_global_ubo& ubo,
+                         const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities);
+    const ViewportContext* MotionTarget(uint32_t viewportId);  // fenced; null unless the latest frame carries motion
     const Camera* GetActiveCamera(const ViewportContext& context) const;
     bool PrepareViewport(ViewportContext& context);
     // One viewport pass: pre-pass / palette / UBO / draws, then tri_render (asynchronous); false on error.
@@ -467,6 +495,14 @@ private:
     bool m_SelectionOutline = false;
     glm::vec4 m_OutlineColour{1.0f, 0.6f, 0.0f, 1.0f};
     uint32_t m_OutlineWidth = 2;
+    struct MotionHistory {  // a viewport's last rendered frame
+        bool m_Valid = false;
+        uint32_t m_Width = 0, m_Height = 0;
+        float m_View[16] = {}, m_Projection[16] = {};
+        std::unordered_map<ECS::Entity, std::array<float, 16>> m_Models;
+    };
+    std::map<uint32_t, bool> m_MotionViewports;  // SetMotionVectorOutputEnabled, by viewport id
+    std::map<uint32_t, MotionHistory> m_MotionHistory;
     std::map<uint32_t, ViewportContext> m_Viewports;
     ViewportInfo m_LastViewport{};
     uint32_t m_ActiveViewportId = 0;

@@ -261,6 +261,16 @@ int trident_app_read_entity_ids(trident_app* app, uint32_t viewport_id, uint32_t
 int trident_app_set_selected_entity(trident_app* app, uint32_t entity);
 int trident_app_set_selection_outline(trident_app* app, int enabled, const float rgba[4], uint32_t width_px);
 
+/* ---- motion vectors ---- */
+/* Renderer::SetMotionVectorOutputEnabled: from the viewport's next draw_frame on; TRI_E_STATE where the renderer
+ * refuses (SetDeviceCount > 1). */
+int trident_app_set_motion_vector_output(trident_app* app, uint32_t viewport_id, int enabled);
+/* Renderer::ReadViewportMotionVectors: width * height * 2 floats; TRI_E_STATE where it returns false, TRI_E_INVALID
+ * when capacity (in floats) is short. */
+int trident_app_read_motion_vectors(trident_app* app, uint32_t viewport_id, float* xy, uint64_t capacity);
+/* Renderer::GetViewportMotionTexture: copies the motion image's handle (TRI_E_STATE where it returns null). */
+int trident_app_motion_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
+
 /* ---- text overlay ---- */
 /* Renderer::SubmitText: `bytes` bytes of UTF-8 (no terminator needed) at `position` (viewport pixels) in `color`
  * (RGBA) for the viewport's next draw_frame. */

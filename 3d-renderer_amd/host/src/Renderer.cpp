@@ -445,6 +445,13 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         LogError("SetDeviceCount", "multi-device viewports draw no selection outline: it was turned off");
         m_SelectionOutline = false;
     }
+    if (devs.size() > 1) {
+        bool any = false;
+        for (auto& it : m_MotionViewports) any |= it.second;
+        if (any) LogError("SetDeviceCount", "multi-device viewports write no motion vectors: the output was turned off");
+        m_MotionViewports.clear();
+        m_MotionHistory.clear();
+    }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
     return true;
@@ -1281,6 +1288,7 @@ bool Renderer::PrepareViewport(ViewportContext& vc) {
         vc.m_HasPosedSuffix = false;
         vc.m_IdOutput = vc.m_OutlineSet = false;  // ... and without the id output and the outline (SetTargetIds)
         vc.m_DrawEntities.clear();
+        vc.m_MotionOutput = false;  // ... and without the motion output (SetTargetMotion)
     }
     const Target t{vc.m_Ctx, vc.m_Group};
     if (vc.m_GeometryGeneration != m_GeometryGeneration && multi) {
@@ -1461,6 +1469,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         UpdateUniformBuffer(GetActiveCamera(vc), ubo);
         if (!SetTargetText(vc, id)) LogError("DrawFrame", "the text overlay of this frame is missing");
         if (!SetTargetIds(vc, id, draws, drawEntities)) LogError("DrawFrame", "the entity ids of this frame are missing");
+        if (!SetTargetMotion(vc, id, ubo, draws, drawEntities)) LogError("DrawFrame", "the motion vectors of this frame are missing");
         if (!SubmitTarget(vc, TargetUniforms(vc, ubo), draws, shadow, shadowOn)) return;
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
@@ -2141,7 +2150,8 @@ bool Renderer::SetTargetIds(ViewportContext& vc, uint32_t viewportId, const std:
         for (uint32_t d = 0; d < entities.size(); ++d)
             if (entities[d] == m_SelectedEntity) selected.push_back(d);
     auto want = m_IdOutputViewports.find(viewportId);
-    const bool ids = (want != m_IdOutputViewports.end() && want->second) || !selected.empty();
+    const bool ids = (want != m_IdOutputViewports.end() && want->second) || !selected.empty() ||
+                     (vc.m_Ctx && IsMotionVectorOutputEnabled(viewportId));  // (the motion pass reads the ids)
     bool ok = true;
     if (ids != vc.m_IdOutput) {
         if (t.IdOutput(ids) != TRI_OK) {
@@ -2245,6 +2255,89 @@ bool Renderer::ReadViewportEntityIds(uint32_t viewportId, std::vector<uint32_t>&
     }
     for (uint32_t& v : out) v = (v == 0 || v > vc->m_DrawEntities.size()) ? background : vc->m_DrawEntities[v - 1];
     return true;
+}
+
+// ---- motion vectors -----------------------------------------------------------------------------------------------
+void Renderer::SetMotionVectorOutputEnabled(uint32_t viewportId, bool enabled) {
+    if (enabled && m_Devices.size() > 1) {
+        LogError("motion vectors", "multi-device viewports (SetDeviceCount > 1) write no motion vectors");
+        return;
+    }
+    m_MotionViewports[viewportId] = enabled;
+}
+
+bool Renderer::IsMotionVectorOutputEnabled(uint32_t viewportId) const {
+    auto it = m_MotionViewports.find(viewportId);
+    return it != m_MotionViewports.end() && it->second;
+}
+
+// The output is context state that stays set, so only changes are sent (ring targets are separate contexts: each is
+// brought up to date when its turn comes). The history is the viewport's, whichever target rendered its last frame.
+bool Renderer::SetTargetMotion(ViewportContext& vc, uint32_t viewportId, const tri_global_ubo& ubo,
+                               const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities) {
+    const bool want = vc.m_Ctx && vc.m_IdOutput && IsMotionVectorOutputEnabled(viewportId);
+    if (vc.m_Ctx && want != vc.m_MotionOutput) {
+        if (tri_set_motion_output(vc.m_Ctx, want ? 1 : 0) != TRI_OK || (want && tri_get_motion_output(vc.m_Ctx, &vc.m_MotionImage) != TRI_OK)) {
+            LogError("motion vectors", tri_last_error());
+            m_MotionHistory.erase(viewportId);
+            return false;
+        }
+        vc.m_MotionOutput = want;
+    }
+    if (!want) {
+        m_MotionHistory.erase(viewportId);  // the first frame after the output is switched on has no history
+        return !IsMotionVectorOutputEnabled(viewportId);
+    }
+    MotionHistory& h = m_MotionHistory[viewportId];
+    const uint32_t n = (uint32_t)std::min(draws.size(), entities.size());
+    int rc;
+    if (h.m_Valid && h.m_Width == vc.m_Width && h.m_Height == vc.m_Height) {
+        tri_motion_history mh{};
+        std::memcpy(mh.prev_view, h.m_View, sizeof mh.prev_view);
+        std::memcpy(mh.prev_projection, h.m_Projection, sizeof mh.prev_projection);
+        std::vector<float> prev((size_t)n * 16);
+        for (uint32_t d = 0; d < n; ++d) {  // an entity the last frame did not draw keeps its current model
+            auto it = h.m_Models.find(entities[d]);
+            std::memcpy(&prev[(size_t)d * 16], it != h.m_Models.end() ? it->second.data() : draws[d].pc.model, 64);
+        }
+        mh.prev_models = n ? prev.data() : nullptr;
+        mh.draw_count = n;
+        rc = tri_set_motion_history(vc.m_Ctx, &mh);
+    } else {
+        rc = tri_set_motion_history(vc.m_Ctx, nullptr);
+    }
+    if (rc != TRI_OK) LogError("motion vectors", tri_last_error());
+    h.m_Valid = true;
+    h.m_Width = vc.m_Width;
+    h.m_Height = vc.m_Height;
+    std::memcpy(h.m_View, ubo.view, sizeof h.m_View);
+    std::memcpy(h.m_Projection, ubo.projection, sizeof h.m_Projection);
+    h.m_Models.clear();
+    for (uint32_t d = 0; d < n; ++d) std::memcpy(h.m_Models[entities[d]].data(), draws[d].pc.model, 64);
+    return rc == TRI_OK;
+}
+
+const Renderer::ViewportContext* Renderer::MotionTarget(uint32_t viewportId) {
+    FinishFrame();
+    const ViewportContext* vc = LatestTarget(viewportId);
+    if (!vc || !vc->m_Ctx || !vc->m_MotionOutput) return nullptr;
+    return vc;
+}
+
+bool Renderer::ReadViewportMotionVectors(uint32_t viewportId, std::vector<float>& out) {
+    const ViewportContext* vc = MotionTarget(viewportId);
+    if (!vc) return false;
+    out.resize((size_t)vc->m_Width * vc->m_Height * 2);
+    if (tri_read_motion(vc->m_Ctx, out.data()) != TRI_OK) {
+        LogError("motion vectors", tri_last_error());
+        return false;
+    }
+    return true;
+}
+
+void* Renderer::GetViewportMotionTexture(uint32_t viewportId) {
+    const ViewportContext* vc = MotionTarget(viewportId);
+    return vc ? const_cast<tri_image*>(&vc->m_MotionImage) : nullptr;
 }
 
 void* Renderer::GetViewportTexture(uint32_t viewportId) const {

@@ -691,6 +691,34 @@ int trident_app_set_selection_outline(trident_app* app, int enabled, const float
     });
 }
 
+int trident_app_set_motion_vector_output(trident_app* app, uint32_t viewport_id, int enabled) {
+    return Guard(app, [&] {
+        app->renderer.SetMotionVectorOutputEnabled(viewport_id, enabled != 0);
+        return app->renderer.IsMotionVectorOutputEnabled(viewport_id) == (enabled != 0) ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_app_read_motion_vectors(trident_app* app, uint32_t viewport_id, float* xy, uint64_t capacity) {
+    return Guard(app, [&] {
+        if (!xy) return TRI_E_INVALID;
+        std::vector<float> m;
+        if (!app->renderer.ReadViewportMotionVectors(viewport_id, m)) return TRI_E_STATE;
+        if (m.size() > capacity) return TRI_E_INVALID;
+        std::memcpy(xy, m.data(), m.size() * sizeof(float));
+        return TRI_OK;
+    });
+}
+
+int trident_app_motion_texture(trident_app* app, uint32_t viewport_id, tri_image* out) {
+    return Guard(app, [&] {
+        if (!out) return TRI_E_INVALID;
+        const void* h = app->renderer.GetViewportMotionTexture(viewport_id);
+        if (!h) return TRI_E_STATE;
+        *out = *static_cast<const tri_image*>(h);
+        return TRI_OK;
+    });
+}
+
 struct trident_font {
     TextRenderer text;
 };

@@ -220,6 +220,18 @@ class TriOutline(C.Structure):
 assert C.sizeof(TriPickResult) == 16 and C.sizeof(TriOutline) == 40
 
 
+# motion vectors (include/tri_raster.h): the motion image's format, the previous frame's camera and models
+TRI_FORMAT_R32G32_SFLOAT = 103
+
+
+class TriMotionHistory(C.Structure):
+    _fields_ = [("prev_view", C.c_float * 16), ("prev_projection", C.c_float * 16), ("prev_models", C.POINTER(C.c_float)),
+                ("draw_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(TriMotionHistory) == 144
+
+
 class TriGroupConfig(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -472,6 +484,13 @@ CABI_FUNCTIONS = [
     ("tri_group_set_id_output", C.c_int, [C.c_void_p, C.c_int]),
     ("tri_group_read_ids", C.c_int, [C.c_void_p, C.c_void_p]),
     ("tri_group_pick", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(TriPickResult)]),
+    ("tri_set_motion_output", C.c_int, [C.c_void_p, C.c_int]),
+    ("tri_set_motion_history", C.c_int, [C.c_void_p, C.POINTER(TriMotionHistory)]),
+    ("tri_read_motion", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tri_get_motion_output", C.c_int, [C.c_void_p, C.POINTER(TriImage)]),
+    ("tri_get_motion_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("tri_motion_matrices", C.c_int, [C.POINTER(TriGlobalUbo), C.POINTER(TriDraw), C.c_uint32, C.POINTER(TriMotionHistory),
+                                      C.c_void_p]),
 ]
 
 

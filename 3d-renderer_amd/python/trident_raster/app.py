@@ -126,6 +126,9 @@ _APP_FUNCTIONS = [
     ("trident_app_read_entity_ids", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32]),
     ("trident_app_set_selected_entity", C.c_int, [C.c_void_p, C.c_uint32]),
     ("trident_app_set_selection_outline", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float * 4), C.c_uint32]),
+    ("trident_app_set_motion_vector_output", C.c_int, [C.c_void_p, C.c_uint32, C.c_int]),
+    ("trident_app_read_motion_vectors", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
+    ("trident_app_motion_texture", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage)]),
     ("trident_app_submit_text", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4),
                                           C.c_char_p, C.c_uint32]),
     ("trident_app_set_font", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
@@ -456,6 +459,32 @@ class TridentApp:
         if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
             _check(rc, "set_selection_outline")
         return rc == abi.TRI_OK
+
+    # ---- motion vectors ----
+    def set_motion_vector_output(self, viewport_id, enabled=True):
+        """Renderer::SetMotionVectorOutputEnabled; False where the renderer refuses it (SetDeviceCount > 1)."""
+        rc = self._lib.trident_app_set_motion_vector_output(self._h, viewport_id, 1 if enabled else 0)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_motion_vector_output")
+        return rc == abi.TRI_OK
+
+    def read_motion_vectors(self, viewport_id, width, height):
+        """Renderer::ReadViewportMotionVectors: float32 [height, width, 2], or None where it returns false."""
+        out = np.zeros((height, width, 2), np.float32)
+        rc = self._lib.trident_app_read_motion_vectors(self._h, viewport_id, out.ctypes.data, out.size)
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "read_motion_vectors")
+        return out
+
+    def motion_texture(self, viewport_id):
+        """Renderer::GetViewportMotionTexture: the motion image's abi.TriImage handle, or None."""
+        img = abi.TriImage()
+        rc = self._lib.trident_app_motion_texture(self._h, viewport_id, C.byref(img))
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "motion_texture")
+        return img
 
     def set_font(self, path, pixel_height=32.0):
         """Renderer::SetTextFont; returns its bool."""

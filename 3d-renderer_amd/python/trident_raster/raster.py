@@ -322,6 +322,39 @@ class TriRaster:
         _check(_lib.tri_get_id_timing(self._ctx, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    # ---- motion vectors ----
+    def set_motion_output(self, enable=True):
+        """tri_set_motion_output: every following render also writes the per-pixel motion (needs the id output)."""
+        _check(_lib.tri_set_motion_output(self._ctx, 1 if enable else 0))
+
+    def set_motion_history(self, prev_view=None, prev_projection=None, prev_models=None, draw_count=None):
+        """tri_set_motion_history: the previous frame's view and projection (16 floats each, column-major) and, per
+        draw of the current list, its previous model ([n, 16] column-major; None: the current one). No view: no
+        history. draw_count overrides the models' count (for the error cases)."""
+        if prev_view is None:
+            _check(_lib.tri_set_motion_history(self._ctx, None))
+            return
+        h, _keep = _motion_history(prev_view, prev_projection, prev_models, draw_count)
+        _check(_lib.tri_set_motion_history(self._ctx, C.byref(h)))
+
+    def read_motion(self):
+        """tri_read_motion: float32 [rows, W, 2], (x, y) in pixels: where the pixel's surface lay one frame ago,
+        minus the pixel."""
+        out = np.empty((self.rows, self.width, 2), dtype=np.float32)
+        _check(_lib.tri_read_motion(self._ctx, _ptr(out)))
+        return out
+
+    def motion_image(self):
+        img = abi.TriImage()
+        _check(_lib.tri_get_motion_output(self._ctx, C.byref(img)))
+        return img
+
+    def motion_timing(self):
+        """tri_get_motion_timing: (summed ms of k_motion, timed frames that ran it)."""
+        ms, n = C.c_double(), C.c_uint64()
+        _check(_lib.tri_get_motion_timing(self._ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def set_timing(self, enable, period=1):
         """Per-stage HIP-event timing of every `period`-th frame (enable=False: off)."""
         _check(_lib.tri_set_timing(self._ctx, int(period) if enable else 0))
@@ -335,6 +368,35 @@ class TriRaster:
         s = abi.TriFrameStats()
         _check(_lib.tri_get_frame_stats(self._ctx, C.byref(s)))
         return {k: getattr(s, k) for k, _ in abi.TriFrameStats._fields_}
+
+
+def _motion_history(prev_view, prev_projection, prev_models, draw_count=None):
+    """(abi.TriMotionHistory, the array it points into)."""
+    h = abi.TriMotionHistory()
+    h.prev_view = (C.c_float * 16)(*np.asarray(prev_view, np.float32).reshape(16).tolist())
+    h.prev_projection = (C.c_float * 16)(*np.asarray(prev_projection, np.float32).reshape(16).tolist())
+    m = None
+    if prev_models is not None:
+        m = np.ascontiguousarray(prev_models, dtype=np.float32).reshape(-1, 16)
+        h.prev_models = m.ctypes.data_as(C.POINTER(C.c_float))
+        h.draw_count = m.shape[0]
+    if draw_count is not None:
+        h.draw_count = int(draw_count)
+    return h, m
+
+
+def motion_matrices(ubo, draws, history=None):
+    """tri_motion_matrices (host-only): the reprojection table of a frame, float32 [len(draws) + 1, 4, 4] with
+    [k, i, j] = R_k[i][j]; row 0 is the background's. history: None, or (prev_view, prev_projection, prev_models or
+    None[, draw_count]) as TriRaster.set_motion_history takes them."""
+    lib = load_library()
+    arr, n = abi.draws_array(draws)
+    out = np.empty((n + 1, 4, 4), dtype=np.float32)
+    h = keep = None
+    if history is not None:
+        h, keep = _motion_history(*history)
+    _check(lib.tri_motion_matrices(C.byref(ubo), arr, n, C.byref(h) if h is not None else None, _ptr(out)))
+    return out
 
 
 def _pick_rect(call, x0, y0, x1, y1, draw_count):

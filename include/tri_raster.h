@@ -832,6 +832,60 @@ int tri_set_outline(tri_ctx* ctx, const tri_outline* outline);
  * milliseconds of k_id_raster, *frames how many timed frames ran it (synchronizes, like tri_get_timing). */
 int tri_get_id_timing(tri_ctx* ctx, double* ms_id, uint64_t* frames);
 
+/* ---- motion vectors: per-pixel screen-space motion from ids and depth ------------------------ */
+/* With the motion output on (it needs the id output), every tri_render also writes two float32 per pixel of the
+ * context's rows: m(p) = prev(p) - p in pixels, where the surface point visible at pixel p lay one frame ago (x right,
+ * y down). k_motion, a streaming kernel of its own after the frame's raster kernel, reads the pixel's id and depth and
+ * one 4 x 4 reprojection matrix per draw; no other kernel of the frame changes, and colour, depth and ids are
+ * bit-identical with the output on or off. With R the matrix of the pixel's draw (row id(p) of the table
+ * tri_motion_matrices builds; row 0 for the background) and W x H the frame, in float32 and in exactly this order:
+ *     fx = (float)x + 0.5f             fy = (float)y + 0.5f            (y: the full-frame row)
+ *     xn = fx * sx - 1.0f              yn = fy * sy - 1.0f             sx = 2.0f / (float)W, sy = 2.0f / (float)H
+ *     z  = id(p) ? depth(p) : 1.0f
+ *     q_i = ((R[i][0] * xn + R[i][1] * yn) + R[i][2] * z) + R[i][3]    for i = 0, 1, 3
+ *     q_3 > 0.0f:  iw = 1.0f / q_3,  m.x = (q_0 * iw - xn) * (0.5f * W),  m.y = (q_1 * iw - yn) * (0.5f * H)
+ *     otherwise (NaN, or the point lay behind the previous camera) m = (0, 0); a pair with a non-finite component is
+ *     stored as (0, 0).
+ * No multiply-add is contracted and the divide is correctly rounded, so a float32 restatement gives the same bits.
+ * Skinned draws get the rigid motion of their model matrix. A frame that reports TRI_E_OVERFLOW has invalid motion
+ * like its colour; re-render it. tri_timing's layout and meaning are unchanged: a timed frame stamps the pass with two
+ * events of its own, its time is taken out of ms_raster and reported by tri_get_motion_timing; ms_frame contains it. */
+#define TRI_FORMAT_R32G32_SFLOAT 103u /* VK_FORMAT_R32G32_SFLOAT: tri_image.format of the motion image */
+typedef struct tri_motion_history {
+    float prev_view[16];        /* as tri_global_ubo.view / .projection, of the previous frame            */
+    float prev_projection[16];
+    const float* prev_models;   /* draw_count x 16 floats: the model each draw of the CURRENT tri_set_draws *
+                                 * array had in the previous frame; NULL: every draw keeps its current one  */
+    uint32_t draw_count;        /* with prev_models: must equal the draw count at tri_render                */
+    uint32_t reserved;
+} tri_motion_history;
+/* Allocates (enable != 0) or frees width x rows x 2 floats. TRI_E_STATE without the id output (switching that off
+ * also switches this off); TRI_E_UNSUPPORTED on a context created with TRI_FLAG_NO_DEPTH_OUTPUT. Row-band contexts
+ * are supported: the pass has no halo. */
+int tri_set_motion_output(tri_ctx* ctx, int enable);
+/* The previous frame's camera and models, copied; stays until replaced. NULL: no history, all motion zero.
+ * TRI_E_INVALID for prev_models with a draw_count of 0. tri_render reports TRI_E_STATE while the motion output is on
+ * and a stored prev_models count differs from the frame's draw count. */
+int tri_set_motion_history(tri_ctx* ctx, const tri_motion_history* history);
+/* width x rows x 2 floats, tightly packed, x then y. Synchronises and reports TRI_E_OVERFLOW like tri_read_ids;
+ * TRI_E_STATE with the output off or before a frame was rendered with it on. */
+int tri_read_motion(tri_ctx* ctx, float* xy);
+/* The motion image in device memory (pitch width * 8, TRI_FORMAT_R32G32_SFLOAT), valid like tri_get_id_output's. */
+int tri_get_motion_output(tri_ctx* ctx, tri_image* out);
+/* As tri_get_id_timing, for k_motion. */
+int tri_get_motion_timing(tri_ctx* ctx, double* ms_motion, uint64_t* frames);
+/* The reprojection table tri_render stages for k_motion, (draw_count + 1) x 16 floats: out[16 k + 4 i + j] = R_k[i][j],
+ * R_0 for the background and R_{d+1} for draws[d]. With P, V the uniform block's projection and view, M_d the first
+ * 64 bytes of the draw's push constant and primes for the history's values,
+ *     R_{d+1} = (P' V' M'_d) inverse(P V M_d),        R_0 = (P' V'_0) inverse(P V_0),
+ * V_0 being V with its translation column replaced by (0, 0, 0, 1) (the background lies at infinity; the kernel
+ * applies R_0 at z = 1). Computed in float64 and rounded once. A row is the exact identity when the current and the
+ * previous matrices are bitwise equal, when P V M_d is singular or non-finite, when the row would hold a non-finite
+ * entry, and — every row — when history is NULL. Host only: no device, no context. TRI_E_INVALID for a null ubo or
+ * out, null draws with draw_count > 0, prev_models with a count of 0 or one that differs from draw_count. */
+int tri_motion_matrices(const tri_global_ubo* ubo, const tri_draw* draws, uint32_t draw_count,
+                        const tri_motion_history* history, float* out);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
@@ -1037,6 +1091,7 @@ static_assert(sizeof(tri_image) == 32, "tri_image layout");
 static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
 static_assert(sizeof(tri_pick_result) == 16, "tri_pick_result layout");
 static_assert(sizeof(tri_outline) == 40, "tri_outline layout");
+static_assert(sizeof(tri_motion_history) == 144, "tri_motion_history layout");
 static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
 static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
 static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
