@@ -123,6 +123,28 @@ void tri_plan_frame(const TriFrameParams& fp, TriFramePlan& plan, bool id_pass =
 // k_motion and its grid over W x rows pixels (motion_pass.hip)
 const void* tri_motion_kernel(bool vec4);
 dim3 tri_motion_grid(uint32_t npix, bool vec4);
+// The history reprojection pass's arguments (history_pass.hip), by value and alone: k_reproject is no part of a frame's
+// plan; tri_history_reproject enqueues it behind the frame. Every image is W x H, whole frames only.
+struct TriReprojectArgs {
+    TRI_G const uint32_t* colour;       // the frame just rendered: B8G8R8A8, ids, depth
+    TRI_G const uint32_t* ids;
+    TRI_G const float* depth;
+    TRI_G const float* table;           // (ndraws + 1) x 16: the motion table the frame staged
+    TRI_G const uint32_t* prev_colour;  // the stored previous frame (not read when has_prev is 0)
+    TRI_G const uint32_t* prev_ids;
+    TRI_G const float* prev_depth;
+    TRI_G uint32_t* next_colour;        // the other set: the frame just rendered, stored for the next call
+    TRI_G uint32_t* next_ids;
+    TRI_G float* next_depth;
+    TRI_G uint32_t* warped;             // B8G8R8A8
+    TRI_G uint8_t* mask;                // one byte per pixel (4-B aligned)
+    uint32_t W, H, npix, ndraws;
+    float sx, sy, hw, hh;               // 2 / W, 2 / H, W / 2, H / 2 (float32, from the host)
+    float tolerance;
+    uint32_t has_prev;
+};
+// k_reproject over the frame on `stream`: four pixels per lane (vec4) when every image starts on a 16-B boundary, else one.
+hipError_t tri_launch_reproject(const TriReprojectArgs& args, bool vec4, hipStream_t stream);
 // k_id_raster at the frame's bin size (id_pass.hip)
 const void* tri_id_raster_kernel(const TriFrameParams& fp);
 #ifdef TRI_DIAG_FRONT

@@ -61,6 +61,15 @@ public:
     static void SetMotionVectorOutputEnabled(uint32_t viewportId, bool enabled) { GetRenderer().SetMotionVectorOutputEnabled(viewportId, enabled); }
     static bool ReadViewportMotionVectors(uint32_t viewportId, std::vector<float>& out) { return GetRenderer().ReadViewportMotionVectors(viewportId, out); }
     static void* GetViewportMotionTexture(uint32_t viewportId) { return GetRenderer().GetViewportMotionTexture(viewportId); }
+    // History reprojection: the viewport's previous frame warped by motion, and its disocclusion mask
+    static void SetHistoryReprojectionEnabled(uint32_t viewportId, bool enabled, float depthTolerance = 0.0f) {
+        GetRenderer().SetHistoryReprojectionEnabled(viewportId, enabled, depthTolerance);
+    }
+    static bool ReadViewportReprojection(uint32_t viewportId, std::vector<uint8_t>& bgra, std::vector<uint8_t>& mask) {
+        return GetRenderer().ReadViewportReprojection(viewportId, bgra, mask);
+    }
+    static void* GetViewportReprojectedTexture(uint32_t viewportId) { return GetRenderer().GetViewportReprojectedTexture(viewportId); }
+    static void* GetViewportDisocclusionTexture(uint32_t viewportId) { return GetRenderer().GetViewportDisocclusionTexture(viewportId); }
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }

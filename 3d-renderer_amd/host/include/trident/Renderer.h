@@ -300,6 +300,27 @@ public:
     // GetViewportTexture's; null where ReadViewportMotionVectors returns false.
     void* GetViewportMotionTexture(uint32_t viewportId);
 
+    // History reprojection (tri_history): behind each of the viewport's frames, the previous frame's colour fetched
+    // where the pixel's motion vector points, and a mask byte per pixel that says where that fetch is not valid
+    // (TRI_REPROJECT_*: no history, no projection, outside the frame, another entity, beyond depthTolerance in depth;
+    // 0: valid) — what temporal accumulation, frame extrapolation and a warped baseline for the frame generator start
+    // from. The request turns the viewport's id and motion outputs on, as motion turns ids on. One history per
+    // VIEWPORT, not per ring target: frame k is warped from frame k - 1 whatever SetFramesInFlight is. No history
+    // (mask 1 everywhere, the current colour): the viewport's first frame, the first after a resize, the first after
+    // the switch goes on. The colour is the frame's as the viewport shows it, text and outline included. A frame
+    // re-rendered after a queue overflow is reprojected again; with several frames in flight the frame after it had
+    // already read it, so the history is reset instead. Refused with a log line while SetDeviceCount > 1 (which also
+    // turns it off), and for a negative or non-finite tolerance.
+    void SetHistoryReprojectionEnabled(uint32_t viewportId, bool enabled, float depthTolerance = 0.0f);
+    bool IsHistoryReprojectionEnabled(uint32_t viewportId) const;
+    // width * height * 4 bytes (B G R A) and width * height mask bytes of the viewport's latest frame (fences); false
+    // for a viewport that does not exist or whose latest frame was not reprojected.
+    bool ReadViewportReprojection(uint32_t viewportId, std::vector<uint8_t>& bgra, std::vector<uint8_t>& mask);
+    // Opaque pointers to the tri_image of the warped colour (B8G8R8A8_UNORM) and of the mask (R8_UINT, pitch width),
+    // valid until the viewport is resized or the switch goes off; null where ReadViewportReprojection returns false.
+    void* GetViewportReprojectedTexture(uint32_t viewportId);
+    void* GetViewportDisocclusionTexture(uint32_t viewportId);
+
     // Frame readback (ResolvePendingReadback, Renderer.cpp:1299-1389): RGBA8 rows of the viewport
     // (BGRA reordered to RGBA), optionally the D32 depth.
     bool ReadViewportPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr);
@@ -405,6 +426,14 @@ private:
     bool SetTargetMotion(ViewportContext& target, uint32_t viewportId, const tri_global_ubo& ubo,
                          const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities);
     const ViewportContext* MotionTarget(uint32_t viewportId);  // fenced; null unless the latest frame carries motion
+    // the motion output a viewport's frames carry: asked for itself, or by the history reprojection
+    bool WantsMotion(uint32_t viewportId) const { return IsMotionVectorOutputEnabled(viewportId) || IsHistoryReprojectionEnabled(viewportId); }
+    struct Reprojection;
+    // behind the target's tri_render: the viewport's history warped by this frame (redo: the frame was rendered again)
+    bool ReprojectTarget(ViewportContext& target, uint32_t viewportId, bool redo);
+    void RedoReprojection(ViewportContext& target);  // FinishOldestFrame re-rendered the target's frame
+    void DropHistories();                            // with the targets (DestroyViewportTargets)
+    Reprojection* ReprojectionOutput(uint32_t viewportId);  // fenced; null unless the latest frame was reprojected
     const Camera* GetActiveCamera(const ViewportContext& context) const;
     bool PrepareViewport(ViewportContext& context);
     // One viewport pass: pre-pass / palette / UBO / draws, then tri_render (asynchronous); false on error.
@@ -503,6 +532,15 @@ private:
     };
     std::map<uint32_t, bool> m_MotionViewports;  // SetMotionVectorOutputEnabled, by viewport id
     std::map<uint32_t, MotionHistory> m_MotionHistory;
+    struct Reprojection {  // SetHistoryReprojectionEnabled, by viewport id
+        bool m_Enabled = false;
+        float m_DepthTolerance = 0.0f;
+        tri_history* m_History = nullptr;  // made at the viewport's first reprojected frame, again after a resize
+        uint32_t m_Width = 0, m_Height = 0;
+        const ViewportContext* m_LastTarget = nullptr;  // the target whose frame the last pass read
+        tri_image m_Colour{}, m_Mask{};
+    };
+    std::map<uint32_t, Reprojection> m_Reprojection;
     std::map<uint32_t, ViewportContext> m_Viewports;
     ViewportInfo m_LastViewport{};
     uint32_t m_ActiveViewportId = 0;

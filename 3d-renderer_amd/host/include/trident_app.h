@@ -271,6 +271,17 @@ int trident_app_read_motion_vectors(trident_app* app, uint32_t viewport_id, floa
 /* Renderer::GetViewportMotionTexture: copies the motion image's handle (TRI_E_STATE where it returns null). */
 int trident_app_motion_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
 
+/* ---- history reprojection ---- */
+/* Renderer::SetHistoryReprojectionEnabled: from the viewport's next draw_frame on; TRI_E_STATE where the renderer
+ * refuses (SetDeviceCount > 1, a negative or non-finite tolerance). */
+int trident_app_set_history_reprojection(trident_app* app, uint32_t viewport_id, int enabled, float depth_tolerance);
+/* Renderer::ReadViewportReprojection: width * height * 4 bytes of warped colour (B G R A) and width * height mask
+ * bytes; TRI_E_STATE where it returns false, TRI_E_INVALID when capacity (in pixels) is short. */
+int trident_app_read_reprojection(trident_app* app, uint32_t viewport_id, uint8_t* bgra, uint8_t* mask, uint64_t capacity);
+/* Renderer::GetViewportReprojectedTexture / GetViewportDisocclusionTexture: copies the two handles (TRI_E_STATE where
+ * they return null). */
+int trident_app_reprojection_textures(trident_app* app, uint32_t viewport_id, tri_image* colour, tri_image* mask);
+
 /* ---- text overlay ---- */
 /* Renderer::SubmitText: `bytes` bytes of UTF-8 (no terminator needed) at `position` (viewport pixels) in `color`
  * (RGBA) for the viewport's next draw_frame. */

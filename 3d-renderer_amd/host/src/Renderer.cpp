@@ -252,6 +252,7 @@ void Renderer::Init() {
 
 void Renderer::DestroyViewportTargets() {
     m_Pending.clear();  // (its targets go; tri_destroy / tri_group_destroy wait for their streams)
+    DropHistories();    // (each waits for its last pass; the new targets' first frames have no history)
     tri_recorder_destroy(m_Recorder);  // (waits for its captures; the next recorded DrawFrame makes a new one)
     m_Recorder = nullptr;
     DropGrab();  // (likewise; the next captured DrawFrame makes a new one)
@@ -451,6 +452,11 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         if (any) LogError("SetDeviceCount", "multi-device viewports write no motion vectors: the output was turned off");
         m_MotionViewports.clear();
         m_MotionHistory.clear();
+        any = false;
+        for (auto& it : m_Reprojection) any |= it.second.m_Enabled;
+        if (any) LogError("SetDeviceCount", "multi-device viewports have no history reprojection: it was turned off");
+        DropHistories();
+        m_Reprojection.clear();
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
@@ -1471,6 +1477,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         if (!SetTargetIds(vc, id, draws, drawEntities)) LogError("DrawFrame", "the entity ids of this frame are missing");
         if (!SetTargetMotion(vc, id, ubo, draws, drawEntities)) LogError("DrawFrame", "the motion vectors of this frame are missing");
         if (!SubmitTarget(vc, TargetUniforms(vc, ubo), draws, shadow, shadowOn)) return;
+        if (!ReprojectTarget(vc, id, false)) LogError("DrawFrame", "the history reprojection of this frame is missing");
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
         // AI readback: the active viewport's tensor, likewise, when the readback throttle has elapsed (ResolvePending-
@@ -1562,6 +1569,7 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
             rerendered = true;
         }
         if (rc != TRI_OK) LogError("frame fence", tri_last_error());
+        if (rc == TRI_OK && rerendered) RedoReprojection(*vc);  // the pass behind the first render read an incomplete frame
         if (rc == TRI_OK) vc->m_HasImage = t.Output(&vc->m_Image) == TRI_OK;  // a re-render moves a group's buffer
         if (vc == p.m_Legacy && rc == TRI_OK) {
             m_PresentSource = vc->m_Ctx;
@@ -2151,7 +2159,7 @@ bool Renderer::SetTargetIds(ViewportContext& vc, uint32_t viewportId, const std:
             if (entities[d] == m_SelectedEntity) selected.push_back(d);
     auto want = m_IdOutputViewports.find(viewportId);
     const bool ids = (want != m_IdOutputViewports.end() && want->second) || !selected.empty() ||
-                     (vc.m_Ctx && IsMotionVectorOutputEnabled(viewportId));  // (the motion pass reads the ids)
+                     (vc.m_Ctx && WantsMotion(viewportId));  // (the motion pass reads the ids)
     bool ok = true;
     if (ids != vc.m_IdOutput) {
         if (t.IdOutput(ids) != TRI_OK) {
@@ -2275,7 +2283,7 @@ bool Renderer::IsMotionVectorOutputEnabled(uint32_t viewportId) const {
 // brought up to date when its turn comes). The history is the viewport's, whichever target rendered its last frame.
 bool Renderer::SetTargetMotion(ViewportContext& vc, uint32_t viewportId, const tri_global_ubo& ubo,
                                const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities) {
-    const bool want = vc.m_Ctx && vc.m_IdOutput && IsMotionVectorOutputEnabled(viewportId);
+    const bool want = vc.m_Ctx && vc.m_IdOutput && WantsMotion(viewportId);
     if (vc.m_Ctx && want != vc.m_MotionOutput) {
         if (tri_set_motion_output(vc.m_Ctx, want ? 1 : 0) != TRI_OK || (want && tri_get_motion_output(vc.m_Ctx, &vc.m_MotionImage) != TRI_OK)) {
             LogError("motion vectors", tri_last_error());
@@ -2286,7 +2294,7 @@ bool Renderer::SetTargetMotion(ViewportContext& vc, uint32_t viewportId, const t
     }
     if (!want) {
         m_MotionHistory.erase(viewportId);  // the first frame after the output is switched on has no history
-        return !IsMotionVectorOutputEnabled(viewportId);
+        return !WantsMotion(viewportId);
     }
     MotionHistory& h = m_MotionHistory[viewportId];
     const uint32_t n = (uint32_t)std::min(draws.size(), entities.size());
@@ -2338,6 +2346,118 @@ bool Renderer::ReadViewportMotionVectors(uint32_t viewportId, std::vector<float>
 void* Renderer::GetViewportMotionTexture(uint32_t viewportId) {
     const ViewportContext* vc = MotionTarget(viewportId);
     return vc ? const_cast<tri_image*>(&vc->m_MotionImage) : nullptr;
+}
+
+// ---- history reprojection -------------------------------------------------------------------------------------------
+void Renderer::SetHistoryReprojectionEnabled(uint32_t viewportId, bool enabled, float depthTolerance) {
+    if (enabled && m_Devices.size() > 1) {
+        LogError("history reprojection", "multi-device viewports (SetDeviceCount > 1) have no history reprojection");
+        return;
+    }
+    if (enabled && !(depthTolerance >= 0.0f && std::isfinite(depthTolerance))) {
+        LogError("history reprojection", "the depth tolerance is negative or not finite");
+        return;
+    }
+    Reprojection& st = m_Reprojection[viewportId];
+    // the first frame after the switch goes on has no history (frames rendered meanwhile were not stored)
+    if (enabled && !st.m_Enabled && st.m_History && tri_history_reset(st.m_History) != TRI_OK)
+        LogError("history reprojection", tri_last_error());
+    if (!enabled) st.m_LastTarget = nullptr;  // the readers answer for reprojected frames only
+    st.m_Enabled = enabled;
+    st.m_DepthTolerance = depthTolerance;
+}
+
+bool Renderer::IsHistoryReprojectionEnabled(uint32_t viewportId) const {
+    auto it = m_Reprojection.find(viewportId);
+    return it != m_Reprojection.end() && it->second.m_Enabled;
+}
+
+void Renderer::DropHistories() {
+    for (auto& it : m_Reprojection) {
+        tri_history_destroy(it.second.m_History);  // (waits for its last pass)
+        it.second.m_History = nullptr;
+        it.second.m_LastTarget = nullptr;
+    }
+}
+
+// One tri_history per viewport, whichever of its targets renders the frame: ring targets are separate contexts and the
+// object orders its passes across their streams itself.
+bool Renderer::ReprojectTarget(ViewportContext& vc, uint32_t viewportId, bool redo) {
+    auto it = m_Reprojection.find(viewportId);
+    if (it == m_Reprojection.end() || !it->second.m_Enabled) return true;
+    Reprojection& st = it->second;
+    st.m_LastTarget = nullptr;
+    if (!vc.m_Ctx || !vc.m_MotionOutput) return false;
+    if (st.m_History && (st.m_Width != vc.m_Width || st.m_Height != vc.m_Height)) {  // a resize: a new object, no history
+        tri_history_destroy(st.m_History);
+        st.m_History = nullptr;
+    }
+    if (!st.m_History) {
+        tri_image img{};
+        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK || tri_history_create(img.device, vc.m_Width, vc.m_Height, &st.m_History) != TRI_OK) {
+            LogError("history reprojection", tri_last_error());
+            st.m_History = nullptr;
+            return false;
+        }
+        st.m_Width = vc.m_Width;
+        st.m_Height = vc.m_Height;
+    }
+    tri_reproject_params params{};
+    params.depth_tolerance = st.m_DepthTolerance;
+    params.flags = redo ? TRI_HISTORY_REDO : 0u;
+    if (tri_history_reproject(st.m_History, vc.m_Ctx, &params) != TRI_OK ||
+        tri_history_get_output(st.m_History, &st.m_Colour, &st.m_Mask) != TRI_OK) {
+        LogError("history reprojection", tri_last_error());
+        return false;
+    }
+    st.m_LastTarget = &vc;
+    return true;
+}
+
+// The target's frame overflowed a queue and was rendered again. When its pass was the history's last, a redo pass reads
+// the same previous frame and stores the complete one. With several frames in flight a later frame has already been
+// warped from the incomplete one: nothing can mend that frame, and the history is reset so that nothing builds on it.
+void Renderer::RedoReprojection(ViewportContext& vc) {
+    auto it = m_Reprojection.find(vc.m_Info.ViewportID);
+    if (it == m_Reprojection.end() || !it->second.m_Enabled || !it->second.m_History || &vc == &m_LegacyTarget) return;
+    Reprojection& st = it->second;
+    if (st.m_LastTarget == &vc) {
+        if (ReprojectTarget(vc, vc.m_Info.ViewportID, true)) {
+            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError("history reprojection", tri_last_error());
+        }
+    } else if (tri_history_reset(st.m_History) != TRI_OK) {
+        LogError("history reprojection", tri_last_error());
+    }
+}
+
+Renderer::Reprojection* Renderer::ReprojectionOutput(uint32_t viewportId) {
+    FinishFrame();
+    auto it = m_Reprojection.find(viewportId);
+    if (it == m_Reprojection.end() || !it->second.m_History || !it->second.m_LastTarget) return nullptr;
+    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame was not reprojected
+    return &it->second;
+}
+
+bool Renderer::ReadViewportReprojection(uint32_t viewportId, std::vector<uint8_t>& bgra, std::vector<uint8_t>& mask) {
+    Reprojection* st = ReprojectionOutput(viewportId);
+    if (!st) return false;
+    bgra.resize((size_t)st->m_Width * st->m_Height * 4);
+    mask.resize((size_t)st->m_Width * st->m_Height);
+    if (tri_history_read(st->m_History, bgra.data(), mask.data()) != TRI_OK) {
+        LogError("history reprojection", tri_last_error());
+        return false;
+    }
+    return true;
+}
+
+void* Renderer::GetViewportReprojectedTexture(uint32_t viewportId) {
+    Reprojection* st = ReprojectionOutput(viewportId);
+    return st ? &st->m_Colour : nullptr;
+}
+
+void* Renderer::GetViewportDisocclusionTexture(uint32_t viewportId) {
+    Reprojection* st = ReprojectionOutput(viewportId);
+    return st ? &st->m_Mask : nullptr;
 }
 
 void* Renderer::GetViewportTexture(uint32_t viewportId) const {

@@ -719,6 +719,37 @@ int trident_app_motion_texture(trident_app* app, uint32_t viewport_id, tri_image
     });
 }
 
+int trident_app_set_history_reprojection(trident_app* app, uint32_t viewport_id, int enabled, float depth_tolerance) {
+    return Guard(app, [&] {
+        app->renderer.SetHistoryReprojectionEnabled(viewport_id, enabled != 0, depth_tolerance);
+        return app->renderer.IsHistoryReprojectionEnabled(viewport_id) == (enabled != 0) ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_app_read_reprojection(trident_app* app, uint32_t viewport_id, uint8_t* bgra, uint8_t* mask, uint64_t capacity) {
+    return Guard(app, [&] {
+        if (!bgra || !mask) return TRI_E_INVALID;
+        std::vector<uint8_t> c, m;
+        if (!app->renderer.ReadViewportReprojection(viewport_id, c, m)) return TRI_E_STATE;
+        if (m.size() > capacity) return TRI_E_INVALID;
+        std::memcpy(bgra, c.data(), c.size());
+        std::memcpy(mask, m.data(), m.size());
+        return TRI_OK;
+    });
+}
+
+int trident_app_reprojection_textures(trident_app* app, uint32_t viewport_id, tri_image* colour, tri_image* mask) {
+    return Guard(app, [&] {
+        if (!colour || !mask) return TRI_E_INVALID;
+        const void* c = app->renderer.GetViewportReprojectedTexture(viewport_id);
+        const void* m = app->renderer.GetViewportDisocclusionTexture(viewport_id);
+        if (!c || !m) return TRI_E_STATE;
+        *colour = *static_cast<const tri_image*>(c);
+        *mask = *static_cast<const tri_image*>(m);
+        return TRI_OK;
+    });
+}
+
 struct trident_font {
     TextRenderer text;
 };

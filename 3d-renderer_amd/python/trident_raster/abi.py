@@ -232,6 +232,19 @@ class TriMotionHistory(C.Structure):
 assert C.sizeof(TriMotionHistory) == 144
 
 
+# history reprojection (include/tri_raster.h): the mask image's format, the mask bits, the pass's parameters
+TRI_FORMAT_R8_UINT = 13
+TRI_REPROJECT_NO_HISTORY, TRI_REPROJECT_NO_PROJ, TRI_REPROJECT_OUTSIDE, TRI_REPROJECT_ID, TRI_REPROJECT_DEPTH = 1, 2, 4, 8, 16
+TRI_HISTORY_REDO = 1
+
+
+class TriReprojectParams(C.Structure):
+    _fields_ = [("depth_tolerance", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(TriReprojectParams) == 16
+
+
 class TriGroupConfig(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -491,6 +504,13 @@ CABI_FUNCTIONS = [
     ("tri_get_motion_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("tri_motion_matrices", C.c_int, [C.POINTER(TriGlobalUbo), C.POINTER(TriDraw), C.c_uint32, C.POINTER(TriMotionHistory),
                                       C.c_void_p]),
+    ("tri_history_create", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_history_destroy", C.c_int, [C.c_void_p]),
+    ("tri_history_reproject", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TriReprojectParams)]),
+    ("tri_history_reset", C.c_int, [C.c_void_p]),
+    ("tri_history_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("tri_history_get_output", C.c_int, [C.c_void_p, C.POINTER(TriImage), C.POINTER(TriImage)]),
+    ("tri_history_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
 ]
 
 

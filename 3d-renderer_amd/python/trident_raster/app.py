@@ -129,6 +129,9 @@ _APP_FUNCTIONS = [
     ("trident_app_set_motion_vector_output", C.c_int, [C.c_void_p, C.c_uint32, C.c_int]),
     ("trident_app_read_motion_vectors", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]),
     ("trident_app_motion_texture", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage)]),
+    ("trident_app_set_history_reprojection", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_float]),
+    ("trident_app_read_reprojection", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("trident_app_reprojection_textures", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage), C.POINTER(abi.TriImage)]),
     ("trident_app_submit_text", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4),
                                           C.c_char_p, C.c_uint32]),
     ("trident_app_set_font", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
@@ -485,6 +488,36 @@ class TridentApp:
             return None
         _check(rc, "motion_texture")
         return img
+
+    # ---- history reprojection ----
+    def set_history_reprojection(self, viewport_id, enabled=True, depth_tolerance=0.0):
+        """Renderer::SetHistoryReprojectionEnabled; False where the renderer refuses it (SetDeviceCount > 1, a bad
+        tolerance)."""
+        rc = self._lib.trident_app_set_history_reprojection(self._h, viewport_id, 1 if enabled else 0, depth_tolerance)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_history_reprojection")
+        return rc == abi.TRI_OK
+
+    def read_reprojection(self, viewport_id, width, height):
+        """Renderer::ReadViewportReprojection: (warped uint8 [height, width, 4] B G R A, mask uint8 [height, width]), or
+        None where it returns false."""
+        col = np.zeros((height, width, 4), np.uint8)
+        mask = np.zeros((height, width), np.uint8)
+        rc = self._lib.trident_app_read_reprojection(self._h, viewport_id, col.ctypes.data, mask.ctypes.data, mask.size)
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "read_reprojection")
+        return col, mask
+
+    def reprojection_textures(self, viewport_id):
+        """Renderer::GetViewportReprojectedTexture and GetViewportDisocclusionTexture: (colour, mask) abi.TriImage
+        handles, or None."""
+        col, mask = abi.TriImage(), abi.TriImage()
+        rc = self._lib.trident_app_reprojection_textures(self._h, viewport_id, C.byref(col), C.byref(mask))
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "reprojection_textures")
+        return col, mask
 
     def set_font(self, path, pixel_height=32.0):
         """Renderer::SetTextFont; returns its bool."""

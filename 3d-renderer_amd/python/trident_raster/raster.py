@@ -399,6 +399,63 @@ def motion_matrices(ubo, draws, history=None):
     return out
 
 
+class TriHistory:
+    """tri_history: the previous frame of one view (colour, ids, depth) outside any context, and the pass that warps it
+    by a rendered frame's motion."""
+
+    def __init__(self, width, height, device=-1):
+        lib = load_library()
+        h = C.c_void_p()
+        _check(lib.tri_history_create(device, width, height, C.byref(h)))
+        self._h = h
+        self.width, self.height = width, height
+
+    def close(self):
+        if self._h:
+            _lib.tri_history_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reproject(self, raster, depth_tolerance=0.0, redo=False, flags=None):
+        """tri_history_reproject behind the raster's last render (asynchronous). flags overrides redo's bit (for the
+        error cases)."""
+        p = abi.TriReprojectParams(float(depth_tolerance), (abi.TRI_HISTORY_REDO if redo else 0) if flags is None else flags)
+        _check(_lib.tri_history_reproject(self._h, raster._ctx, C.byref(p)))
+
+    def reset(self):
+        _check(_lib.tri_history_reset(self._h))
+
+    def read(self):
+        """tri_history_read: (warped colour uint8 [H, W, 4] B G R A, mask uint8 [H, W])."""
+        col = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        mask = np.empty((self.height, self.width), dtype=np.uint8)
+        _check(_lib.tri_history_read(self._h, _ptr(col), _ptr(mask)))
+        return col, mask
+
+    def images(self):
+        """tri_history_get_output: (colour, mask) as abi.TriImage."""
+        col, mask = abi.TriImage(), abi.TriImage()
+        _check(_lib.tri_history_get_output(self._h, C.byref(col), C.byref(mask)))
+        return col, mask
+
+    def timing(self):
+        """tri_history_get_timing: (summed ms of the stamped passes, their number)."""
+        ms, n = C.c_double(), C.c_uint64()
+        _check(_lib.tri_history_get_timing(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
 def _pick_rect(call, x0, y0, x1, y1, draw_count):
     words = max((int(draw_count) + 31) // 32, 1)
     bits = np.zeros(words, dtype=np.uint32)

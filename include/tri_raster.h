@@ -886,6 +886,78 @@ int tri_get_motion_timing(tri_ctx* ctx, double* ms_motion, uint64_t* frames);
 int tri_motion_matrices(const tri_global_ubo* ubo, const tri_draw* draws, uint32_t draw_count,
                         const tri_motion_history* history, float* out);
 
+/* ---- history reprojection: the last frame warped by motion, with a disocclusion mask ---------- */
+/* A tri_history keeps the previous frame of one view — colour, ids and depth — outside any context, so it survives
+ * frames in flight that are separate contexts as well as a single context that overwrites itself. After a tri_render
+ * with the motion output on, tri_history_reproject enqueues k_reproject on the context's stream: per pixel it fetches
+ * the previous frame's colour where the motion vector points, says in a mask byte where that fetch is not valid, and
+ * stores the frame just rendered as the next call's previous frame. No kernel of the frame changes; the context's
+ * colour, depth, ids and motion are bit-identical with and without the pass.
+ * The rule, for pixel p = (x, y) with current id i, depth d and colour c (4 bytes, B G R A), R the row of the motion
+ * table tri_render staged for i, I', D', C' the stored previous frame and W x H the frame; float32, no multiply-add
+ * contracted, in exactly this order:
+ *     fx, fy, xn, yn, z, q_0, q_1, q_3, iw, m.x, m.y   exactly as under "motion vectors" (m is what k_motion stores)
+ *     q_2  = ((R[2][0] * xn + R[2][1] * yn) + R[2][2] * z) + R[2][3]
+ *     proj = q_3 > 0.0f and m.x, m.y finite before their zeroing
+ *     u = fx + m.x       v = fy + m.y                   the previous position, pixel centres at + 0.5
+ *     inside = proj && u >= 0.0f && u < (float)W && v >= 0.0f && v < (float)H
+ *     xi = (int)floorf(u)    yi = (int)floorf(v)        only when inside
+ *     i' = I'[yi][xi]        d' = i' ? D'[yi][xi] : 1.0f          zp = q_2 * iw
+ * The mask byte (at most one bit is set):
+ *     TRI_REPROJECT_NO_HISTORY  the object holds no previous frame; the mask is then exactly 1 on every pixel
+ *     TRI_REPROJECT_NO_PROJ     !proj
+ *     TRI_REPROJECT_OUTSIDE     proj && !inside
+ *     TRI_REPROJECT_ID          inside && i' != i
+ *     TRI_REPROJECT_DEPTH       inside && i' == i && i != 0 && depth_tolerance > 0 && !(fabsf(zp - d') <= depth_tolerance)
+ * The warped colour where the mask is 0: with su = u - 0.5f, sv = v - 0.5f, x0 = floorf(su), y0 = floorf(sv),
+ * fu = su - x0, fv = sv - y0 and the taps (x0, y0) (x0+1, y0) (x0, y0+1) (x0+1, y0+1) of C', each coordinate clamped
+ * to the frame, per channel as float:  t = c00 * (1.0f - fu) + c10 * fu,  b = c01 * (1.0f - fu) + c11 * fu,
+ * r = t * (1.0f - fv) + b * fv,  out = min((int)(r + 0.5f), 255). Where the mask is not 0 it is c, unchanged. A tap is
+ * taken whatever id it has.
+ * The colour is read as the context holds it when the call is enqueued: after the selection outline and the text
+ * overlay. A caller who wants clean history leaves them off that frame. One host thread per object. */
+#define TRI_FORMAT_R8_UINT 13u /* VK_FORMAT_R8_UINT: tri_image.format of the mask image */
+#define TRI_REPROJECT_NO_HISTORY 1u
+#define TRI_REPROJECT_NO_PROJ 2u
+#define TRI_REPROJECT_OUTSIDE 4u
+#define TRI_REPROJECT_ID 8u
+#define TRI_REPROJECT_DEPTH 16u
+#define TRI_HISTORY_REDO 1u /* tri_reproject_params.flags: the frame of the last call, rendered again */
+typedef struct tri_history tri_history;
+typedef struct tri_reproject_params {
+    float depth_tolerance; /* >= 0 and finite, in depth-buffer units; 0: no depth test */
+    uint32_t flags;        /* 0 or TRI_HISTORY_REDO */
+    uint32_t reserved[2];
+} tri_reproject_params;
+/* Two sets of {colour, ids, depth} (12 B per pixel each), the warped colour (4 B), the mask (1 B) and the object's
+ * events, on one device (-1 = current). TRI_E_INVALID for a zero extent or more than 2^31 pixels, before any device
+ * is touched. tri_history_destroy waits for the last pass; NULL is TRI_OK. */
+int tri_history_create(int32_t device, uint32_t width, uint32_t height, tri_history** out);
+int tri_history_destroy(tri_history* history);
+/* Asynchronous, on the context's stream behind the tri_render whose frame it reads (and behind the object's previous
+ * pass, which may have run on another context's stream). The sets swap at the start of the NEXT call: that call reads
+ * what this one stored — unless it carries TRI_HISTORY_REDO, which reads the same previous set again and overwrites
+ * what this call stored (for a frame re-rendered after TRI_E_OVERFLOW). On an object that has not been reprojected
+ * since its creation or tri_history_reset, a redo is a plain call.
+ * TRI_E_INVALID: a null argument, a context on another device or of another extent, a negative or non-finite
+ * tolerance, unknown flag bits. TRI_E_UNSUPPORTED: a row-band context (the fetch leaves the band). TRI_E_STATE: the
+ * context's motion output is off, or no frame has been rendered with it. Every check comes before the device is made
+ * current. While a timed frame is wanted of the context (tri_set_timing), the pass is stamped by two events of the
+ * object's own whenever the previous stamps have been collected. */
+int tri_history_reproject(tri_history* history, tri_ctx* ctx, const tri_reproject_params* params);
+/* Forget the stored frame: the next call reports TRI_REPROJECT_NO_HISTORY everywhere (and a redo is a plain call). */
+int tri_history_reset(tri_history* history);
+/* The last pass's warped colour (width x height x 4 bytes, B G R A) and mask (width x height bytes), tightly packed;
+ * either pointer may be NULL. Waits for the pass. TRI_E_STATE before the first pass. */
+int tri_history_read(tri_history* history, uint8_t* bgra8, uint8_t* mask);
+/* The two images in device memory: the colour as the context's (TRI_FORMAT_B8G8R8A8_UNORM, pitch width * 4), the mask
+ * as TRI_FORMAT_R8_UINT with pitch width. Either pointer may be NULL. Valid until the object is destroyed; contents
+ * are those of the last completed pass. TRI_E_STATE before the first pass. */
+int tri_history_get_output(tri_history* history, tri_image* colour, tri_image* mask);
+/* The summed milliseconds of the stamped passes and their number (waits for the last stamped pass). tri_timing is
+ * untouched: the pass runs behind the frame's last stamp. */
+int tri_history_get_timing(tri_history* history, double* ms, uint64_t* passes);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
@@ -1092,6 +1164,7 @@ static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
 static_assert(sizeof(tri_pick_result) == 16, "tri_pick_result layout");
 static_assert(sizeof(tri_outline) == 40, "tri_outline layout");
 static_assert(sizeof(tri_motion_history) == 144, "tri_motion_history layout");
+static_assert(sizeof(tri_reproject_params) == 16, "tri_reproject_params layout");
 static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
 static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
 static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
