@@ -145,6 +145,26 @@ struct TriReprojectArgs {
 };
 // k_reproject over the frame on `stream`: four pixels per lane (vec4) when every image starts on a 16-B boundary, else one.
 hipError_t tri_launch_reproject(const TriReprojectArgs& args, bool vec4, hipStream_t stream);
+// The temporal anti-aliasing pass's arguments (taa_pass.hip), by value and alone like k_reproject's: tri_taa_resolve
+// enqueues k_taa_resolve behind the frame. Every image is W x H, whole frames only. The context's planes are read four
+// bytes at a time and may start anywhere; the object's own come from hipMalloc.
+struct TriTaaArgs {
+    TRI_G const uint32_t* colour;    // the frame just rendered: B8G8R8A8, ids, depth
+    TRI_G const uint32_t* ids;
+    TRI_G const float* depth;
+    TRI_G const float* table;        // (ndraws + 1) x 16: the motion table the frame staged
+    TRI_G const uint2* prev_acc;     // the stored history (not read when has_prev is 0): 4 x uint16 per pixel, and ids
+    TRI_G const uint32_t* prev_ids;
+    TRI_G uint2* next_acc;           // the other set
+    TRI_G uint32_t* next_ids;
+    TRI_G uint32_t* resolved;        // B8G8R8A8
+    TRI_G uint8_t* mask;             // one byte per pixel
+    uint32_t W, H, ndraws;
+    float sx, sy, hw, hh;            // 2 / W, 2 / H, W / 2, H / 2 (float32, from the host)
+    float alpha;
+    uint32_t has_prev, reject_id;
+};
+hipError_t tri_launch_taa_resolve(const TriTaaArgs& args, hipStream_t stream);
 // k_id_raster at the frame's bin size (id_pass.hip)
 const void* tri_id_raster_kernel(const TriFrameParams& fp);
 #ifdef TRI_DIAG_FRONT

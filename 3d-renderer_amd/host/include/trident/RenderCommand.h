@@ -70,6 +70,17 @@ public:
     }
     static void* GetViewportReprojectedTexture(uint32_t viewportId) { return GetRenderer().GetViewportReprojectedTexture(viewportId); }
     static void* GetViewportDisocclusionTexture(uint32_t viewportId) { return GetRenderer().GetViewportDisocclusionTexture(viewportId); }
+    // Temporal anti-aliasing: jittered frames resolved over the viewport's clamped, accumulated history
+    static void SetTemporalAntiAliasingEnabled(uint32_t viewportId, bool enabled, float alpha = 0.1f, uint32_t period = 8,
+                                               bool rejectIds = true) {
+        GetRenderer().SetTemporalAntiAliasingEnabled(viewportId, enabled, alpha, period, rejectIds);
+    }
+    static bool IsTemporalAntiAliasingEnabled(uint32_t viewportId) { return GetRenderer().IsTemporalAntiAliasingEnabled(viewportId); }
+    static bool ReadViewportResolvedPixels(uint32_t viewportId, std::vector<uint8_t>& rgba) {
+        return GetRenderer().ReadViewportResolvedPixels(viewportId, rgba);
+    }
+    static bool ReadViewportTaaMask(uint32_t viewportId, std::vector<uint8_t>& mask) { return GetRenderer().ReadViewportTaaMask(viewportId, mask); }
+    static void* GetViewportResolvedTexture(uint32_t viewportId) { return GetRenderer().GetViewportResolvedTexture(viewportId); }
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }

@@ -321,6 +321,31 @@ public:
     void* GetViewportReprojectedTexture(uint32_t viewportId);
     void* GetViewportDisocclusionTexture(uint32_t viewportId);
 
+    // Temporal anti-aliasing (tri_taa): while it is on, each DrawFrame of the viewport renders with its projection
+    // moved inside the pixel — tri_taa_jitter(frameIndex, period), frameIndex counting the viewport's frames from 0
+    // since the switch went on or the last resize — and resolves the frame over the viewport's accumulated, clamped
+    // history (weight alpha for the current frame; rejectIds: the 3 x 3 entity test). The request turns the viewport's
+    // id and motion outputs on; the motion history keeps the UNJITTERED projection and is handed on under the current
+    // jitter, so still geometry maps to itself and nothing blurs. One tri_taa per VIEWPORT, not per ring target; a
+    // resize makes a new one, switching on resets it. Behind the viewport's tri_render and before the history
+    // reprojection. A frame re-rendered after a queue overflow is resolved again (redo); with several frames in
+    // flight the history is reset instead, as for the history reprojection. While it is on for the active viewport,
+    // the present blit and ReadPresentPixels show the RESOLVED image. GetViewportTexture, ReadViewportPixels, the
+    // recording, the AI tensor and the dataset samples keep taking the context's raw, jittered frame. Refused with a
+    // log line while SetDeviceCount > 1 (which also turns it off), for an alpha outside (0, 1] and for a period
+    // above 64.
+    void SetTemporalAntiAliasingEnabled(uint32_t viewportId, bool enabled, float alpha = 0.1f, uint32_t period = 8,
+                                        bool rejectIds = true);
+    bool IsTemporalAntiAliasingEnabled(uint32_t viewportId) const;
+    // width * height * 4 bytes, R G B A like ReadViewportPixels, of the viewport's latest resolved frame (fences); false
+    // for a viewport that does not exist or whose latest frame was not resolved.
+    bool ReadViewportResolvedPixels(uint32_t viewportId, std::vector<uint8_t>& rgba);
+    // width * height mask bytes (TRI_TAA_*) of the same frame.
+    bool ReadViewportTaaMask(uint32_t viewportId, std::vector<uint8_t>& mask);
+    // Opaque pointer to the tri_image of the resolved colour (B8G8R8A8_UNORM), valid until the viewport is resized or
+    // the switch goes off; null where ReadViewportResolvedPixels returns false.
+    void* GetViewportResolvedTexture(uint32_t viewportId);
+
     // Frame readback (ResolvePendingReadback, Renderer.cpp:1299-1389): RGBA8 rows of the viewport
     // (BGRA reordered to RGBA), optionally the D32 depth.
     bool ReadViewportPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr);
@@ -423,11 +448,28 @@ private:
     const ViewportContext* IdTarget(uint32_t viewportId);  // fenced; null unless the latest frame carries ids
     // before the target's tri_render, after SetTargetIds: the motion output this frame wants on it, the viewport's
     // history as the context's, and this frame's camera and models as the history of the viewport's next frame
+    // (ubo: the UNJITTERED block; jitter: null, or this frame's sub-pixel offset, under which the stored previous
+    // projection is handed to the context — the temporal anti-aliasing's contract)
     bool SetTargetMotion(ViewportContext& target, uint32_t viewportId, const tri_global_ubo& ubo,
-                         const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities);
+                         const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities,
+                         const float* jitter = nullptr);
     const ViewportContext* MotionTarget(uint32_t viewportId);  // fenced; null unless the latest frame carries motion
-    // the motion output a viewport's frames carry: asked for itself, or by the history reprojection
-    bool WantsMotion(uint32_t viewportId) const { return IsMotionVectorOutputEnabled(viewportId) || IsHistoryReprojectionEnabled(viewportId); }
+    // the motion output a viewport's frames carry: asked for itself, by the history reprojection, or by the
+    // temporal anti-aliasing
+    bool WantsMotion(uint32_t viewportId) const {
+        return IsMotionVectorOutputEnabled(viewportId) || IsHistoryReprojectionEnabled(viewportId) ||
+               IsTemporalAntiAliasingEnabled(viewportId);
+    }
+    struct Taa;
+    // before the target's tri_render: this frame's jitter of the viewport (false: the switch is off, no jitter)
+    bool BeginTaaFrame(const ViewportContext& target, uint32_t viewportId, float jitter[2]);
+    // behind the target's tri_render: the frame resolved over the viewport's history (redo: it was rendered again)
+    bool ResolveTarget(ViewportContext& target, uint32_t viewportId, bool redo);
+    void RedoTaa(ViewportContext& target);      // FinishOldestFrame re-rendered the target's frame
+    void DropTaa();                             // with the targets (DestroyViewportTargets)
+    Taa* TaaOutput(uint32_t viewportId);        // fenced; null unless the latest frame was resolved
+    // the presentation blit of a target: its viewport's resolved image while that frame was resolved, else its colour
+    int PresentBlit(ViewportContext& target, uint32_t width, uint32_t height);
     struct Reprojection;
     // behind the target's tri_render: the viewport's history warped by this frame (redo: the frame was rendered again)
     bool ReprojectTarget(ViewportContext& target, uint32_t viewportId, bool redo);
@@ -541,6 +583,19 @@ private:
         tri_image m_Colour{}, m_Mask{};
     };
     std::map<uint32_t, Reprojection> m_Reprojection;
+    struct Taa {  // SetTemporalAntiAliasingEnabled, by viewport id
+        bool m_Enabled = false;
+        float m_Alpha = 0.1f;
+        uint32_t m_Period = 8;
+        bool m_RejectIds = true;
+        tri_taa* m_Object = nullptr;  // made at the viewport's first resolved frame, again after a resize
+        uint32_t m_ObjectWidth = 0, m_ObjectHeight = 0;
+        uint32_t m_Width = 0, m_Height = 0;  // the extent m_FrameIndex counts frames of
+        uint32_t m_FrameIndex = 0;    // the viewport's frames since the switch went on or the last resize
+        const ViewportContext* m_LastTarget = nullptr;  // the target whose frame the last pass read
+        tri_image m_Resolved{};
+    };
+    std::map<uint32_t, Taa> m_Taa;
     std::map<uint32_t, ViewportContext> m_Viewports;
     ViewportInfo m_LastViewport{};
     uint32_t m_ActiveViewportId = 0;

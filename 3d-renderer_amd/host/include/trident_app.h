@@ -282,6 +282,20 @@ int trident_app_read_reprojection(trident_app* app, uint32_t viewport_id, uint8_
  * they return null). */
 int trident_app_reprojection_textures(trident_app* app, uint32_t viewport_id, tri_image* colour, tri_image* mask);
 
+/* ---- temporal anti-aliasing ---- */
+/* Renderer::SetTemporalAntiAliasingEnabled: from the viewport's next draw_frame on; TRI_E_STATE where the renderer
+ * refuses (SetDeviceCount > 1, an alpha outside (0, 1], a period above 64). */
+int trident_app_set_temporal_anti_aliasing(trident_app* app, uint32_t viewport_id, int enabled, float alpha, uint32_t period,
+                                           int reject_ids);
+/* Renderer::IsTemporalAntiAliasingEnabled into *enabled. */
+int trident_app_is_temporal_anti_aliasing(trident_app* app, uint32_t viewport_id, int* enabled);
+/* Renderer::ReadViewportResolvedPixels (width * height * 4 bytes, R G B A) and ReadViewportTaaMask (width * height
+ * bytes); either pointer may be NULL. TRI_E_STATE where they return false, TRI_E_INVALID when capacity (in pixels) is
+ * short. */
+int trident_app_read_resolved(trident_app* app, uint32_t viewport_id, uint8_t* rgba, uint8_t* mask, uint64_t capacity);
+/* Renderer::GetViewportResolvedTexture: copies the handle (TRI_E_STATE where it returns null). */
+int trident_app_resolved_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
+
 /* ---- text overlay ---- */
 /* Renderer::SubmitText: `bytes` bytes of UTF-8 (no terminator needed) at `position` (viewport pixels) in `color`
  * (RGBA) for the viewport's next draw_frame. */

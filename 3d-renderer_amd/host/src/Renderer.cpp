@@ -253,6 +253,7 @@ void Renderer::Init() {
 void Renderer::DestroyViewportTargets() {
     m_Pending.clear();  // (its targets go; tri_destroy / tri_group_destroy wait for their streams)
     DropHistories();    // (each waits for its last pass; the new targets' first frames have no history)
+    DropTaa();          // (likewise)
     tri_recorder_destroy(m_Recorder);  // (waits for its captures; the next recorded DrawFrame makes a new one)
     m_Recorder = nullptr;
     DropGrab();  // (likewise; the next captured DrawFrame makes a new one)
@@ -457,6 +458,11 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         if (any) LogError("SetDeviceCount", "multi-device viewports have no history reprojection: it was turned off");
         DropHistories();
         m_Reprojection.clear();
+        any = false;
+        for (auto& it : m_Taa) any |= it.second.m_Enabled;
+        if (any) LogError("SetDeviceCount", "multi-device viewports have no temporal anti-aliasing: it was turned off");
+        DropTaa();
+        m_Taa.clear();
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
@@ -1475,8 +1481,17 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         UpdateUniformBuffer(GetActiveCamera(vc), ubo);
         if (!SetTargetText(vc, id)) LogError("DrawFrame", "the text overlay of this frame is missing");
         if (!SetTargetIds(vc, id, draws, drawEntities)) LogError("DrawFrame", "the entity ids of this frame are missing");
-        if (!SetTargetMotion(vc, id, ubo, draws, drawEntities)) LogError("DrawFrame", "the motion vectors of this frame are missing");
-        if (!SubmitTarget(vc, TargetUniforms(vc, ubo), draws, shadow, shadowOn)) return;
+        // temporal anti-aliasing: the frame is rendered under this frame's jitter, the motion history keeps the
+        // unjittered block and hands the previous projection on under the same jitter
+        float jitter[2] = {0.0f, 0.0f};
+        const bool jittered = BeginTaaFrame(vc, id, jitter);
+        if (!SetTargetMotion(vc, id, ubo, draws, drawEntities, jittered ? jitter : nullptr))
+            LogError("DrawFrame", "the motion vectors of this frame are missing");
+        tri_global_ubo shown = ubo;
+        if (jittered && tri_taa_jitter_projection(ubo.projection, jitter[0], jitter[1], vc.m_Width, vc.m_Height, shown.projection) != TRI_OK)
+            LogError("temporal anti-aliasing", tri_last_error());
+        if (!SubmitTarget(vc, TargetUniforms(vc, shown), draws, shadow, shadowOn)) return;
+        if (!ResolveTarget(vc, id, false)) LogError("DrawFrame", "the temporal anti-aliasing of this frame is missing");
         if (!ReprojectTarget(vc, id, false)) LogError("DrawFrame", "the history reprojection of this frame is missing");
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
@@ -1528,8 +1543,7 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
     pf.m_Grabbed = grabbed;
     pf.m_GrabGeneration = m_GrabGeneration;
     if (primaryActive && m_PresentWidth && m_PresentHeight) {
-        const Target t{activeTarget->m_Ctx, activeTarget->m_Group};
-        if (t.Blit(m_PresentWidth, m_PresentHeight) == TRI_OK) {
+        if (PresentBlit(*activeTarget, m_PresentWidth, m_PresentHeight) == TRI_OK) {
             pf.m_Blit = activeTarget;
             pf.m_BlitWidth = m_PresentWidth;
             pf.m_BlitHeight = m_PresentHeight;
@@ -1569,7 +1583,8 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
             rerendered = true;
         }
         if (rc != TRI_OK) LogError("frame fence", tri_last_error());
-        if (rc == TRI_OK && rerendered) RedoReprojection(*vc);  // the pass behind the first render read an incomplete frame
+        if (rc == TRI_OK && rerendered) RedoTaa(*vc);           // the passes behind the first render read an incomplete frame
+        if (rc == TRI_OK && rerendered) RedoReprojection(*vc);
         if (rc == TRI_OK) vc->m_HasImage = t.Output(&vc->m_Image) == TRI_OK;  // a re-render moves a group's buffer
         if (vc == p.m_Legacy && rc == TRI_OK) {
             m_PresentSource = vc->m_Ctx;
@@ -1596,7 +1611,7 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
             ResolveReadbackFrame(*vc, p.m_RecordSlot, rc == TRI_OK, rerendered);
         if (vc == p.m_Blit && rc != TRI_OK) p.m_Blit = nullptr;
         if (vc == p.m_Blit && rerendered) {  // (the first wait covered the blit behind the pass: same stream)
-            if (t.Blit(p.m_BlitWidth, p.m_BlitHeight) != TRI_OK || t.Sync() != TRI_OK) {
+            if (PresentBlit(*vc, p.m_BlitWidth, p.m_BlitHeight) != TRI_OK || t.Sync() != TRI_OK) {
                 LogError("present blit", tri_last_error());
                 p.m_Blit = nullptr;
             }
@@ -2282,7 +2297,7 @@ bool Renderer::IsMotionVectorOutputEnabled(uint32_t viewportId) const {
 // The output is context state that stays set, so only changes are sent (ring targets are separate contexts: each is
 // brought up to date when its turn comes). The history is the viewport's, whichever target rendered its last frame.
 bool Renderer::SetTargetMotion(ViewportContext& vc, uint32_t viewportId, const tri_global_ubo& ubo,
-                               const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities) {
+                               const std::vector<tri_draw>& draws, const std::vector<ECS::Entity>& entities, const float* jitter) {
     const bool want = vc.m_Ctx && vc.m_IdOutput && WantsMotion(viewportId);
     if (vc.m_Ctx && want != vc.m_MotionOutput) {
         if (tri_set_motion_output(vc.m_Ctx, want ? 1 : 0) != TRI_OK || (want && tri_get_motion_output(vc.m_Ctx, &vc.m_MotionImage) != TRI_OK)) {
@@ -2303,6 +2318,9 @@ bool Renderer::SetTargetMotion(ViewportContext& vc, uint32_t viewportId, const t
         tri_motion_history mh{};
         std::memcpy(mh.prev_view, h.m_View, sizeof mh.prev_view);
         std::memcpy(mh.prev_projection, h.m_Projection, sizeof mh.prev_projection);
+        // under temporal anti-aliasing: the previous unjittered projection under the CURRENT jitter
+        if (jitter && tri_taa_jitter_projection(h.m_Projection, jitter[0], jitter[1], vc.m_Width, vc.m_Height, mh.prev_projection) != TRI_OK)
+            LogError("temporal anti-aliasing", tri_last_error());
         std::vector<float> prev((size_t)n * 16);
         for (uint32_t d = 0; d < n; ++d) {  // an entity the last frame did not draw keeps its current model
             auto it = h.m_Models.find(entities[d]);
@@ -2458,6 +2476,161 @@ void* Renderer::GetViewportReprojectedTexture(uint32_t viewportId) {
 void* Renderer::GetViewportDisocclusionTexture(uint32_t viewportId) {
     Reprojection* st = ReprojectionOutput(viewportId);
     return st ? &st->m_Mask : nullptr;
+}
+
+// ---- temporal anti-aliasing -----------------------------------------------------------------------------------------
+void Renderer::SetTemporalAntiAliasingEnabled(uint32_t viewportId, bool enabled, float alpha, uint32_t period, bool rejectIds) {
+    if (enabled && m_Devices.size() > 1) {
+        LogError("temporal anti-aliasing", "multi-device viewports (SetDeviceCount > 1) have no temporal anti-aliasing");
+        return;
+    }
+    if (enabled && !(alpha > 0.0f && alpha <= 1.0f)) {
+        LogError("temporal anti-aliasing", "alpha lies outside (0, 1]");
+        return;
+    }
+    if (enabled && period > 64) {
+        LogError("temporal anti-aliasing", "the jitter period is above 64");
+        return;
+    }
+    Taa& st = m_Taa[viewportId];
+    if (enabled && !st.m_Enabled) {  // switching on: frames rendered meanwhile were not accumulated
+        if (st.m_Object && tri_taa_reset(st.m_Object) != TRI_OK) LogError("temporal anti-aliasing", tri_last_error());
+        st.m_FrameIndex = 0;
+    }
+    if (!enabled) st.m_LastTarget = nullptr;  // the readers and the present answer for resolved frames only
+    st.m_Enabled = enabled;
+    st.m_Alpha = alpha;
+    st.m_Period = period;
+    st.m_RejectIds = rejectIds;
+}
+
+bool Renderer::IsTemporalAntiAliasingEnabled(uint32_t viewportId) const {
+    auto it = m_Taa.find(viewportId);
+    return it != m_Taa.end() && it->second.m_Enabled;
+}
+
+void Renderer::DropTaa() {
+    for (auto& it : m_Taa) {
+        tri_taa_destroy(it.second.m_Object);  // (waits for its last pass)
+        it.second.m_Object = nullptr;
+        it.second.m_LastTarget = nullptr;
+        it.second.m_FrameIndex = 0;
+    }
+}
+
+bool Renderer::BeginTaaFrame(const ViewportContext& vc, uint32_t viewportId, float jitter[2]) {
+    auto it = m_Taa.find(viewportId);
+    if (it == m_Taa.end() || !it->second.m_Enabled || !vc.m_Ctx) return false;
+    Taa& st = it->second;
+    if (st.m_Width != vc.m_Width || st.m_Height != vc.m_Height) {  // the first frame, or a resize: the count restarts
+        st.m_FrameIndex = 0;
+        st.m_Width = vc.m_Width;
+        st.m_Height = vc.m_Height;
+    }
+    if (tri_taa_jitter(st.m_FrameIndex, st.m_Period, jitter) != TRI_OK) {
+        LogError("temporal anti-aliasing", tri_last_error());
+        return false;
+    }
+    ++st.m_FrameIndex;
+    return true;
+}
+
+// One tri_taa per viewport, whichever of its targets renders the frame, like the history reprojection's object.
+bool Renderer::ResolveTarget(ViewportContext& vc, uint32_t viewportId, bool redo) {
+    auto it = m_Taa.find(viewportId);
+    if (it == m_Taa.end() || !it->second.m_Enabled) return true;
+    Taa& st = it->second;
+    st.m_LastTarget = nullptr;
+    if (!vc.m_Ctx || !vc.m_MotionOutput) return false;
+    if (st.m_Object && (st.m_ObjectWidth != vc.m_Width || st.m_ObjectHeight != vc.m_Height)) {  // a resize: a new object, no history
+        tri_taa_destroy(st.m_Object);
+        st.m_Object = nullptr;
+    }
+    if (!st.m_Object) {
+        tri_image img{};
+        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK || tri_taa_create(img.device, vc.m_Width, vc.m_Height, &st.m_Object) != TRI_OK) {
+            LogError("temporal anti-aliasing", tri_last_error());
+            st.m_Object = nullptr;
+            return false;
+        }
+        st.m_ObjectWidth = vc.m_Width;
+        st.m_ObjectHeight = vc.m_Height;
+    }
+    tri_taa_params params{};
+    params.alpha = st.m_Alpha;
+    params.flags = (redo ? TRI_TAA_REDO : 0u) | (st.m_RejectIds ? TRI_TAA_REJECT_ID : 0u);
+    if (tri_taa_resolve(st.m_Object, vc.m_Ctx, &params) != TRI_OK ||
+        tri_taa_get_output(st.m_Object, &st.m_Resolved, nullptr, nullptr) != TRI_OK) {
+        LogError("temporal anti-aliasing", tri_last_error());
+        return false;
+    }
+    st.m_LastTarget = &vc;
+    return true;
+}
+
+// As RedoReprojection: a redo pass when the target's pass was the object's last, else (a later frame has already been
+// accumulated over the incomplete one) a reset.
+void Renderer::RedoTaa(ViewportContext& vc) {
+    auto it = m_Taa.find(vc.m_Info.ViewportID);
+    if (it == m_Taa.end() || !it->second.m_Enabled || !it->second.m_Object || &vc == &m_LegacyTarget) return;
+    Taa& st = it->second;
+    if (st.m_LastTarget == &vc) {
+        if (ResolveTarget(vc, vc.m_Info.ViewportID, true)) {
+            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError("temporal anti-aliasing", tri_last_error());
+        }
+    } else if (tri_taa_reset(st.m_Object) != TRI_OK) {
+        LogError("temporal anti-aliasing", tri_last_error());
+    }
+}
+
+int Renderer::PresentBlit(ViewportContext& vc, uint32_t width, uint32_t height) {
+    auto it = m_Taa.find(vc.m_Info.ViewportID);
+    if (it != m_Taa.end() && it->second.m_Enabled && it->second.m_Object && it->second.m_LastTarget == &vc && vc.m_Ctx &&
+        &vc != &m_LegacyTarget)
+        return tri_taa_blit_linear(it->second.m_Object, vc.m_Ctx, nullptr, width, height);
+    return Target{vc.m_Ctx, vc.m_Group}.Blit(width, height);
+}
+
+Renderer::Taa* Renderer::TaaOutput(uint32_t viewportId) {
+    FinishFrame();
+    auto it = m_Taa.find(viewportId);
+    if (it == m_Taa.end() || !it->second.m_Object || !it->second.m_LastTarget) return nullptr;
+    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame was not resolved
+    return &it->second;
+}
+
+bool Renderer::ReadViewportResolvedPixels(uint32_t viewportId, std::vector<uint8_t>& rgba) {
+    Taa* st = TaaOutput(viewportId);
+    if (!st) return false;
+    std::vector<uint8_t> bgra((size_t)st->m_ObjectWidth * st->m_ObjectHeight * 4);
+    if (tri_taa_read(st->m_Object, bgra.data(), nullptr, nullptr) != TRI_OK) {
+        LogError("temporal anti-aliasing", tri_last_error());
+        return false;
+    }
+    rgba.resize(bgra.size());
+    for (size_t i = 0; i < bgra.size(); i += 4) {  // BGRA -> RGBA, as ReadViewportPixels
+        rgba[i + 0] = bgra[i + 2];
+        rgba[i + 1] = bgra[i + 1];
+        rgba[i + 2] = bgra[i + 0];
+        rgba[i + 3] = bgra[i + 3];
+    }
+    return true;
+}
+
+bool Renderer::ReadViewportTaaMask(uint32_t viewportId, std::vector<uint8_t>& mask) {
+    Taa* st = TaaOutput(viewportId);
+    if (!st) return false;
+    mask.resize((size_t)st->m_ObjectWidth * st->m_ObjectHeight);
+    if (tri_taa_read(st->m_Object, nullptr, nullptr, mask.data()) != TRI_OK) {
+        LogError("temporal anti-aliasing", tri_last_error());
+        return false;
+    }
+    return true;
+}
+
+void* Renderer::GetViewportResolvedTexture(uint32_t viewportId) {
+    Taa* st = TaaOutput(viewportId);
+    return st ? &st->m_Resolved : nullptr;
 }
 
 void* Renderer::GetViewportTexture(uint32_t viewportId) const {

@@ -750,6 +750,51 @@ int trident_app_reprojection_textures(trident_app* app, uint32_t viewport_id, tr
     });
 }
 
+int trident_app_set_temporal_anti_aliasing(trident_app* app, uint32_t viewport_id, int enabled, float alpha, uint32_t period,
+                                           int reject_ids) {
+    return Guard(app, [&] {
+        app->renderer.SetTemporalAntiAliasingEnabled(viewport_id, enabled != 0, alpha, period, reject_ids != 0);
+        // (a refused request leaves the switch as it was: on, perhaps, with its earlier values)
+        if (enabled && (!(alpha > 0.0f && alpha <= 1.0f) || period > 64)) return TRI_E_STATE;
+        return app->renderer.IsTemporalAntiAliasingEnabled(viewport_id) == (enabled != 0) ? TRI_OK : TRI_E_STATE;
+    });
+}
+
+int trident_app_is_temporal_anti_aliasing(trident_app* app, uint32_t viewport_id, int* enabled) {
+    return Guard(app, [&] {
+        if (!enabled) return TRI_E_INVALID;
+        *enabled = app->renderer.IsTemporalAntiAliasingEnabled(viewport_id) ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_read_resolved(trident_app* app, uint32_t viewport_id, uint8_t* rgba, uint8_t* mask, uint64_t capacity) {
+    return Guard(app, [&] {
+        std::vector<uint8_t> c, m;
+        if (rgba) {
+            if (!app->renderer.ReadViewportResolvedPixels(viewport_id, c)) return TRI_E_STATE;
+            if (c.size() / 4 > capacity) return TRI_E_INVALID;
+            std::memcpy(rgba, c.data(), c.size());
+        }
+        if (mask) {
+            if (!app->renderer.ReadViewportTaaMask(viewport_id, m)) return TRI_E_STATE;
+            if (m.size() > capacity) return TRI_E_INVALID;
+            std::memcpy(mask, m.data(), m.size());
+        }
+        return TRI_OK;
+    });
+}
+
+int trident_app_resolved_texture(trident_app* app, uint32_t viewport_id, tri_image* out) {
+    return Guard(app, [&] {
+        if (!out) return TRI_E_INVALID;
+        const void* c = app->renderer.GetViewportResolvedTexture(viewport_id);
+        if (!c) return TRI_E_STATE;
+        *out = *static_cast<const tri_image*>(c);
+        return TRI_OK;
+    });
+}
+
 struct trident_font {
     TextRenderer text;
 };

@@ -245,6 +245,19 @@ class TriReprojectParams(C.Structure):
 assert C.sizeof(TriReprojectParams) == 16
 
 
+# temporal anti-aliasing (include/tri_raster.h): the accumulated colour's format, the mask bits, the flags, the parameters
+TRI_FORMAT_R16G16B16A16_UNORM = 91
+TRI_TAA_NO_HISTORY, TRI_TAA_NO_PROJ, TRI_TAA_OUTSIDE, TRI_TAA_ID, TRI_TAA_CLAMPED = 1, 2, 4, 8, 32
+TRI_TAA_REDO, TRI_TAA_REJECT_ID = 1, 2
+
+
+class TriTaaParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(TriTaaParams) == 16
+
+
 class TriGroupConfig(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -511,6 +524,17 @@ CABI_FUNCTIONS = [
     ("tri_history_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     ("tri_history_get_output", C.c_int, [C.c_void_p, C.POINTER(TriImage), C.POINTER(TriImage)]),
     ("tri_history_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("tri_taa_jitter", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_float * 2)]),
+    ("tri_taa_jitter_projection", C.c_int, [C.POINTER(C.c_float * 16), C.c_float, C.c_float, C.c_uint32, C.c_uint32,
+                                            C.POINTER(C.c_float * 16)]),
+    ("tri_taa_create", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_taa_destroy", C.c_int, [C.c_void_p]),
+    ("tri_taa_resolve", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TriTaaParams)]),
+    ("tri_taa_reset", C.c_int, [C.c_void_p]),
+    ("tri_taa_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("tri_taa_get_output", C.c_int, [C.c_void_p, C.POINTER(TriImage), C.POINTER(TriImage), C.POINTER(TriImage)]),
+    ("tri_taa_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("tri_taa_blit_linear", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
 ]
 
 

@@ -132,6 +132,10 @@ _APP_FUNCTIONS = [
     ("trident_app_set_history_reprojection", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_float]),
     ("trident_app_read_reprojection", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("trident_app_reprojection_textures", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage), C.POINTER(abi.TriImage)]),
+    ("trident_app_set_temporal_anti_aliasing", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_uint32, C.c_int]),
+    ("trident_app_is_temporal_anti_aliasing", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    ("trident_app_read_resolved", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("trident_app_resolved_texture", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage)]),
     ("trident_app_submit_text", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4),
                                           C.c_char_p, C.c_uint32]),
     ("trident_app_set_font", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
@@ -518,6 +522,42 @@ class TridentApp:
             return None
         _check(rc, "reprojection_textures")
         return col, mask
+
+    # ---- temporal anti-aliasing ----
+    def set_temporal_anti_aliasing(self, viewport_id, enabled=True, alpha=0.1, period=8, reject_ids=True):
+        """Renderer::SetTemporalAntiAliasingEnabled; False where the renderer refuses it (SetDeviceCount > 1, a bad alpha
+        or period)."""
+        rc = self._lib.trident_app_set_temporal_anti_aliasing(self._h, viewport_id, 1 if enabled else 0, alpha, period,
+                                                              1 if reject_ids else 0)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_temporal_anti_aliasing")
+        return rc == abi.TRI_OK
+
+    def is_temporal_anti_aliasing(self, viewport_id):
+        """Renderer::IsTemporalAntiAliasingEnabled."""
+        on = C.c_int()
+        _check(self._lib.trident_app_is_temporal_anti_aliasing(self._h, viewport_id, C.byref(on)), "is_temporal_anti_aliasing")
+        return bool(on.value)
+
+    def read_resolved(self, viewport_id, width, height):
+        """Renderer::ReadViewportResolvedPixels and ReadViewportTaaMask: (resolved uint8 [height, width, 4] R G B A, mask
+        uint8 [height, width]), or None where they return false."""
+        col = np.zeros((height, width, 4), np.uint8)
+        mask = np.zeros((height, width), np.uint8)
+        rc = self._lib.trident_app_read_resolved(self._h, viewport_id, col.ctypes.data, mask.ctypes.data, mask.size)
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "read_resolved")
+        return col, mask
+
+    def resolved_texture(self, viewport_id):
+        """Renderer::GetViewportResolvedTexture: an abi.TriImage handle, or None."""
+        img = abi.TriImage()
+        rc = self._lib.trident_app_resolved_texture(self._h, viewport_id, C.byref(img))
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "resolved_texture")
+        return img
 
     def set_font(self, path, pixel_height=32.0):
         """Renderer::SetTextFont; returns its bool."""

@@ -456,6 +456,89 @@ class TriHistory:
         return ms.value, n.value
 
 
+def taa_jitter(index, period):
+    """tri_taa_jitter (host-only): the sub-pixel offset of frame `index`, (x, y) in pixels as float32."""
+    lib = load_library()
+    xy = (C.c_float * 2)()
+    _check(lib.tri_taa_jitter(index, period, C.byref(xy)))
+    return np.float32(xy[0]), np.float32(xy[1])
+
+
+def taa_jitter_projection(projection, jx, jy, width, height):
+    """tri_taa_jitter_projection (host-only): the column-major projection (16 floats, any shape) with every projected
+    point moved by (jx, jy) pixels; float32 [16]."""
+    lib = load_library()
+    src = (C.c_float * 16)(*np.asarray(projection, np.float32).reshape(16).tolist())
+    out = (C.c_float * 16)()
+    _check(lib.tri_taa_jitter_projection(C.byref(src), jx, jy, width, height, C.byref(out)))
+    return np.array(out[:], dtype=np.float32)
+
+
+class TriTaa:
+    """tri_taa: the accumulated colour of one view (16-bit) outside any context, and the pass that resolves a jittered
+    frame over it."""
+
+    def __init__(self, width, height, device=-1):
+        lib = load_library()
+        h = C.c_void_p()
+        _check(lib.tri_taa_create(device, width, height, C.byref(h)))
+        self._h = h
+        self.width, self.height = width, height
+
+    def close(self):
+        if self._h:
+            _lib.tri_taa_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def resolve(self, raster, alpha=0.1, reject_ids=True, redo=False, flags=None):
+        """tri_taa_resolve behind the raster's last render (asynchronous). flags overrides the two switches' bits (for
+        the error cases)."""
+        bits = (abi.TRI_TAA_REDO if redo else 0) | (abi.TRI_TAA_REJECT_ID if reject_ids else 0)
+        p = abi.TriTaaParams(float(alpha), bits if flags is None else flags)
+        _check(_lib.tri_taa_resolve(self._h, raster._ctx, C.byref(p)))
+
+    def reset(self):
+        _check(_lib.tri_taa_reset(self._h))
+
+    def read(self):
+        """tri_taa_read: (resolved uint8 [H, W, 4] B G R A, accumulated uint16 [H, W, 4] B G R A, mask uint8 [H, W])."""
+        col = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        acc = np.empty((self.height, self.width, 4), dtype=np.uint16)
+        mask = np.empty((self.height, self.width), dtype=np.uint8)
+        _check(_lib.tri_taa_read(self._h, _ptr(col), _ptr(acc), _ptr(mask)))
+        return col, acc, mask
+
+    def images(self):
+        """tri_taa_get_output: (resolved, accumulated, mask) as abi.TriImage."""
+        col, acc, mask = abi.TriImage(), abi.TriImage(), abi.TriImage()
+        _check(_lib.tri_taa_get_output(self._h, C.byref(col), C.byref(acc), C.byref(mask)))
+        return col, acc, mask
+
+    def timing(self):
+        """tri_taa_get_timing: (summed ms of the stamped passes, their number)."""
+        ms, n = C.c_double(), C.c_uint64()
+        _check(_lib.tri_taa_get_timing(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def blit(self, raster, width, height, dst_ptr=None):
+        """tri_taa_blit_linear: the resolved image scaled to width x height into dst_ptr, or into the raster's present
+        image (TriRaster.read_present)."""
+        _check(_lib.tri_taa_blit_linear(self._h, raster._ctx, C.c_void_p(dst_ptr) if dst_ptr else None, width, height))
+        raster._present = None if dst_ptr else (width, height)
+
+
 def _pick_rect(call, x0, y0, x1, y1, draw_count):
     words = max((int(draw_count) + 31) // 32, 1)
     bits = np.zeros(words, dtype=np.uint32)

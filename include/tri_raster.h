@@ -958,6 +958,99 @@ int tri_history_get_output(tri_history* history, tri_image* colour, tri_image* m
  * untouched: the pass runs behind the frame's last stamp. */
 int tri_history_get_timing(tri_history* history, double* ms, uint64_t* passes);
 
+/* ---- temporal anti-aliasing: jittered frames resolved over clamped, accumulated history -------- */
+/* The raster samples a pixel once, at its centre. A caller who moves that sample inside the pixel from frame to frame
+ * (tri_taa_jitter, tri_taa_jitter_projection) and accumulates the frames gets the pixel's area instead. A tri_taa keeps
+ * the accumulated colour of one view — 16-bit UNORM, so that a weight of 0.1 still moves it by one step — and the ids
+ * it was accumulated under, twice, outside any context like a tri_history. After a tri_render with the motion output
+ * on, tri_taa_resolve enqueues k_taa_resolve on the context's stream: per pixel it fetches the accumulated history where
+ * the motion table says the surface lay, clamps it to the range of the current frame's 3 x 3 neighbourhood (stale
+ * history cannot ghost), mixes the current colour in with weight alpha, and stores the sum as the next history and,
+ * rounded to 8 bits, as the resolved image. No kernel of the frame changes; the context's colour, depth, ids and motion
+ * are bit-identical with and without the pass.
+ * The rule, for pixel p = (x, y) with current colour c (4 bytes, B G R A), id i and depth d, R the row of the motion
+ * table tri_render staged for i, A' the previous accumulated colour (four uint16 per pixel, B G R A), I' the previous
+ * ids and W x H the frame; integers and float32, no multiply-add contracted, in exactly this order:
+ *     u, v, proj, inside, xi, yi and the four taps with fu, fv      exactly as under "history reprojection"
+ *     TRI_TAA_NO_HISTORY  the object holds no previous frame; the mask is then exactly 1 on every pixel
+ *     TRI_TAA_NO_PROJ     !proj                      TRI_TAA_OUTSIDE     proj && !inside
+ *     TRI_TAA_ID          with TRI_TAA_REJECT_ID, inside, and none of I'[clamp(yi + dy, 0, H - 1)][clamp(xi + dx, 0, W - 1)],
+ *                         dx, dy in {-1, 0, 1}, equals i. (A 3 x 3 test on purpose: under jitter a silhouette moves by up
+ *                         to half a pixel between frames, and a nearest-pixel test would reject exactly the pixels that
+ *                         need accumulating. There is no depth test: a slope's depth changes under jitter.)
+ *     lo, hi = per channel, as bytes, the min and max of c over (clamp(x + dx, 0, W - 1), clamp(y + dy, 0, H - 1))
+ *     cur16 = (float)(c_ch * 257)     lo16 = (float)(lo * 257)     hi16 = (float)(hi * 257)
+ *     valid = (mask & 15) == 0
+ *     valid:    t = c00 * (1.0f - fu) + c10 * fu,  b = c01 * (1.0f - fu) + c11 * fu,  h = t * (1.0f - fv) + b * fv
+ *               over the taps of A' (not rounded);  hc = fminf(fmaxf(h, lo16), hi16)
+ *               TRI_TAA_CLAMPED iff hc != h in any channel
+ *               r = hc * (1.0f - alpha) + cur16 * alpha;  s = min((int)(r + 0.5f), 65535)
+ *               out8 = min((int)((float)s * (1.0f / 257.0f) + 0.5f), 255)
+ *     invalid:  s = c_ch * 257,  out8 = c_ch       (the history restarts from the current frame)
+ *     stored:   A[p] = s, I[p] = i, resolved[p] = out8 (B8G8R8A8), mask[p]
+ * All four channels follow the same rule. The colour is read as the context holds it when the call is enqueued: after
+ * the selection outline and the text overlay. One host thread per object.
+ *
+ * The jitter contract. Frame n is rendered with tri_taa_jitter_projection(P_n, j_n) in the uniform block, and
+ * tri_set_motion_history is given the previous view with tri_taa_jitter_projection(P_{n-1}, j_n) as prev_projection:
+ * the previous UNJITTERED projection under the CURRENT jitter. The staged table then maps a pixel to the place its
+ * surface had in the unjittered history plus j_n — where the accumulated history, which is registered to the
+ * unjittered frame, must be sampled. For a still camera and scene the two matrices are bitwise equal, the row is the
+ * exact identity, the history tap is the pixel itself and nothing blurs. */
+#define TRI_FORMAT_R16G16B16A16_UNORM 91u /* VK_FORMAT_R16G16B16A16_UNORM: tri_image.format of the accumulated colour */
+#define TRI_TAA_NO_HISTORY 1u
+#define TRI_TAA_NO_PROJ 2u
+#define TRI_TAA_OUTSIDE 4u
+#define TRI_TAA_ID 8u
+#define TRI_TAA_CLAMPED 32u
+#define TRI_TAA_REDO 1u      /* tri_taa_params.flags: the frame of the last call, rendered again */
+#define TRI_TAA_REJECT_ID 2u /* ... the 3 x 3 id test */
+typedef struct tri_taa tri_taa;
+typedef struct tri_taa_params {
+    float alpha;    /* the current frame's weight, 0 < alpha <= 1 (1: the resolved image is the current frame) */
+    uint32_t flags; /* TRI_TAA_REDO | TRI_TAA_REJECT_ID */
+    uint32_t reserved[2];
+} tri_taa_params;
+/* The sub-pixel offset of frame `index`, in pixels: with k = index % period + 1,
+ * xy = (radical_inverse_2(k) - 0.5, radical_inverse_3(k) - 0.5), computed in double and rounded once (the Halton
+ * sequence, centred). period == 0 gives (0, 0). Host only. TRI_E_INVALID for a null xy or a period above 64. */
+int tri_taa_jitter(uint32_t index, uint32_t period, float xy[2]);
+/* proj with every projected point moved by exactly (+jx, +jy) pixels of a width x height frame (x right, y down, the
+ * pixel convention of "motion vectors"), perspective and orthographic alike: with dx = 2 jx / width, dy = 2 jy / height
+ * in double, out[4c + 0] = proj[4c + 0] + dx * proj[4c + 3] and out[4c + 1] = proj[4c + 1] + dy * proj[4c + 3] for every
+ * column c, rounded once; rows 2 and 3 are copied bitwise, so depth is untouched. out may be proj. Host only.
+ * TRI_E_INVALID for a null pointer or a zero extent. */
+int tri_taa_jitter_projection(const float proj[16], float jx, float jy, uint32_t width, uint32_t height, float out[16]);
+/* Two sets of {accumulated colour 8 B, ids 4 B} per pixel, the resolved image (4 B), the mask (1 B) and the object's
+ * events, on one device (-1 = current). TRI_E_INVALID for a zero extent or more than 2^31 pixels, before any device is
+ * touched. tri_taa_destroy waits for the last pass; NULL is TRI_OK. */
+int tri_taa_create(int32_t device, uint32_t width, uint32_t height, tri_taa** out);
+int tri_taa_destroy(tri_taa* taa);
+/* Asynchronous, on the context's stream behind the tri_render whose frame it reads (and behind the object's previous
+ * pass, which may have run on another context's stream). The sets swap and TRI_TAA_REDO works as tri_history_reproject's
+ * do. TRI_E_INVALID: a null argument, a context on another device or of another extent, an alpha outside (0, 1] or not
+ * finite, unknown flag bits. TRI_E_UNSUPPORTED: a row-band context. TRI_E_STATE: the context's motion output is off, or
+ * no frame has been rendered with it. Every check comes before the device is made current. Stamped like
+ * tri_history_reproject while a timed frame is wanted of the context. */
+int tri_taa_resolve(tri_taa* taa, tri_ctx* ctx, const tri_taa_params* params);
+/* Forget the accumulated frame: the next call reports TRI_TAA_NO_HISTORY everywhere (and a redo is a plain call). */
+int tri_taa_reset(tri_taa* taa);
+/* The last pass's resolved image (width x height x 4 bytes, B G R A), accumulated colour (width x height x 4 uint16,
+ * B G R A) and mask (width x height bytes), tightly packed; any pointer may be NULL. Waits for the pass. TRI_E_STATE
+ * before the first pass. */
+int tri_taa_read(tri_taa* taa, uint8_t* bgra8, uint16_t* rgba16, uint8_t* mask);
+/* The three images in device memory: the resolved colour (TRI_FORMAT_B8G8R8A8_UNORM, pitch width * 4), the accumulated
+ * colour the last pass wrote (TRI_FORMAT_R16G16B16A16_UNORM, pitch width * 8; it changes sets from pass to pass, so ask
+ * after each), the mask (TRI_FORMAT_R8_UINT, pitch width). Any pointer may be NULL. TRI_E_STATE before the first pass. */
+int tri_taa_get_output(tri_taa* taa, tri_image* colour8, tri_image* colour16, tri_image* mask);
+/* As tri_history_get_timing. */
+int tri_taa_get_timing(tri_taa* taa, double* ms, uint64_t* passes);
+/* tri_blit_linear's rule over the resolved image instead of the context's colour: the presentation blit into dst
+ * (width x height B8G8R8A8; NULL: the context's present image, read by tri_read_present), on the context's stream
+ * behind the object's last pass. TRI_E_INVALID: a null object or context, a bad destination extent, another device or
+ * extent; TRI_E_STATE: a row-band context, or no pass has run. */
+int tri_taa_blit_linear(tri_taa* taa, tri_ctx* ctx, void* dst, uint32_t width, uint32_t height);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
@@ -1165,6 +1258,7 @@ static_assert(sizeof(tri_pick_result) == 16, "tri_pick_result layout");
 static_assert(sizeof(tri_outline) == 40, "tri_outline layout");
 static_assert(sizeof(tri_motion_history) == 144, "tri_motion_history layout");
 static_assert(sizeof(tri_reproject_params) == 16, "tri_reproject_params layout");
+static_assert(sizeof(tri_taa_params) == 16, "tri_taa_params layout");
 static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
 static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
 static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
