@@ -165,6 +165,28 @@ struct TriTaaArgs {
     uint32_t has_prev, reject_id;
 };
 hipError_t tri_launch_taa_resolve(const TriTaaArgs& args, hipStream_t stream);
+// The temporal upscaling pass's arguments (upscale_pass.hip), by value and alone like k_taa_resolve's: tri_upscale_resolve
+// enqueues k_upscale_resolve behind the frame. The context's planes and the previous ids are Wr x Hr, the object's
+// accumulated colour, resolved image and mask Wo x Ho; whole frames only. The context's planes are read four bytes at a
+// time and may start anywhere; the object's own come from hipMalloc. The frame's ids reach the written set through a
+// copy on the same stream, not through the kernel.
+struct TriUpscaleArgs {
+    TRI_G const uint32_t* colour;    // the frame just rendered, Wr x Hr: B8G8R8A8, ids, depth
+    TRI_G const uint32_t* ids;
+    TRI_G const float* depth;
+    TRI_G const float* table;        // (ndraws + 1) x 16: the motion table the frame staged
+    TRI_G const uint2* prev_acc;     // the stored history (not read when has_prev is 0): Wo x Ho, 4 x uint16 per pixel
+    TRI_G const uint32_t* prev_ids;  // ... and the ids it was accumulated under, Wr x Hr
+    TRI_G uint2* next_acc;           // the other set, Wo x Ho
+    TRI_G uint32_t* resolved;        // B8G8R8A8, Wo x Ho
+    TRI_G uint8_t* mask;             // one byte per output pixel
+    uint32_t Wr, Hr, Wo, Ho, ndraws;
+    float rx, ry, ox, oy;            // Wr / Wo, Hr / Ho, Wo / Wr, Ho / Hr (float32, from the host)
+    float sx, sy, hw, hh;            // 2 / Wo, 2 / Ho, Wo / 2, Ho / 2
+    float alpha, jx, jy;
+    uint32_t has_prev, reject_id;
+};
+hipError_t tri_launch_upscale_resolve(const TriUpscaleArgs& args, hipStream_t stream);
 // k_id_raster at the frame's bin size (id_pass.hip)
 const void* tri_id_raster_kernel(const TriFrameParams& fp);
 #ifdef TRI_DIAG_FRONT

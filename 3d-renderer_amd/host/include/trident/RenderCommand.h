@@ -81,6 +81,19 @@ public:
     }
     static bool ReadViewportTaaMask(uint32_t viewportId, std::vector<uint8_t>& mask) { return GetRenderer().ReadViewportTaaMask(viewportId, mask); }
     static void* GetViewportResolvedTexture(uint32_t viewportId) { return GetRenderer().GetViewportResolvedTexture(viewportId); }
+    static bool SetTemporalUpscalingEnabled(uint32_t viewportId, bool enabled, float renderScale = 0.5f, float alpha = 0.1f,
+                                            bool rejectIds = true) {
+        return GetRenderer().SetTemporalUpscalingEnabled(viewportId, enabled, renderScale, alpha, rejectIds);
+    }
+    static bool IsTemporalUpscalingEnabled(uint32_t viewportId) { return GetRenderer().IsTemporalUpscalingEnabled(viewportId); }
+    static bool ReadViewportUpscaledPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, uint32_t* width = nullptr,
+                                           uint32_t* height = nullptr) {
+        return GetRenderer().ReadViewportUpscaledPixels(viewportId, rgba, width, height);
+    }
+    static bool ReadViewportUpscaleMask(uint32_t viewportId, std::vector<uint8_t>& mask) {
+        return GetRenderer().ReadViewportUpscaleMask(viewportId, mask);
+    }
+    static void* GetViewportUpscaledTexture(uint32_t viewportId) { return GetRenderer().GetViewportUpscaledTexture(viewportId); }
     static FrameTimingStats GetFrameTimingStats() { return GetRenderer().GetFrameTimingStats(); }
     static size_t GetModelCount() { return GetRenderer().GetModelCount(); }
     static int32_t ResolveTextureSlot(const std::string& texturePath) { return GetRenderer().ResolveTextureSlot(texturePath); }

@@ -346,6 +346,38 @@ public:
     // the switch goes off; null where ReadViewportResolvedPixels returns false.
     void* GetViewportResolvedTexture(uint32_t viewportId);
 
+    // Temporal upscaling (tri_upscale): while it is on, the viewport's context is made at
+    // max(1, (uint32_t)(size * renderScale + 0.5f)) per axis, each DrawFrame renders it under
+    // tri_taa_jitter(frameIndex, tri_upscale_jitter_period(...)) over that RENDER extent (the motion history keeps the
+    // unjittered projection, as for temporal anti-aliasing) and resolves it over a history kept at the viewport's full
+    // size (weight alpha for a sample on a pixel's centre; rejectIds: the 3 x 3 entity test). The request turns the id
+    // and motion outputs on. One tri_upscale per VIEWPORT; a resize or another scale makes a new one and restarts the
+    // frame index; redo and reset as for temporal anti-aliasing. While it is on for the active viewport, the present
+    // blit and ReadPresentPixels show the UPSCALED image. ReadViewportPixels, GetViewportTexture, the id and motion
+    // readers, the AI tensor (TryAcquireRenderedFrame, GetFrameReadbackDeviceTensor; GetFrameReadbackExtent says its
+    // extent) and the dataset samples made from it keep the raw frame AT THE RENDER EXTENT; the readback's present-extent
+    // condition compares the viewport's size. PickEntity and PickEntitiesInRect keep taking viewport pixels. Text and the
+    // selection outline are drawn at the render extent (text positions scaled to it) and enlarged with the frame.
+    // A viewport is NOT recorded while it is upscaled: a recording session has one fixed extent, the viewport's size, so
+    // the request is refused on a viewport that is being recorded, and SetViewportRecordingEnabled is refused for a
+    // viewport that has it on.
+    // Refused with a log line, the switch staying as it was: a renderScale outside [1/3, 1] or one whose render extent
+    // breaks tri_upscale_create's extent rule for the viewport's size, an alpha outside (0, 1], a viewport with
+    // temporal anti-aliasing on (and SetTemporalAntiAliasingEnabled is refused while this is on), SetDeviceCount > 1
+    // (which also turns it off). Returns whether the request was taken.
+    bool SetTemporalUpscalingEnabled(uint32_t viewportId, bool enabled, float renderScale = 0.5f, float alpha = 0.1f,
+                                     bool rejectIds = true);
+    bool IsTemporalUpscalingEnabled(uint32_t viewportId) const;
+    // The viewport's full size: width * height * 4 bytes, R G B A, of its latest upscaled frame (fences); false for a
+    // viewport that does not exist or whose latest frame was not upscaled. width / height (may be null) get the extent.
+    bool ReadViewportUpscaledPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, uint32_t* width = nullptr,
+                                    uint32_t* height = nullptr);
+    // width * height mask bytes (TRI_UPSCALE_*) of the same frame.
+    bool ReadViewportUpscaleMask(uint32_t viewportId, std::vector<uint8_t>& mask);
+    // Opaque pointer to the tri_image of the upscaled colour (B8G8R8A8_UNORM), valid until the viewport is resized, the
+    // scale changes or the switch goes off; null where ReadViewportUpscaledPixels returns false.
+    void* GetViewportUpscaledTexture(uint32_t viewportId);
+
     // Frame readback (ResolvePendingReadback, Renderer.cpp:1299-1389): RGBA8 rows of the viewport
     // (BGRA reordered to RGBA), optionally the D32 depth.
     bool ReadViewportPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, std::vector<float>* depth = nullptr);
@@ -458,8 +490,20 @@ private:
     // temporal anti-aliasing
     bool WantsMotion(uint32_t viewportId) const {
         return IsMotionVectorOutputEnabled(viewportId) || IsHistoryReprojectionEnabled(viewportId) ||
-               IsTemporalAntiAliasingEnabled(viewportId);
+               IsTemporalAntiAliasingEnabled(viewportId) || IsTemporalUpscalingEnabled(viewportId);
     }
+    struct Upscale;
+    // the extent a viewport's context is made at: its size, scaled while temporal upscaling is on for it
+    void RenderExtent(const ViewportContext& target, uint32_t& width, uint32_t& height) const;
+    // a viewport pixel (PickEntity, PickEntitiesInRect) as a pixel of the target's frame
+    void ToFramePixel(const ViewportContext& target, int32_t& x, int32_t& y) const;
+    // before the target's tri_render: this frame's jitter of the viewport (false: the switch is off, no jitter)
+    bool BeginUpscaleFrame(const ViewportContext& target, uint32_t viewportId, float jitter[2]);
+    // behind the target's tri_render: the frame resolved over the viewport's full-size history
+    bool UpscaleTarget(ViewportContext& target, uint32_t viewportId, bool redo);
+    void RedoUpscale(ViewportContext& target);  // FinishOldestFrame re-rendered the target's frame
+    void DropUpscale();                         // with the targets (DestroyViewportTargets)
+    Upscale* UpscaleOutput(uint32_t viewportId);  // fenced; null unless the latest frame was upscaled
     struct Taa;
     // before the target's tri_render: this frame's jitter of the viewport (false: the switch is off, no jitter)
     bool BeginTaaFrame(const ViewportContext& target, uint32_t viewportId, float jitter[2]);
@@ -596,6 +640,19 @@ private:
         tri_image m_Resolved{};
     };
     std::map<uint32_t, Taa> m_Taa;
+    struct Upscale {  // SetTemporalUpscalingEnabled, by viewport id
+        bool m_Enabled = false;
+        float m_Scale = 0.5f, m_Alpha = 0.1f;
+        bool m_RejectIds = true;
+        tri_upscale* m_Object = nullptr;  // made at the viewport's first upscaled frame, again after a resize or a scale change
+        uint32_t m_RenderWidth = 0, m_RenderHeight = 0, m_OutWidth = 0, m_OutHeight = 0;  // the object's extents
+        uint32_t m_Width = 0, m_Height = 0;  // the render extent m_FrameIndex counts frames of
+        uint32_t m_FrameIndex = 0;           // the viewport's frames since the switch went on, the last resize or scale change
+        float m_Jitter[2] = {0.0f, 0.0f};    // of the frame being rendered (BeginUpscaleFrame)
+        const ViewportContext* m_LastTarget = nullptr;  // the target whose frame the last pass read
+        tri_image m_Resolved{};
+    };
+    std::map<uint32_t, Upscale> m_Upscale;
     std::map<uint32_t, ViewportContext> m_Viewports;
     ViewportInfo m_LastViewport{};
     uint32_t m_ActiveViewportId = 0;

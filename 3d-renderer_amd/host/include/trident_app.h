@@ -295,6 +295,19 @@ int trident_app_is_temporal_anti_aliasing(trident_app* app, uint32_t viewport_id
 int trident_app_read_resolved(trident_app* app, uint32_t viewport_id, uint8_t* rgba, uint8_t* mask, uint64_t capacity);
 /* Renderer::GetViewportResolvedTexture: copies the handle (TRI_E_STATE where it returns null). */
 int trident_app_resolved_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
+/* Renderer::SetTemporalUpscalingEnabled: from the viewport's next draw_frame on; TRI_E_STATE where the renderer refuses
+ * (SetDeviceCount > 1, a render scale outside [1/3, 1] or against the extent rule, an alpha outside (0, 1], temporal
+ * anti-aliasing on for the viewport). */
+int trident_app_set_temporal_upscaling(trident_app* app, uint32_t viewport_id, int enabled, float render_scale, float alpha,
+                                       int reject_ids);
+/* Renderer::IsTemporalUpscalingEnabled into *enabled. */
+int trident_app_is_temporal_upscaling(trident_app* app, uint32_t viewport_id, int* enabled);
+/* Renderer::ReadViewportUpscaledPixels (width * height * 4 bytes, R G B A, at the viewport's full size) and
+ * ReadViewportUpscaleMask (width * height bytes); either pointer may be NULL. TRI_E_STATE where they return false,
+ * TRI_E_INVALID when capacity (in pixels) is short. */
+int trident_app_read_upscaled(trident_app* app, uint32_t viewport_id, uint8_t* rgba, uint8_t* mask, uint64_t capacity);
+/* Renderer::GetViewportUpscaledTexture: copies the handle (TRI_E_STATE where it returns null). */
+int trident_app_upscaled_texture(trident_app* app, uint32_t viewport_id, tri_image* out);
 
 /* ---- text overlay ---- */
 /* Renderer::SubmitText: `bytes` bytes of UTF-8 (no terminator needed) at `position` (viewport pixels) in `color`

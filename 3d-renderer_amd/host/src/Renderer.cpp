@@ -254,6 +254,7 @@ void Renderer::DestroyViewportTargets() {
     m_Pending.clear();  // (its targets go; tri_destroy / tri_group_destroy wait for their streams)
     DropHistories();    // (each waits for its last pass; the new targets' first frames have no history)
     DropTaa();          // (likewise)
+    DropUpscale();      // (likewise)
     tri_recorder_destroy(m_Recorder);  // (waits for its captures; the next recorded DrawFrame makes a new one)
     m_Recorder = nullptr;
     DropGrab();  // (likewise; the next captured DrawFrame makes a new one)
@@ -326,6 +327,16 @@ bool Renderer::SetTextFont(const std::string& path, float pixelHeight) {
 bool Renderer::SetTargetText(ViewportContext& vc, uint32_t viewportId) {
     m_TextQuads.clear();
     m_TextRenderer.LayoutViewport(viewportId, m_TextQuads);
+    if (IsTemporalUpscalingEnabled(viewportId) && &vc != &m_LegacyTarget && vc.m_Info.Size.x > 0.0f && vc.m_Info.Size.y > 0.0f) {
+        // the context is smaller than the viewport the quads were laid out for: drawn there, enlarged with the frame
+        const float sx = (float)vc.m_Width / (float)(uint32_t)vc.m_Info.Size.x, sy = (float)vc.m_Height / (float)(uint32_t)vc.m_Info.Size.y;
+        for (tri_text_quad& q : m_TextQuads) {
+            q.x0 *= sx;
+            q.x1 *= sx;
+            q.y0 *= sy;
+            q.y1 *= sy;
+        }
+    }
     if (m_TextQuads.empty()) {
         const int rc = vc.m_Group ? tri_group_set_text(vc.m_Group, nullptr, nullptr, 0) : tri_set_text(vc.m_Ctx, nullptr, nullptr, 0);
         return rc == TRI_OK;
@@ -463,6 +474,11 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         if (any) LogError("SetDeviceCount", "multi-device viewports have no temporal anti-aliasing: it was turned off");
         DropTaa();
         m_Taa.clear();
+        any = false;
+        for (auto& it : m_Upscale) any |= it.second.m_Enabled;
+        if (any) LogError("SetDeviceCount", "multi-device viewports have no temporal upscaling: it was turned off");
+        DropUpscale();
+        m_Upscale.clear();
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
     m_Devices = devs;
@@ -1265,8 +1281,9 @@ std::vector<tri_mesh_range> Renderer::GetMeshRanges() const {
 }
 
 bool Renderer::PrepareViewport(ViewportContext& vc) {
-    const uint32_t w = (uint32_t)std::max(vc.m_Info.Size.x, 0.0f), h = (uint32_t)std::max(vc.m_Info.Size.y, 0.0f);
+    uint32_t w = (uint32_t)std::max(vc.m_Info.Size.x, 0.0f), h = (uint32_t)std::max(vc.m_Info.Size.y, 0.0f);
     if (w == 0 || h == 0) return false;
+    RenderExtent(vc, w, h);  // (smaller than the viewport while temporal upscaling is on for it)
     const bool multi = m_Devices.size() > 1;
     if ((vc.m_Ctx || vc.m_Group) && (vc.m_Width != w || vc.m_Height != h)) {  // CreateOrResizeOffscreenResources
         tri_destroy(vc.m_Ctx);
@@ -1484,7 +1501,8 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
         // temporal anti-aliasing: the frame is rendered under this frame's jitter, the motion history keeps the
         // unjittered block and hands the previous projection on under the same jitter
         float jitter[2] = {0.0f, 0.0f};
-        const bool jittered = BeginTaaFrame(vc, id, jitter);
+        // (temporal upscaling, exclusive with it on a viewport: the same contract over the smaller render extent)
+        const bool jittered = BeginTaaFrame(vc, id, jitter) || BeginUpscaleFrame(vc, id, jitter);
         if (!SetTargetMotion(vc, id, ubo, draws, drawEntities, jittered ? jitter : nullptr))
             LogError("DrawFrame", "the motion vectors of this frame are missing");
         tri_global_ubo shown = ubo;
@@ -1492,13 +1510,16 @@ void Renderer::DrawFrame() {  // Renderer.cpp:733-837
             LogError("temporal anti-aliasing", tri_last_error());
         if (!SubmitTarget(vc, TargetUniforms(vc, shown), draws, shadow, shadowOn)) return;
         if (!ResolveTarget(vc, id, false)) LogError("DrawFrame", "the temporal anti-aliasing of this frame is missing");
+        if (!UpscaleTarget(vc, id, false)) LogError("DrawFrame", "the temporal upscaling of this frame is missing");
         if (!ReprojectTarget(vc, id, false)) LogError("DrawFrame", "the history reprojection of this frame is missing");
         // recording: convert this frame on the device, behind its pass, into the slot of this frame in flight
         if (m_Recording && id == m_RecordingViewportId && CaptureRecordedFrame(vc, tix)) recorded = &vc;
         // AI readback: the active viewport's tensor, likewise, when the readback throttle has elapsed (ResolvePending-
         // Readback's interval, Renderer.cpp:1111-1140) and the viewport has the present extent (:5301-5337)
+        // (the viewport's size: under temporal upscaling the context is smaller, and the tensor is its raw frame)
+        const uint32_t viewW = (uint32_t)std::max(vc.m_Info.Size.x, 0.0f), viewH = (uint32_t)std::max(vc.m_Info.Size.y, 0.0f);
         if (m_AiReadback && id == m_ActiveViewportId && vc.m_Ctx &&
-            !(m_PresentWidth && m_PresentHeight && (m_PresentWidth != vc.m_Width || m_PresentHeight != vc.m_Height))) {
+            !(m_PresentWidth && m_PresentHeight && (m_PresentWidth != viewW || m_PresentHeight != viewH))) {
             const auto now = std::chrono::steady_clock::now();
             if (now >= m_NextAiReadbackTime && CaptureReadbackFrame(vc, tix)) {
                 m_NextAiReadbackTime = now + m_AiReadbackInterval;
@@ -1584,6 +1605,7 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
         }
         if (rc != TRI_OK) LogError("frame fence", tri_last_error());
         if (rc == TRI_OK && rerendered) RedoTaa(*vc);           // the passes behind the first render read an incomplete frame
+        if (rc == TRI_OK && rerendered) RedoUpscale(*vc);
         if (rc == TRI_OK && rerendered) RedoReprojection(*vc);
         if (rc == TRI_OK) vc->m_HasImage = t.Output(&vc->m_Image) == TRI_OK;  // a re-render moves a group's buffer
         if (vc == p.m_Legacy && rc == TRI_OK) {
@@ -1633,6 +1655,10 @@ bool Renderer::SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, ui
     if (!enabled) return true;
     if (m_Devices.size() > 1) {
         LogError("viewport recording", "multi-device viewports (SetDeviceCount > 1) are not recorded");
+        return false;
+    }
+    if (IsTemporalUpscalingEnabled(viewportId)) {  // (its context has the render extent, a session one fixed extent)
+        LogError("viewport recording", "the viewport has temporal upscaling on (SetTemporalUpscalingEnabled): not recorded");
         return false;
     }
     const uint32_t w = width + (width & 1u), h = height + (height & 1u);  // even planes, as the reference rounds
@@ -2221,8 +2247,19 @@ const Renderer::ViewportContext* Renderer::IdTarget(uint32_t viewportId) {
     return vc;
 }
 
+// A viewport pixel as a pixel of the target's frame: the same unless temporal upscaling renders the viewport smaller, then
+// the render pixel that holds the viewport pixel's centre (the upscale rule's unjittered sample). Negative stays negative.
+void Renderer::ToFramePixel(const ViewportContext& vc, int32_t& x, int32_t& y) const {
+    if (&vc == &m_LegacyTarget || !IsTemporalUpscalingEnabled(vc.m_Info.ViewportID)) return;
+    const int64_t vw = (int64_t)std::max(vc.m_Info.Size.x, 0.0f), vh = (int64_t)std::max(vc.m_Info.Size.y, 0.0f);
+    if (vw <= 0 || vh <= 0) return;
+    if (x >= 0) x = (int32_t)std::min<int64_t>((2 * (int64_t)x + 1) * vc.m_Width / (2 * vw), 0x7FFFFFFF);
+    if (y >= 0) y = (int32_t)std::min<int64_t>((2 * (int64_t)y + 1) * vc.m_Height / (2 * vh), 0x7FFFFFFF);
+}
+
 bool Renderer::PickEntity(uint32_t viewportId, int32_t x, int32_t y, ECS::Entity& out, float* depth01) {
     const ViewportContext* vc = IdTarget(viewportId);
+    if (vc) ToFramePixel(*vc, x, y);
     if (!vc || x < 0 || y < 0 || x >= (int32_t)vc->m_Width || y >= (int32_t)vc->m_Height) return false;
     tri_pick_result r{};
     if (Target{vc->m_Ctx, vc->m_Group}.Pick(x, y, &r) != TRI_OK) {
@@ -2243,6 +2280,8 @@ std::vector<ECS::Entity> Renderer::PickEntitiesInRect(uint32_t viewportId, int32
     std::vector<ECS::Entity> found;
     const ViewportContext* vc = IdTarget(viewportId);
     if (!vc || x1 < x0 || y1 < y0) return found;
+    ToFramePixel(*vc, x0, y0);
+    ToFramePixel(*vc, x1, y1);
     const uint32_t n = (uint32_t)vc->m_DrawEntities.size();
     std::vector<uint32_t> bits((n + 31u) / 32u + 1u, 0u);
     if (vc->m_Ctx) {
@@ -2492,6 +2531,10 @@ void Renderer::SetTemporalAntiAliasingEnabled(uint32_t viewportId, bool enabled,
         LogError("temporal anti-aliasing", "the jitter period is above 64");
         return;
     }
+    if (enabled && IsTemporalUpscalingEnabled(viewportId)) {
+        LogError("temporal anti-aliasing", "the viewport has temporal upscaling on (SetTemporalUpscalingEnabled)");
+        return;
+    }
     Taa& st = m_Taa[viewportId];
     if (enabled && !st.m_Enabled) {  // switching on: frames rendered meanwhile were not accumulated
         if (st.m_Object && tri_taa_reset(st.m_Object) != TRI_OK) LogError("temporal anti-aliasing", tri_last_error());
@@ -2588,7 +2631,204 @@ int Renderer::PresentBlit(ViewportContext& vc, uint32_t width, uint32_t height) 
     if (it != m_Taa.end() && it->second.m_Enabled && it->second.m_Object && it->second.m_LastTarget == &vc && vc.m_Ctx &&
         &vc != &m_LegacyTarget)
         return tri_taa_blit_linear(it->second.m_Object, vc.m_Ctx, nullptr, width, height);
+    auto up = m_Upscale.find(vc.m_Info.ViewportID);
+    if (up != m_Upscale.end() && up->second.m_Enabled && up->second.m_Object && up->second.m_LastTarget == &vc && vc.m_Ctx &&
+        &vc != &m_LegacyTarget)
+        return tri_upscale_blit_linear(up->second.m_Object, vc.m_Ctx, nullptr, width, height);
     return Target{vc.m_Ctx, vc.m_Group}.Blit(width, height);
+}
+
+// ---- temporal upscaling ---------------------------------------------------------------------------------------------
+namespace {
+uint32_t ScaledExtent(uint32_t size, float scale) { return std::max(1u, (uint32_t)((float)size * scale + 0.5f)); }
+}  // namespace
+
+bool Renderer::SetTemporalUpscalingEnabled(uint32_t viewportId, bool enabled, float renderScale, float alpha, bool rejectIds) {
+    if (enabled && m_Devices.size() > 1) {
+        LogError("temporal upscaling", "multi-device viewports (SetDeviceCount > 1) have no temporal upscaling");
+        return false;
+    }
+    if (enabled && !(alpha > 0.0f && alpha <= 1.0f)) {
+        LogError("temporal upscaling", "alpha lies outside (0, 1]");
+        return false;
+    }
+    if (enabled && !(renderScale >= 1.0f / 3.0f && renderScale <= 1.0f)) {
+        LogError("temporal upscaling", "the render scale lies outside [1/3, 1]");
+        return false;
+    }
+    if (enabled && IsTemporalAntiAliasingEnabled(viewportId)) {
+        LogError("temporal upscaling", "the viewport has temporal anti-aliasing on (SetTemporalAntiAliasingEnabled)");
+        return false;
+    }
+    if (enabled && m_Recording && viewportId == m_RecordingViewportId) {  // (the session's extent is the viewport's size)
+        LogError("temporal upscaling", "the viewport is being recorded (SetViewportRecordingEnabled)");
+        return false;
+    }
+    auto vp = m_Viewports.find(viewportId);
+    if (enabled && vp != m_Viewports.end()) {  // the extent rule, for the size the viewport has now
+        const uint32_t w = (uint32_t)std::max(vp->second.m_Info.Size.x, 0.0f), h = (uint32_t)std::max(vp->second.m_Info.Size.y, 0.0f);
+        uint32_t period = 0;
+        if (w && h && tri_upscale_jitter_period(ScaledExtent(w, renderScale), ScaledExtent(h, renderScale), w, h, &period) != TRI_OK) {
+            LogError("temporal upscaling", tri_last_error());
+            return false;
+        }
+    }
+    Upscale& st = m_Upscale[viewportId];
+    if (enabled && (!st.m_Enabled || st.m_Scale != renderScale)) {  // switching on, or another scale: no history
+        if (st.m_Object && tri_upscale_reset(st.m_Object) != TRI_OK) LogError("temporal upscaling", tri_last_error());
+        st.m_FrameIndex = 0;
+    }
+    if (!enabled) st.m_LastTarget = nullptr;  // the readers and the present answer for upscaled frames only
+    st.m_Enabled = enabled;
+    if (enabled) {
+        st.m_Scale = renderScale;
+        st.m_Alpha = alpha;
+        st.m_RejectIds = rejectIds;
+    }
+    return true;
+}
+
+bool Renderer::IsTemporalUpscalingEnabled(uint32_t viewportId) const {
+    auto it = m_Upscale.find(viewportId);
+    return it != m_Upscale.end() && it->second.m_Enabled;
+}
+
+void Renderer::RenderExtent(const ViewportContext& vc, uint32_t& width, uint32_t& height) const {
+    if (&vc == &m_LegacyTarget) return;
+    auto it = m_Upscale.find(vc.m_Info.ViewportID);
+    if (it == m_Upscale.end() || !it->second.m_Enabled) return;
+    width = ScaledExtent(width, it->second.m_Scale);
+    height = ScaledExtent(height, it->second.m_Scale);
+}
+
+void Renderer::DropUpscale() {
+    for (auto& it : m_Upscale) {
+        tri_upscale_destroy(it.second.m_Object);  // (waits for its last pass)
+        it.second.m_Object = nullptr;
+        it.second.m_LastTarget = nullptr;
+        it.second.m_FrameIndex = 0;
+    }
+}
+
+bool Renderer::BeginUpscaleFrame(const ViewportContext& vc, uint32_t viewportId, float jitter[2]) {
+    auto it = m_Upscale.find(viewportId);
+    if (it == m_Upscale.end() || !it->second.m_Enabled || !vc.m_Ctx || &vc == &m_LegacyTarget) return false;
+    Upscale& st = it->second;
+    st.m_Jitter[0] = st.m_Jitter[1] = 0.0f;
+    if (st.m_Width != vc.m_Width || st.m_Height != vc.m_Height) {  // the first frame, a resize or another scale
+        st.m_FrameIndex = 0;
+        st.m_Width = vc.m_Width;
+        st.m_Height = vc.m_Height;
+    }
+    const uint32_t ow = (uint32_t)std::max(vc.m_Info.Size.x, 0.0f), oh = (uint32_t)std::max(vc.m_Info.Size.y, 0.0f);
+    uint32_t period = 0;
+    if (tri_upscale_jitter_period(vc.m_Width, vc.m_Height, ow, oh, &period) != TRI_OK ||
+        tri_taa_jitter(st.m_FrameIndex, period, jitter) != TRI_OK) {
+        LogError("temporal upscaling", tri_last_error());
+        jitter[0] = jitter[1] = 0.0f;
+        return false;
+    }
+    st.m_Jitter[0] = jitter[0];
+    st.m_Jitter[1] = jitter[1];
+    ++st.m_FrameIndex;
+    return true;
+}
+
+// One tri_upscale per viewport, whichever of its targets renders the frame, like temporal anti-aliasing's object.
+bool Renderer::UpscaleTarget(ViewportContext& vc, uint32_t viewportId, bool redo) {
+    auto it = m_Upscale.find(viewportId);
+    if (it == m_Upscale.end() || !it->second.m_Enabled || &vc == &m_LegacyTarget) return true;
+    Upscale& st = it->second;
+    st.m_LastTarget = nullptr;
+    if (!vc.m_Ctx || !vc.m_MotionOutput) return false;
+    const uint32_t ow = (uint32_t)std::max(vc.m_Info.Size.x, 0.0f), oh = (uint32_t)std::max(vc.m_Info.Size.y, 0.0f);
+    if (st.m_Object && (st.m_RenderWidth != vc.m_Width || st.m_RenderHeight != vc.m_Height || st.m_OutWidth != ow || st.m_OutHeight != oh)) {
+        tri_upscale_destroy(st.m_Object);  // a resize or another scale: a new object, no history
+        st.m_Object = nullptr;
+    }
+    if (!st.m_Object) {
+        tri_image img{};
+        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK ||
+            tri_upscale_create(img.device, vc.m_Width, vc.m_Height, ow, oh, &st.m_Object) != TRI_OK) {
+            LogError("temporal upscaling", tri_last_error());
+            st.m_Object = nullptr;
+            return false;
+        }
+        st.m_RenderWidth = vc.m_Width;
+        st.m_RenderHeight = vc.m_Height;
+        st.m_OutWidth = ow;
+        st.m_OutHeight = oh;
+    }
+    tri_upscale_params params{};
+    params.alpha = st.m_Alpha;
+    params.jitter[0] = st.m_Jitter[0];
+    params.jitter[1] = st.m_Jitter[1];
+    params.flags = (redo ? TRI_UPSCALE_REDO : 0u) | (st.m_RejectIds ? TRI_UPSCALE_REJECT_ID : 0u);
+    if (tri_upscale_resolve(st.m_Object, vc.m_Ctx, &params) != TRI_OK ||
+        tri_upscale_get_output(st.m_Object, &st.m_Resolved, nullptr, nullptr) != TRI_OK) {
+        LogError("temporal upscaling", tri_last_error());
+        return false;
+    }
+    st.m_LastTarget = &vc;
+    return true;
+}
+
+// As RedoTaa: a redo pass when the target's pass was the object's last, else a reset.
+void Renderer::RedoUpscale(ViewportContext& vc) {
+    auto it = m_Upscale.find(vc.m_Info.ViewportID);
+    if (it == m_Upscale.end() || !it->second.m_Enabled || !it->second.m_Object || &vc == &m_LegacyTarget) return;
+    Upscale& st = it->second;
+    if (st.m_LastTarget == &vc) {
+        if (UpscaleTarget(vc, vc.m_Info.ViewportID, true)) {
+            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError("temporal upscaling", tri_last_error());
+        }
+    } else if (tri_upscale_reset(st.m_Object) != TRI_OK) {
+        LogError("temporal upscaling", tri_last_error());
+    }
+}
+
+Renderer::Upscale* Renderer::UpscaleOutput(uint32_t viewportId) {
+    FinishFrame();
+    auto it = m_Upscale.find(viewportId);
+    if (it == m_Upscale.end() || !it->second.m_Object || !it->second.m_LastTarget) return nullptr;
+    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame was not upscaled
+    return &it->second;
+}
+
+bool Renderer::ReadViewportUpscaledPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, uint32_t* width, uint32_t* height) {
+    Upscale* st = UpscaleOutput(viewportId);
+    if (!st) return false;
+    std::vector<uint8_t> bgra((size_t)st->m_OutWidth * st->m_OutHeight * 4);
+    if (tri_upscale_read(st->m_Object, bgra.data(), nullptr, nullptr) != TRI_OK) {
+        LogError("temporal upscaling", tri_last_error());
+        return false;
+    }
+    rgba.resize(bgra.size());
+    for (size_t i = 0; i < bgra.size(); i += 4) {  // BGRA -> RGBA, as ReadViewportPixels
+        rgba[i + 0] = bgra[i + 2];
+        rgba[i + 1] = bgra[i + 1];
+        rgba[i + 2] = bgra[i + 0];
+        rgba[i + 3] = bgra[i + 3];
+    }
+    if (width) *width = st->m_OutWidth;
+    if (height) *height = st->m_OutHeight;
+    return true;
+}
+
+bool Renderer::ReadViewportUpscaleMask(uint32_t viewportId, std::vector<uint8_t>& mask) {
+    Upscale* st = UpscaleOutput(viewportId);
+    if (!st) return false;
+    mask.resize((size_t)st->m_OutWidth * st->m_OutHeight);
+    if (tri_upscale_read(st->m_Object, nullptr, nullptr, mask.data()) != TRI_OK) {
+        LogError("temporal upscaling", tri_last_error());
+        return false;
+    }
+    return true;
+}
+
+void* Renderer::GetViewportUpscaledTexture(uint32_t viewportId) {
+    Upscale* st = UpscaleOutput(viewportId);
+    return st ? &st->m_Resolved : nullptr;
 }
 
 Renderer::Taa* Renderer::TaaOutput(uint32_t viewportId) {

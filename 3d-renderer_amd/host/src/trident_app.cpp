@@ -795,6 +795,50 @@ int trident_app_resolved_texture(trident_app* app, uint32_t viewport_id, tri_ima
     });
 }
 
+int trident_app_set_temporal_upscaling(trident_app* app, uint32_t viewport_id, int enabled, float render_scale, float alpha,
+                                       int reject_ids) {
+    return Guard(app, [&] {
+        // (a refused request leaves the switch as it was: on, perhaps, with its earlier values)
+        return app->renderer.SetTemporalUpscalingEnabled(viewport_id, enabled != 0, render_scale, alpha, reject_ids != 0) ? TRI_OK
+                                                                                                                         : TRI_E_STATE;
+    });
+}
+
+int trident_app_is_temporal_upscaling(trident_app* app, uint32_t viewport_id, int* enabled) {
+    return Guard(app, [&] {
+        if (!enabled) return TRI_E_INVALID;
+        *enabled = app->renderer.IsTemporalUpscalingEnabled(viewport_id) ? 1 : 0;
+        return TRI_OK;
+    });
+}
+
+int trident_app_read_upscaled(trident_app* app, uint32_t viewport_id, uint8_t* rgba, uint8_t* mask, uint64_t capacity) {
+    return Guard(app, [&] {
+        std::vector<uint8_t> c, m;
+        if (rgba) {
+            if (!app->renderer.ReadViewportUpscaledPixels(viewport_id, c)) return TRI_E_STATE;
+            if (c.size() / 4 > capacity) return TRI_E_INVALID;
+            std::memcpy(rgba, c.data(), c.size());
+        }
+        if (mask) {
+            if (!app->renderer.ReadViewportUpscaleMask(viewport_id, m)) return TRI_E_STATE;
+            if (m.size() > capacity) return TRI_E_INVALID;
+            std::memcpy(mask, m.data(), m.size());
+        }
+        return TRI_OK;
+    });
+}
+
+int trident_app_upscaled_texture(trident_app* app, uint32_t viewport_id, tri_image* out) {
+    return Guard(app, [&] {
+        if (!out) return TRI_E_INVALID;
+        const void* c = app->renderer.GetViewportUpscaledTexture(viewport_id);
+        if (!c) return TRI_E_STATE;
+        *out = *static_cast<const tri_image*>(c);
+        return TRI_OK;
+    });
+}
+
 struct trident_font {
     TextRenderer text;
 };

@@ -258,6 +258,19 @@ class TriTaaParams(C.Structure):
 assert C.sizeof(TriTaaParams) == 16
 
 
+# temporal upscaling (include/tri_raster.h): the mask bits, the flags, the parameters
+TRI_UPSCALE_NO_HISTORY, TRI_UPSCALE_NO_PROJ, TRI_UPSCALE_OUTSIDE, TRI_UPSCALE_ID = 1, 2, 4, 8
+TRI_UPSCALE_CLAMPED, TRI_UPSCALE_NO_SAMPLE = 32, 64
+TRI_UPSCALE_REDO, TRI_UPSCALE_REJECT_ID = 1, 2
+
+
+class TriUpscaleParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("jitter", C.c_float * 2), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(TriUpscaleParams) == 16
+
+
 class TriGroupConfig(C.Structure):
     _fields_ = [
         ("width", C.c_uint32),
@@ -535,6 +548,16 @@ CABI_FUNCTIONS = [
     ("tri_taa_get_output", C.c_int, [C.c_void_p, C.POINTER(TriImage), C.POINTER(TriImage), C.POINTER(TriImage)]),
     ("tri_taa_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("tri_taa_blit_linear", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("tri_upscale_create", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    ("tri_upscale_destroy", C.c_int, [C.c_void_p]),
+    ("tri_upscale_resolve", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(TriUpscaleParams)]),
+    ("tri_upscale_reset", C.c_int, [C.c_void_p]),
+    ("tri_upscale_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("tri_upscale_read_ids", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("tri_upscale_get_output", C.c_int, [C.c_void_p, C.POINTER(TriImage), C.POINTER(TriImage), C.POINTER(TriImage)]),
+    ("tri_upscale_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    ("tri_upscale_blit_linear", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("tri_upscale_jitter_period", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
 ]
 
 

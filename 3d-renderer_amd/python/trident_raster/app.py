@@ -136,6 +136,10 @@ _APP_FUNCTIONS = [
     ("trident_app_is_temporal_anti_aliasing", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
     ("trident_app_read_resolved", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
     ("trident_app_resolved_texture", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage)]),
+    ("trident_app_set_temporal_upscaling", C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_int]),
+    ("trident_app_is_temporal_upscaling", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]),
+    ("trident_app_read_upscaled", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("trident_app_upscaled_texture", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(abi.TriImage)]),
     ("trident_app_submit_text", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float * 2), C.POINTER(C.c_float * 4),
                                           C.c_char_p, C.c_uint32]),
     ("trident_app_set_font", C.c_int, [C.c_void_p, C.c_char_p, C.c_float]),
@@ -557,6 +561,42 @@ class TridentApp:
         if rc == abi.TRI_E_STATE:
             return None
         _check(rc, "resolved_texture")
+        return img
+
+    # ---- temporal upscaling ----
+    def set_temporal_upscaling(self, viewport_id, enabled=True, render_scale=0.5, alpha=0.1, reject_ids=True):
+        """Renderer::SetTemporalUpscalingEnabled; False where the renderer refuses it (SetDeviceCount > 1, a bad scale
+        or alpha, temporal anti-aliasing on for the viewport)."""
+        rc = self._lib.trident_app_set_temporal_upscaling(self._h, viewport_id, 1 if enabled else 0, render_scale, alpha,
+                                                          1 if reject_ids else 0)
+        if rc not in (abi.TRI_OK, abi.TRI_E_STATE):
+            _check(rc, "set_temporal_upscaling")
+        return rc == abi.TRI_OK
+
+    def is_temporal_upscaling(self, viewport_id):
+        """Renderer::IsTemporalUpscalingEnabled."""
+        on = C.c_int()
+        _check(self._lib.trident_app_is_temporal_upscaling(self._h, viewport_id, C.byref(on)), "is_temporal_upscaling")
+        return bool(on.value)
+
+    def read_upscaled(self, viewport_id, width, height):
+        """Renderer::ReadViewportUpscaledPixels and ReadViewportUpscaleMask at the viewport's full size: (uint8 [height,
+        width, 4] R G B A, mask uint8 [height, width]), or None where they return false."""
+        col = np.zeros((height, width, 4), np.uint8)
+        mask = np.zeros((height, width), np.uint8)
+        rc = self._lib.trident_app_read_upscaled(self._h, viewport_id, col.ctypes.data, mask.ctypes.data, mask.size)
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "read_upscaled")
+        return col, mask
+
+    def upscaled_texture(self, viewport_id):
+        """Renderer::GetViewportUpscaledTexture: an abi.TriImage handle, or None."""
+        img = abi.TriImage()
+        rc = self._lib.trident_app_upscaled_texture(self._h, viewport_id, C.byref(img))
+        if rc == abi.TRI_E_STATE:
+            return None
+        _check(rc, "upscaled_texture")
         return img
 
     def set_font(self, path, pixel_height=32.0):

@@ -539,6 +539,86 @@ class TriTaa:
         raster._present = None if dst_ptr else (width, height)
 
 
+def upscale_jitter_period(render_w, render_h, out_w, out_h):
+    """tri_upscale_jitter_period (host-only): eight samples per output pixel's area, at most 64."""
+    lib = load_library()
+    n = C.c_uint32()
+    _check(lib.tri_upscale_jitter_period(render_w, render_h, out_w, out_h, C.byref(n)))
+    return n.value
+
+
+class TriUpscale:
+    """tri_upscale: the accumulated colour of one view at an output extent (16-bit) outside any context, and the pass that
+    resolves a jittered frame of the render extent over it."""
+
+    def __init__(self, render_w, render_h, out_w, out_h, device=-1):
+        lib = load_library()
+        h = C.c_void_p()
+        _check(lib.tri_upscale_create(device, render_w, render_h, out_w, out_h, C.byref(h)))
+        self._h = h
+        self.render_width, self.render_height = render_w, render_h
+        self.width, self.height = out_w, out_h
+
+    def close(self):
+        if self._h:
+            _lib.tri_upscale_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def resolve(self, raster, jitter=(0.0, 0.0), alpha=0.1, reject_ids=True, redo=False, flags=None):
+        """tri_upscale_resolve behind the raster's last render (asynchronous). jitter: the one the frame was rendered
+        under, in render pixels. flags overrides the two switches' bits (for the error cases)."""
+        bits = (abi.TRI_UPSCALE_REDO if redo else 0) | (abi.TRI_UPSCALE_REJECT_ID if reject_ids else 0)
+        p = abi.TriUpscaleParams(float(alpha), (C.c_float * 2)(float(jitter[0]), float(jitter[1])), bits if flags is None else flags)
+        _check(_lib.tri_upscale_resolve(self._h, raster._ctx, C.byref(p)))
+
+    def reset(self):
+        _check(_lib.tri_upscale_reset(self._h))
+
+    def read(self):
+        """tri_upscale_read: (resolved uint8 [Ho, Wo, 4] B G R A, accumulated uint16 [Ho, Wo, 4], mask uint8 [Ho, Wo])."""
+        col = np.empty((self.height, self.width, 4), dtype=np.uint8)
+        acc = np.empty((self.height, self.width, 4), dtype=np.uint16)
+        mask = np.empty((self.height, self.width), dtype=np.uint8)
+        _check(_lib.tri_upscale_read(self._h, _ptr(col), _ptr(acc), _ptr(mask)))
+        return col, acc, mask
+
+    def read_ids(self):
+        """tri_upscale_read_ids: the ids the last pass stored, uint32 [Hr, Wr]."""
+        ids = np.empty((self.render_height, self.render_width), dtype=np.uint32)
+        _check(_lib.tri_upscale_read_ids(self._h, _ptr(ids)))
+        return ids
+
+    def images(self):
+        """tri_upscale_get_output: (resolved, accumulated, mask) as abi.TriImage."""
+        col, acc, mask = abi.TriImage(), abi.TriImage(), abi.TriImage()
+        _check(_lib.tri_upscale_get_output(self._h, C.byref(col), C.byref(acc), C.byref(mask)))
+        return col, acc, mask
+
+    def timing(self):
+        """tri_upscale_get_timing: (summed ms of the stamped passes, their number)."""
+        ms, n = C.c_double(), C.c_uint64()
+        _check(_lib.tri_upscale_get_timing(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def blit(self, raster, width, height, dst_ptr=None):
+        """tri_upscale_blit_linear: the resolved image scaled to width x height into dst_ptr, or into the raster's
+        present image (TriRaster.read_present)."""
+        _check(_lib.tri_upscale_blit_linear(self._h, raster._ctx, C.c_void_p(dst_ptr) if dst_ptr else None, width, height))
+        raster._present = None if dst_ptr else (width, height)
+
+
 def _pick_rect(call, x0, y0, x1, y1, draw_count):
     words = max((int(draw_count) + 31) // 32, 1)
     bits = np.zeros(words, dtype=np.uint32)

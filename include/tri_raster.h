@@ -1051,6 +1051,87 @@ int tri_taa_get_timing(tri_taa* taa, double* ms, uint64_t* passes);
  * extent; TRI_E_STATE: a row-band context, or no pass has run. */
 int tri_taa_blit_linear(tri_taa* taa, tri_ctx* ctx, void* dst, uint32_t width, uint32_t height);
 
+/* ---- temporal upscaling: jittered low-resolution frames resolved at the display extent ---------- */
+/* The jitter that removes staircases also places each frame's samples at new sub-pixel positions of a finer grid. A
+ * tri_upscale keeps the accumulated colour of one view at an OUTPUT extent Wo x Ho (16-bit UNORM, as a tri_taa) and the
+ * ids of the last frame at the RENDER extent Wr x Hr (the context's), twice, outside any context. After a tri_render with
+ * the motion output on, tri_upscale_resolve enqueues k_upscale_resolve on the context's stream: one output pixel per
+ * lane takes the render pixel whose jittered sample lies nearest, weighs it by the sample's distance from the output
+ * pixel's centre, and accumulates it over the clamped history fetched at the output extent. No kernel of the frame
+ * changes; the context's colour, depth, ids and motion are bit-identical with and without the pass.
+ * The host computes, each as one float32 division, rx = (float)Wr / (float)Wo, ry = (float)Hr / (float)Ho,
+ * ox = (float)Wo / (float)Wr, oy = (float)Ho / (float)Hr; (jx, jy) is the frame's jitter in render pixels. The rule for
+ * output pixel (X, Y), integers and float32, no multiply-add contracted, in exactly this order:
+ *     px = ((float)X + 0.5f) * rx                      py likewise with Y, ry
+ *     xr = clamp((int)floorf(px + jx), 0, Wr - 1)      yr likewise: the render pixel whose jittered sample lies nearest
+ *     c, i, d = colour, id, depth of render pixel (xr, yr);  R = the staged motion table's row for i
+ *     dx = (((float)xr + 0.5f) - jx) * ox - ((float)X + 0.5f)      dy likewise: the sample minus the output centre, output px
+ *     k  = fmaxf(0.0f, 1.0f - fabsf(dx)) * fmaxf(0.0f, 1.0f - fabsf(dy))       a = alpha * k
+ *     TRI_UPSCALE_NO_HISTORY  the object holds no previous frame; the mask is then exactly 1 on every pixel
+ *     u, v, proj, inside, the nearest previous pixel `at` and the four taps with fu, fv: exactly as under "history
+ *     reprojection", for pixel (X, Y) of a Wo x Ho frame with id i and depth d
+ *     TRI_UPSCALE_NO_PROJ     !proj                    TRI_UPSCALE_OUTSIDE     proj && !inside
+ *     TRI_UPSCALE_ID          with TRI_UPSCALE_REJECT_ID, inside, and with xi = at % Wo, yi = at / Wo,
+ *                             xq = min((int)(((float)xi + 0.5f) * rx), Wr - 1), yq likewise, none of the previous ids
+ *                             I'[clamp(yq + dy, 0, Hr - 1)][clamp(xq + dx, 0, Wr - 1)], dx, dy in {-1, 0, 1}, equals i
+ *     lo, hi = per channel, as bytes, the min and max of the render frame's colour over the clamped 3 x 3 round (xr, yr)
+ *     valid = (mask & 15) == 0
+ *     valid:    "temporal anti-aliasing"'s blend of the four taps of A' (Wo x Ho), its clamp to lo, hi
+ *               (TRI_UPSCALE_CLAMPED) and its mix r = hc * (1.0f - a) + cur16 * a, s and out8 as there;
+ *               TRI_UPSCALE_NO_SAMPLE in addition iff k == 0.0f: the frame added nothing to this pixel
+ *     invalid:  s = c_ch * 257,  out8 = c_ch       (the history restarts from the nearest sample, whatever k is)
+ *     stored:   A[Y][X] = s, resolved[Y][X] = out8 (B8G8R8A8), mask[Y][X] at the output extent;
+ *               I[y][x] = ids[y][x] for every render pixel
+ * At Wo == Wr and Ho == Hr this is not tri_taa's rule: the weight is alpha (1 - |jx|)(1 - |jy|).
+ *
+ * The jitter contract is tri_taa's, with tri_taa_jitter_projection taking the RENDER extent: frame n is rendered with
+ * jitter(P_n, j_n), tri_set_motion_history gets jitter(P_{n-1}, j_n). A still scene gives identity rows, and each output
+ * pixel's tap is then the pixel itself. */
+#define TRI_UPSCALE_NO_HISTORY 1u
+#define TRI_UPSCALE_NO_PROJ 2u
+#define TRI_UPSCALE_OUTSIDE 4u
+#define TRI_UPSCALE_ID 8u
+#define TRI_UPSCALE_CLAMPED 32u
+#define TRI_UPSCALE_NO_SAMPLE 64u
+#define TRI_UPSCALE_REDO 1u      /* tri_upscale_params.flags: the frame of the last call, rendered again */
+#define TRI_UPSCALE_REJECT_ID 2u /* ... the 3 x 3 id test */
+typedef struct tri_upscale tri_upscale;
+typedef struct tri_upscale_params {
+    float alpha;     /* the current frame's weight at a sample on the pixel's centre, 0 < alpha <= 1 */
+    float jitter[2]; /* the jitter the frame was rendered under, in render pixels, |j| <= 0.5 */
+    uint32_t flags;  /* TRI_UPSCALE_REDO | TRI_UPSCALE_REJECT_ID */
+} tri_upscale_params;
+/* Two sets of {accumulated colour 8 B per output pixel, ids 4 B per render pixel}, the resolved image (4 B) and the mask
+ * (1 B) at the output extent and the object's events, on one device (-1 = current). TRI_E_INVALID, before any device is
+ * touched: a zero extent, more than 2^31 pixels, a side above 2^30, or an output extent outside render_w <= out_w <= 3 render_w,
+ * render_h <= out_h <= 3 render_h. tri_upscale_destroy waits for the last pass; NULL is TRI_OK. */
+int tri_upscale_create(int32_t device, uint32_t render_w, uint32_t render_h, uint32_t out_w, uint32_t out_h, tri_upscale** out);
+int tri_upscale_destroy(tri_upscale* up);
+/* Asynchronous, on the context's stream behind the tri_render whose frame it reads (and behind the object's previous
+ * pass, which may have run on another context's stream); the frame's ids are copied into the written set on the same
+ * stream. The sets swap and TRI_UPSCALE_REDO works as tri_history_reproject's do. TRI_E_INVALID: a null argument, a
+ * context on another device or whose extent is not the render extent, an alpha outside (0, 1], a jitter that is not
+ * finite or beyond half a pixel, unknown flag bits. TRI_E_UNSUPPORTED: a row-band context. TRI_E_STATE: the context's
+ * motion output is off, or no frame has been rendered with it. Every check comes before the device is made current. */
+int tri_upscale_resolve(tri_upscale* up, tri_ctx* ctx, const tri_upscale_params* params);
+/* Forget the accumulated frame: the next call reports TRI_UPSCALE_NO_HISTORY everywhere (and a redo is a plain call). */
+int tri_upscale_reset(tri_upscale* up);
+/* The last pass's resolved image (out_w x out_h x 4 bytes, B G R A), accumulated colour (x 4 uint16) and mask (bytes),
+ * tightly packed; any pointer may be NULL. Waits for the pass. TRI_E_STATE before the first pass. */
+int tri_upscale_read(tri_upscale* up, uint8_t* bgra8, uint16_t* rgba16, uint8_t* mask);
+/* The last pass's stored ids (render_w x render_h uint32). Waits for the pass. TRI_E_STATE before the first pass. */
+int tri_upscale_read_ids(tri_upscale* up, uint32_t* ids);
+/* The three images in device memory, all at the output extent, in tri_taa_get_output's formats; colour16 is the set the
+ * last pass wrote. Any pointer may be NULL. TRI_E_STATE before the first pass. */
+int tri_upscale_get_output(tri_upscale* up, tri_image* colour8, tri_image* colour16, tri_image* mask);
+/* As tri_history_get_timing; the interval covers the kernel and the id copy. */
+int tri_upscale_get_timing(tri_upscale* up, double* ms, uint64_t* passes);
+/* As tri_taa_blit_linear, over the object's resolved image. */
+int tri_upscale_blit_linear(tri_upscale* up, tri_ctx* ctx, void* dst, uint32_t width, uint32_t height);
+/* min(64, ceil(8 (out_w / render_w) (out_h / render_h))) in double: eight samples per output pixel's area (8 at 1 x, 18 at
+ * 1.5 x, 32 at 2 x, 64 at 3 x). Host only. TRI_E_INVALID for a null period or extents tri_upscale_create refuses. */
+int tri_upscale_jitter_period(uint32_t render_w, uint32_t render_h, uint32_t out_w, uint32_t out_h, uint32_t* period);
+
 /* ---- one rank's band exchange (process per GPU) --------------------------------------------- */
 /* A process-per-GPU caller (bench.py at N > 1) renders one row band per rank and assembles the frame on the
  * display rank. tri_xfer drives that exchange natively over RCCL communicators of its own: one call per frame
@@ -1259,6 +1340,7 @@ static_assert(sizeof(tri_outline) == 40, "tri_outline layout");
 static_assert(sizeof(tri_motion_history) == 144, "tri_motion_history layout");
 static_assert(sizeof(tri_reproject_params) == 16, "tri_reproject_params layout");
 static_assert(sizeof(tri_taa_params) == 16, "tri_taa_params layout");
+static_assert(sizeof(tri_upscale_params) == 16, "tri_upscale_params layout");
 static_assert(sizeof(tri_pose_bone) == 128, "tri_pose_bone layout");
 static_assert(sizeof(tri_pose_channel) == 32, "tri_pose_channel layout");
 static_assert(sizeof(tri_pose_instance) == 16, "tri_pose_instance layout");
