@@ -266,6 +266,22 @@ hipError_t tri_launch_dbp_unpack_bands(const uint8_t* const* src, uint32_t* cons
 // conversion (VideoEncoder.cpp:716-736), byte for byte.
 hipError_t tri_launch_bgra_to_yuv444(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, uint8_t* dst,
                                      hipStream_t stream);
+// JPEG recording (jpeg_encode.hip): the same source -> a baseline JPEG behind the header that `out` already holds, by
+// csrc/jpeg_math.h's rule. Every pointer is device memory sized by jpeg::make_layout / jpeg::max_bytes for the extent
+// and `restart` (>= 1): tables one jpeg::Tables, coef mcus * 384 int16 (16-B aligned), scratch intervals *
+// segment_bytes, counts and offsets one dword per interval, size_word one dword (the stream's size, SOI to EOI).
+struct tri_jpeg_job {
+    const void* src;
+    uint32_t pitch_bytes, width, height;
+    uint32_t restart, segment_bytes, header_bytes;
+    const void* tables;
+    int16_t* coef;
+    uint8_t* scratch;
+    uint32_t *counts, *offsets;
+    uint8_t* out;
+    uint32_t* size_word;
+};
+hipError_t tri_launch_jpeg_encode(const tri_jpeg_job& job, hipStream_t stream);
 // The AI input tensor (frame_tensor.hip): the same source -> dst width * height * 4 floats (4-B aligned; 16-B aligned
 // for the 16-B store path), R, G, B, A per pixel, each (float)byte * (1.0f / 255.0f) (Renderer.cpp:1111-1389).
 hipError_t tri_launch_bgra_to_rgba_f32(const void* src, uint32_t width, uint32_t height, uint32_t pitch_bytes, float* dst,

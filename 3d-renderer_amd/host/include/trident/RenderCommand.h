@@ -103,6 +103,8 @@ public:
         return GetRenderer().SetViewportRecordingEnabled(enabled, viewportId, width, height, outputPath);
     }
     static bool IsViewportRecording() { return GetRenderer().IsViewportRecording(); }
+    static void SetRecordingQuality(int quality) { GetRenderer().SetRecordingQuality(quality); }
+    static int GetRecordingQuality() { return GetRenderer().GetRecordingQuality(); }
     static void GetRecordingExtent(uint32_t& width, uint32_t& height) { GetRenderer().GetRecordingExtent(width, height); }
     static uint64_t GetRecordedFrameCount() { return GetRenderer().GetRecordedFrameCount(); }
     // Dataset capture (RenderCommand.h:69-77)

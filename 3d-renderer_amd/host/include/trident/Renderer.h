@@ -146,6 +146,12 @@ public:
     bool SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, uint32_t width, uint32_t height,
                                      const std::string& outputPath);
     bool IsViewportRecording() const { return m_Recording; }
+    // An outputPath ending in .mkv (any case) records Motion-JPEG in Matroska instead: each frame is encoded on the
+    // device (tri_recorder_create_ex, TRI_RECORD_JPEG420) behind its pass and reaches the file as one SimpleBlock
+    // through VideoEncoder::SubmitJpeg; every rule above holds unchanged, "FRAME record" read as "block". The quality
+    // (1..100, default 90; values outside are clamped) applies from the next session.
+    void SetRecordingQuality(int quality) { m_RecordingQuality = quality < 1 ? 1u : (quality > 100 ? 100u : (uint32_t)quality); }
+    int GetRecordingQuality() const { return (int)m_RecordingQuality; }
     uint32_t GetRecordingViewportId() const { return m_RecordingViewportId; }  // meaningful while recording
     void GetRecordingExtent(uint32_t& width, uint32_t& height) const { width = m_RecordingWidth; height = m_RecordingHeight; }
     uint64_t GetRecordedFrameCount() const { return m_VideoEncoder.GetFrameCount(); }  // of the current or last session
@@ -693,6 +699,8 @@ private:
     std::string m_RecordingPath;
     VideoEncoder m_VideoEncoder;
     tri_recorder* m_Recorder = nullptr;
+    bool m_RecordingJpeg = false;  // the session is an .mkv: the recorder makes JPEGs
+    uint32_t m_RecordingQuality = 90;
 
     // text overlay: the font and the frame's queue, and one device atlas per device (made by the first DrawFrame
     // with text, dropped with the viewport targets and when the font changes)

@@ -3,6 +3,13 @@
 // in the same double-precision operation order. The reference hands .mp4 / .mov / .avi to FFmpeg; FFmpeg is not part
 // of this project, so those containers are refused with a log line that says so (a documented deviation).
 // SubmitPlanes is this project's addition: frames the device has converted already (tri_recorder).
+//
+// A second container is this project's own: .mkv, Matroska with one V_MJPEG track. Every frame is a baseline JPEG by
+// csrc/jpeg_math.h's rule, encoded here on the host from RGBA (SubmitFrame) or taken as the device encoded it
+// (SubmitJpeg). The writer follows the Matroska specification with no library: EBML header, a Segment of unknown
+// size with Info and Tracks, then Clusters (a new one at least once per second of video) of SimpleBlocks, every frame
+// a keyframe with the timecode round(1000 n / fps) ms. Segment and Cluster sizes and the Duration are patched when
+// the element closes, so a file whose session was never ended is still a valid live-style stream.
 #pragma once
 
 #include <chrono>
@@ -27,14 +34,24 @@ public:
     VideoEncoder& operator=(const VideoEncoder&) = delete;
 
     // Ends any session in progress, then opens `path` (binary, truncating) and writes the header. False, without
-    // creating a file, for a zero extent, an FFmpeg container or any extension but .y4m (compared lower-cased).
-    // targetFps 0 means 30.
+    // creating a file, for a zero extent, an FFmpeg container or any extension but .y4m and .mkv (compared
+    // lower-cased; .mkv also for an extent side above 65535). targetFps 0 means 30.
     bool BeginSession(const std::string& path, uint32_t width, uint32_t height, uint32_t targetFps);
-    // One FRAME record from RGBA pixels, converted here on the host. False (nothing written) without a session, for
-    // an empty pixel buffer, or an extent that is not the session's.
+    // One FRAME record (.y4m) or one SimpleBlock (.mkv) from RGBA pixels, converted or encoded here on the host. False
+    // (nothing written) without a session, for an empty pixel buffer, or an extent that is not the session's.
     bool SubmitFrame(const RecordedFrame& frame);
-    // One FRAME record from 3 * width * height bytes converted already (Y, U, V planes). Same refusals.
+    // One FRAME record from 3 * width * height bytes converted already (Y, U, V planes). Same refusals, and refused
+    // by an .mkv session.
     bool SubmitPlanes(const uint8_t* yuv, uint32_t width, uint32_t height);
+    // One SimpleBlock from a complete JPEG of the session's extent, encoded already (tri_recorder_wait_ex). Same
+    // refusals, and refused by a .y4m session and for a stream that does not run from SOI to EOI.
+    bool SubmitJpeg(const uint8_t* jpeg, uint64_t bytes, uint32_t width, uint32_t height);
+    // The JPEG parameters of SubmitFrame on an .mkv session: sticky across sessions. Quality 1..100 (default 90);
+    // the restart interval in MCUs, 1..65535, 0 = the rule's default. False (unchanged) outside the range.
+    bool SetQuality(uint32_t quality);
+    bool SetRestartInterval(uint32_t restartMcus);
+    uint32_t GetQuality() const { return m_Quality; }
+    uint32_t GetRestartInterval() const { return m_RestartMcus; }
     // Flushes and closes the file; false when no session is active.
     bool EndSession();
     bool IsSessionActive() const { return m_File != nullptr; }
@@ -49,11 +66,27 @@ public:
 
 private:
     bool WriteRecord(const uint8_t* yuv);
+    // the Matroska writer
+    bool MkvWrite(const void* data, size_t bytes);
+    bool MkvPatch(long at, const void* data, size_t bytes);
+    bool MkvWriteHeader();
+    bool MkvWriteBlock(const uint8_t* jpeg, uint64_t bytes);
+    bool MkvCloseCluster();
+    bool MkvFinish();
+    void Abandon(const char* why);  // a failed write: log, close the file, end the session
 
     std::FILE* m_File = nullptr;
     uint32_t m_Width = 0, m_Height = 0;
     uint64_t m_Frames = 0;
     std::vector<uint8_t> m_Planes;  // SubmitFrame's conversion scratch
+    bool m_Mkv = false;
+    uint32_t m_Fps = 30, m_Quality = 90, m_RestartMcus = 0;
+    uint64_t m_Pos = 0;                        // bytes written so far (the file offset of the next byte)
+    long m_SegmentSizeAt = 0, m_DurationAt = 0;  // where the patched fields are
+    long m_ClusterSizeAt = -1;                 // -1: no cluster is open
+    uint64_t m_ClusterMs = 0, m_SegmentDataAt = 0, m_ClusterDataAt = 0;
+    std::vector<int16_t> m_Coefficients;       // SubmitFrame's JPEG scratch
+    std::vector<uint8_t> m_Jpeg;
 };
 
 }  // namespace Trident

@@ -147,6 +147,10 @@ int trident_app_set_frames_in_flight(trident_app* app, uint32_t n);
  * size it), so the frames are those of a viewport of that extent. enabled = 0 finalises the file (path may be NULL). */
 int trident_app_set_recording(trident_app* app, int enabled, uint32_t viewport_id, uint32_t width, uint32_t height,
                               const char* path, uint32_t out_extent[2]);
+/* Renderer::SetRecordingQuality / GetRecordingQuality: the JPEG quality of .mkv recordings (a `path` ending in .mkv
+ * records Motion-JPEG in Matroska, encoded on the device), from the next session; clamped to 1..100, default 90.
+ * out_quality, nullable, gets the value in force. */
+int trident_app_set_recording_quality(trident_app* app, int quality, int* out_quality);
 /* Renderer::IsViewportRecording / GetRecordedFrameCount (FRAME records of the current or last session). */
 int trident_app_recording_state(trident_app* app, int* recording, uint64_t* frames);
 
@@ -160,6 +164,12 @@ int trident_video_begin(trident_video* video, const char* path, uint32_t width, 
 int trident_video_submit_rgba(trident_video* video, const uint8_t* rgba, uint64_t bytes, uint32_t width,
                               uint32_t height);
 int trident_video_submit_planes(trident_video* video, const uint8_t* yuv, uint32_t width, uint32_t height);
+/* An .mkv session (Matroska, V_MJPEG): submit_rgba encodes the frame as a baseline JPEG on the host; submit_jpeg
+ * takes a complete JPEG of the session's extent, encoded already (tri_recorder_wait_ex). set_quality (1..100, default
+ * 90) and set_restart_interval (MCUs, 1..65535; 0 = the default) are sticky; TRI_E_INVALID outside the range. */
+int trident_video_submit_jpeg(trident_video* video, const uint8_t* jpeg, uint64_t bytes, uint32_t width, uint32_t height);
+int trident_video_set_quality(trident_video* video, uint32_t quality);
+int trident_video_set_restart_interval(trident_video* video, uint32_t restart_mcus);
 int trident_video_end(trident_video* video);
 int trident_video_state(trident_video* video, int* active, uint64_t* frames);
 /* VideoEncoder::ConvertRgbaToYuv444 alone: `pixels` RGBA8 pixels -> 3 * pixels bytes, planar (alpha ignored). */

@@ -11,6 +11,7 @@
 #include "trident/ModelLoader.h"
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1620,12 +1621,14 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
             bool ok = rc == TRI_OK;
             if (ok && rerendered)
                 ok = tri_recorder_release(m_Recorder, p.m_RecordSlot) == TRI_OK && CaptureRecordedFrame(*vc, p.m_RecordSlot);
-            const uint8_t* planes = nullptr;
-            if (ok && tri_recorder_wait(m_Recorder, p.m_RecordSlot, &planes) != TRI_OK) {
+            const uint8_t* product = nullptr;
+            uint64_t bytes = 0;
+            if (ok && tri_recorder_wait_ex(m_Recorder, p.m_RecordSlot, &product, &bytes) != TRI_OK) {
                 LogError("recording", tri_last_error());
                 ok = false;
             }
-            if (ok && !m_VideoEncoder.SubmitPlanes(planes, m_RecordingWidth, m_RecordingHeight))
+            if (ok && !(m_RecordingJpeg ? m_VideoEncoder.SubmitJpeg(product, bytes, m_RecordingWidth, m_RecordingHeight)
+                                        : m_VideoEncoder.SubmitPlanes(product, m_RecordingWidth, m_RecordingHeight)))
                 LogError("recording", "the encoder refused a frame");
             if (tri_recorder_release(m_Recorder, p.m_RecordSlot) != TRI_OK) LogError("recording", tri_last_error());
         }
@@ -1671,6 +1674,7 @@ bool Renderer::SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, ui
         LogError("viewport recording", "extent beyond the framebuffer limit");
         return false;
     }
+    m_VideoEncoder.SetQuality(m_RecordingQuality);
     if (!m_VideoEncoder.BeginSession(outputPath, w, h, 1) || !m_VideoEncoder.IsSessionActive()) {
         LogError("viewport recording", "the video encoder did not start a session");
         return false;
@@ -1681,6 +1685,10 @@ bool Renderer::SetViewportRecordingEnabled(bool enabled, uint32_t viewportId, ui
     m_RecordingWidth = w;
     m_RecordingHeight = h;
     m_RecordingPath = outputPath;
+    m_RecordingJpeg = outputPath.size() >= 4 && std::tolower((unsigned char)outputPath[outputPath.size() - 3]) == 'm' &&
+                      std::tolower((unsigned char)outputPath[outputPath.size() - 2]) == 'k' &&
+                      std::tolower((unsigned char)outputPath[outputPath.size() - 1]) == 'v' &&
+                      outputPath[outputPath.size() - 4] == '.';  // (the encoder accepted the name: .y4m or .mkv)
     auto it = m_Viewports.find(viewportId);  // (a viewport registered later is pinned by SetViewport)
     if (it != m_Viewports.end()) it->second.m_Info.Size = glm::vec2((float)w, (float)h);
     tri_recorder_destroy(m_Recorder);  // a recorder of the previous extent
@@ -1707,8 +1715,10 @@ bool Renderer::CaptureRecordedFrame(ViewportContext& vc, uint32_t slot) {
         return false;
     }
     if (!m_Recorder) {  // (SetFramesInFlight drops it with the targets, so its slots always match)
-        if (tri_recorder_create(vc.m_Image.device, m_RecordingWidth, m_RecordingHeight, m_FramesInFlight, &m_Recorder) !=
-            TRI_OK) {
+        const tri_record_params params{m_RecordingJpeg ? TRI_RECORD_JPEG420 : TRI_RECORD_YUV444, m_VideoEncoder.GetQuality(),
+                                       m_VideoEncoder.GetRestartInterval(), 0};
+        if (tri_recorder_create_ex(vc.m_Image.device, m_RecordingWidth, m_RecordingHeight, m_FramesInFlight, &params,
+                                   &m_Recorder) != TRI_OK) {
             LogError("recording", tri_last_error());
             return false;
         }

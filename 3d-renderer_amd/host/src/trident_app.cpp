@@ -625,6 +625,14 @@ int trident_app_set_recording(trident_app* app, int enabled, uint32_t viewport_i
     });
 }
 
+int trident_app_set_recording_quality(trident_app* app, int quality, int* out_quality) {
+    return Guard(app, [&] {
+        app->renderer.SetRecordingQuality(quality);
+        if (out_quality) *out_quality = app->renderer.GetRecordingQuality();
+        return TRI_OK;
+    });
+}
+
 int trident_app_recording_state(trident_app* app, int* recording, uint64_t* frames) {
     return Guard(app, [&] {
         if (recording) *recording = app->renderer.IsViewportRecording() ? 1 : 0;
@@ -981,6 +989,25 @@ int trident_video_submit_rgba(trident_video* video, const uint8_t* rgba, uint64_
 int trident_video_submit_planes(trident_video* video, const uint8_t* yuv, uint32_t width, uint32_t height) {
     if (!video) return TRI_E_INVALID;
     return video->encoder.SubmitPlanes(yuv, width, height) ? TRI_OK : TRI_E_STATE;
+}
+
+int trident_video_submit_jpeg(trident_video* video, const uint8_t* jpeg, uint64_t bytes, uint32_t width, uint32_t height) {
+    if (!video) return TRI_E_INVALID;
+    try {
+        return video->encoder.SubmitJpeg(jpeg, bytes, width, height) ? TRI_OK : TRI_E_STATE;
+    } catch (const std::exception&) {
+        return TRI_E_OOM;
+    }
+}
+
+int trident_video_set_quality(trident_video* video, uint32_t quality) {
+    if (!video) return TRI_E_INVALID;
+    return video->encoder.SetQuality(quality) ? TRI_OK : TRI_E_INVALID;
+}
+
+int trident_video_set_restart_interval(trident_video* video, uint32_t restart_mcus) {
+    if (!video) return TRI_E_INVALID;
+    return video->encoder.SetRestartInterval(restart_mcus) ? TRI_OK : TRI_E_INVALID;
 }
 
 int trident_video_end(trident_video* video) {

@@ -238,6 +238,17 @@ TRI_REPROJECT_NO_HISTORY, TRI_REPROJECT_NO_PROJ, TRI_REPROJECT_OUTSIDE, TRI_REPR
 TRI_HISTORY_REDO = 1
 
 
+TRI_RECORD_YUV444 = 0
+TRI_RECORD_JPEG420 = 1
+
+
+class TriRecordParams(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("quality", C.c_uint32), ("restart_mcus", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(TriRecordParams) == 16
+
+
 class TriReprojectParams(C.Structure):
     _fields_ = [("depth_tolerance", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
@@ -437,6 +448,13 @@ CABI_FUNCTIONS = [
     ("tri_recorder_capture", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     ("tri_recorder_wait", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("tri_recorder_release", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("tri_recorder_create_ex", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(TriRecordParams),
+                                         C.POINTER(C.c_void_p)]),
+    ("tri_recorder_capture_image", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("tri_recorder_wait_ex", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    ("tri_jpeg_header", C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(TriRecordParams), C.c_void_p, C.c_uint32,
+                                  C.POINTER(C.c_uint32)]),
+    ("tri_jpeg_max_bytes", C.c_uint64, [C.c_uint32, C.c_uint32, C.POINTER(TriRecordParams)]),
     ("tri_convert_rgba_f32", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("tri_framegrab_create", C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     ("tri_framegrab_destroy", C.c_int, [C.c_void_p]),

@@ -78,11 +78,15 @@ _APP_FUNCTIONS = [
     ("trident_app_set_recording", C.c_int, [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p,
                                             C.POINTER(C.c_uint32 * 2)]),
     ("trident_app_recording_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    ("trident_app_set_recording_quality", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     ("trident_video_create", C.c_int, [C.POINTER(C.c_void_p)]),
     ("trident_video_destroy", None, [C.c_void_p]),
     ("trident_video_begin", C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("trident_video_submit_rgba", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
     ("trident_video_submit_planes", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("trident_video_submit_jpeg", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
+    ("trident_video_set_quality", C.c_int, [C.c_void_p, C.c_uint32]),
+    ("trident_video_set_restart_interval", C.c_int, [C.c_void_p, C.c_uint32]),
     ("trident_video_end", C.c_int, [C.c_void_p]),
     ("trident_video_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     ("trident_video_convert_rgba", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
@@ -626,6 +630,12 @@ class TridentApp:
             _check(rc, "set_recording")
         return rc == abi.TRI_OK, (ext[0], ext[1])
 
+    def set_recording_quality(self, quality):
+        """Renderer::SetRecordingQuality -> GetRecordingQuality (the JPEG quality of .mkv recordings, clamped to 1..100)."""
+        q = C.c_int()
+        _check(self._lib.trident_app_set_recording_quality(self._h, quality, C.byref(q)), "set_recording_quality")
+        return q.value
+
     def recording_state(self):
         """(Renderer::IsViewportRecording, GetRecordedFrameCount)."""
         rec, frames = C.c_int(), C.c_uint64()
@@ -881,6 +891,20 @@ class VideoEncoder:
             raise ValueError("submit_planes: 3 * width * height bytes expected")
         return self._bool(self._lib.trident_video_submit_planes(self._h, a.ctypes.data, width, height),
                           "video_submit_planes")
+
+    def submit_jpeg(self, jpeg, width, height):
+        """SubmitJpeg: a complete JPEG (bytes or a uint8 array) into an .mkv session."""
+        a = np.frombuffer(bytes(jpeg), np.uint8) if isinstance(jpeg, (bytes, bytearray)) else np.ascontiguousarray(jpeg, np.uint8)
+        return self._bool(self._lib.trident_video_submit_jpeg(self._h, a.ctypes.data if a.size else None, a.size, width,
+                                                              height), "video_submit_jpeg")
+
+    def set_quality(self, quality):
+        """SetQuality: False (unchanged) outside 1..100."""
+        return self._lib.trident_video_set_quality(self._h, quality) == abi.TRI_OK
+
+    def set_restart_interval(self, restart_mcus):
+        """SetRestartInterval: False (unchanged) outside 0..65535."""
+        return self._lib.trident_video_set_restart_interval(self._h, restart_mcus) == abi.TRI_OK
 
     def end(self):
         return self._bool(self._lib.trident_video_end(self._h), "video_end")

@@ -811,13 +811,42 @@ def convert_yuv444(src_ptr, width, height, pitch_bytes, dst_ptr, stream_ptr=None
                                    C.c_void_p(dst_ptr) if dst_ptr else None, C.c_void_p(stream_ptr) if stream_ptr else None))
 
 
-class TriRecorder:
-    """tri_recorder: `slots` device + pinned YUV 4:4:4 buffers of one extent; capture is asynchronous."""
+def record_params(fmt=abi.TRI_RECORD_JPEG420, quality=90, restart_mcus=0, flags=0):
+    return abi.TriRecordParams(fmt, quality, restart_mcus, flags)
 
-    def __init__(self, width, height, slots, device=-1):
+
+def jpeg_header(width, height, quality=90, restart_mcus=0, capacity=1024, params=None):
+    """tri_jpeg_header: the stream's bytes before the entropy-coded data (host only)."""
+    load_library()
+    p = params if params is not None else record_params(abi.TRI_RECORD_JPEG420, quality, restart_mcus)
+    buf = (C.c_uint8 * max(capacity, 1))()
+    n = C.c_uint32()
+    _check(_lib.tri_jpeg_header(width, height, C.byref(p), buf, capacity, C.byref(n)))
+    return bytes(buf[:n.value])
+
+
+def jpeg_max_bytes(width, height, quality=90, restart_mcus=0, params=None):
+    """tri_jpeg_max_bytes: the size no stream of this extent and these parameters exceeds (host only)."""
+    load_library()
+    p = params if params is not None else record_params(abi.TRI_RECORD_JPEG420, quality, restart_mcus)
+    n = _lib.tri_jpeg_max_bytes(width, height, C.byref(p))
+    if n == 0:
+        _check(abi.TRI_E_INVALID)
+    return n
+
+
+class TriRecorder:
+    """tri_recorder: `slots` device + pinned buffers of one extent; capture is asynchronous. fmt None is
+    tri_recorder_create (YUV 4:4:4 planes); TRI_RECORD_YUV444 / TRI_RECORD_JPEG420 go through tri_recorder_create_ex."""
+
+    def __init__(self, width, height, slots, device=-1, fmt=None, quality=90, restart_mcus=0, params=None):
         lib = load_library()
         r = C.c_void_p()
-        _check(lib.tri_recorder_create(device, width, height, slots, C.byref(r)))
+        if fmt is None and params is None:
+            _check(lib.tri_recorder_create(device, width, height, slots, C.byref(r)))
+        else:
+            p = params if params is not None else record_params(fmt, quality, restart_mcus)
+            _check(lib.tri_recorder_create_ex(device, width, height, slots, C.byref(p), C.byref(r)))
         self._r = r
         self.width, self.height, self.slots = width, height, slots
 
@@ -851,6 +880,17 @@ class TriRecorder:
         p = self.wait_pointer(slot)
         buf = (C.c_uint8 * (3 * self.width * self.height)).from_address(p)
         return np.frombuffer(buf, np.uint8).reshape(3, self.height, self.width)
+
+    def capture_image(self, slot, src_ptr, pitch_bytes, stream_ptr=None):
+        """tri_recorder_capture_image: the capture from any device image of the recorder's extent."""
+        _check(_lib.tri_recorder_capture_image(self._r, slot, C.c_void_p(src_ptr) if src_ptr else None, pitch_bytes,
+                                               C.c_void_p(stream_ptr) if stream_ptr else None))
+
+    def wait_ex(self, slot):
+        """The slot's product, uint8 [bytes]: a view of the pinned buffer, valid until release."""
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.tri_recorder_wait_ex(self._r, slot, C.byref(p), C.byref(n)))
+        return np.frombuffer((C.c_uint8 * n.value).from_address(p.value), np.uint8)
 
     def release(self, slot):
         _check(_lib.tri_recorder_release(self._r, slot))

@@ -604,6 +604,46 @@ int tri_recorder_capture(tri_recorder* recorder, uint32_t slot, tri_ctx* ctx);
 int tri_recorder_wait(tri_recorder* recorder, uint32_t slot, const uint8_t** yuv);
 int tri_recorder_release(tri_recorder* recorder, uint32_t slot);
 
+/* ---- JPEG recording: the frame as a baseline JPEG, encoded on the device (Matroska V_MJPEG payloads) ----
+ * A recorder created with TRI_RECORD_JPEG420 turns a frame into a complete JFIF stream instead of YUV planes: SOF0,
+ * 8 bit, Y sampled 2 x 2 and Cb, Cr 1 x 1 (16 x 16 MCUs, extents padded by edge replication), JFIF full-range
+ * BT.601, the T.81 Annex K quantisers scaled by `quality` (1..100, the IJG rule) and the Annex K Huffman tables, with
+ * restart intervals of `restart_mcus` MCUs (1..65535; 0 = the library's default) that the device encodes in
+ * parallel. The rule is integer arithmetic throughout (csrc/jpeg_math.h): the bytes are the same from the device and
+ * from the host encoder. Three stages run on the capturing stream: pixels to quantised coefficients, one restart
+ * interval per wave to stuffed bytes, and the gather of the intervals and their RSTn behind the header. Every
+ * buffer is sized from the worst case (tri_jpeg_max_bytes), so no frame can overflow one.
+ *   tri_recorder_create_ex     `params` NULL, or format TRI_RECORD_YUV444, is tri_recorder_create. TRI_E_INVALID: an
+ *                              unknown format or flag bit, a quality or restart interval out of range.
+ *   tri_recorder_capture       as above, for either format.
+ *   tri_recorder_capture_image the same capture from any device image of the recorder's extent (B8G8R8A8, 4-B
+ *                              aligned, rows pitch_bytes apart), ordered on hip_stream (NULL = the null stream); the
+ *                              image must stay unchanged until the slot's wait returns. TRI_E_INVALID: a null image,
+ *                              a pitch below 4 * width or not a multiple of 4.
+ *   tri_recorder_wait_ex       waits for the slot and returns its product in pinned memory, valid until the release:
+ *                              a JPEG recorder's stream, SOI to EOI, and its size (only the stream's own bytes,
+ *                              rounded up to 256, cross the bus); a YUV444 recorder's planes with bytes = 3 w h.
+ *   tri_recorder_wait          on a JPEG recorder is TRI_E_STATE.
+ * tri_jpeg_header writes the stream's bytes before the first entropy-coded byte (SOI .. SOS; they depend only on the
+ * extent, 1..65535 each, and the parameters) into `out`; tri_jpeg_max_bytes is the size no stream of that extent
+ * and those parameters exceeds (0 with an error recorded for bad arguments). Both are host only and need no device. */
+#define TRI_RECORD_YUV444 0u
+#define TRI_RECORD_JPEG420 1u
+typedef struct tri_record_params {
+    uint32_t format;       /* TRI_RECORD_* */
+    uint32_t quality;      /* JPEG: 1..100 */
+    uint32_t restart_mcus; /* JPEG: 1..65535 MCUs per restart interval, 0 = default */
+    uint32_t flags;        /* 0 */
+} tri_record_params;
+int tri_recorder_create_ex(int32_t device, uint32_t width, uint32_t height, uint32_t slots,
+                           const tri_record_params* params, tri_recorder** out);
+int tri_recorder_capture_image(tri_recorder* recorder, uint32_t slot, const void* device_bgra, uint32_t pitch_bytes,
+                               void* hip_stream);
+int tri_recorder_wait_ex(tri_recorder* recorder, uint32_t slot, const uint8_t** data, uint64_t* bytes);
+int tri_jpeg_header(uint32_t width, uint32_t height, const tri_record_params* params, uint8_t* out, uint32_t capacity,
+                    uint32_t* bytes);
+uint64_t tri_jpeg_max_bytes(uint32_t width, uint32_t height, const tri_record_params* params);
+
 /* ---- frame tensors for AI consumers (Renderer::SetReadbackEnabled / ResolvePendingReadback /
  * TryAcquireRenderedFrame, Renderer.cpp:984-995, :1111-1389) ----
  * The reference reads the primary viewport back and builds the frame generator's input on the host; here the
@@ -1338,6 +1378,7 @@ static_assert(sizeof(tri_text_quad) == 48, "tri_text_quad layout");
 static_assert(sizeof(tri_pick_result) == 16, "tri_pick_result layout");
 static_assert(sizeof(tri_outline) == 40, "tri_outline layout");
 static_assert(sizeof(tri_motion_history) == 144, "tri_motion_history layout");
+static_assert(sizeof(tri_record_params) == 16, "tri_record_params layout");
 static_assert(sizeof(tri_reproject_params) == 16, "tri_reproject_params layout");
 static_assert(sizeof(tri_taa_params) == 16, "tri_taa_params layout");
 static_assert(sizeof(tri_upscale_params) == 16, "tri_upscale_params layout");
