@@ -22,7 +22,7 @@
 // the sanitizers; the unit is built with -ffp-contract=off like the rest of the library, so a float32 restatement gives
 // the same bytes.
 #define TRI_KERNEL_TU 1
-#include "raster_launch.h"
+#include "temporal_device.h"
 
 #include "history_math.h"
 
@@ -30,15 +30,8 @@ namespace {
 
 constexpr uint32_t kReprojectMaxBlocks = 2048;  // a grid-stride loop over the rest: 8 workgroups on each of 256 CUs
 
-struct Rows {
-    float r[16];
-};
-
-__device__ __forceinline__ Rows load_rows(TRI_G const float* table, uint32_t k) {
-    TRI_G const float4* t = reinterpret_cast<TRI_G const float4*>(table) + (size_t)k * 4;  // 64-B rows: 16-B aligned
-    const float4 a = t[0], b = t[1], c = t[2], d = t[3];
-    return Rows{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
-}
+using temporal::Rows;
+using temporal::load_rows;
 
 __device__ __forceinline__ history::Pixel pixel(const Rows& R, uint32_t x, uint32_t y, uint32_t id, float depth, uint32_t colour,
                                                 const history::Frame& f, const TriReprojectArgs& a) {

@@ -17,38 +17,14 @@
 // sanitizers; the unit is built with -ffp-contract=off like the rest of the library, so a float32 restatement gives the
 // same bytes.
 #define TRI_KERNEL_TU 1
-#include "raster_launch.h"
+#include "temporal_device.h"
 
 #include "taa_math.h"
 
 namespace {
 
-constexpr uint32_t kTileW = 64, kTileH = TRI_BLOCK / kTileW;
-static_assert(kTileW * kTileH == TRI_BLOCK, "a workgroup is one tile");
-
-struct Rows {
-    float r[16];
-};
-
-__device__ __forceinline__ Rows load_rows(TRI_G const float* table, uint32_t k) {
-    TRI_G const float4* t = reinterpret_cast<TRI_G const float4*>(table) + (size_t)k * 4;  // 64-B rows: 16-B aligned
-    const float4 a = t[0], b = t[1], c = t[2], d = t[3];
-    return Rows{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
-}
-
-// The accumulated history as taa::resolve_pixel indexes it: one 8-B load per texel.
-struct AccAt {
-    TRI_G const uint2* p;
-    __device__ __forceinline__ taa::Texel operator[](uint32_t i) const {
-        const uint2 v = p[i];
-        return taa::Texel{v.x, v.y};
-    }
-};
-
 __global__ __launch_bounds__(TRI_BLOCK) void k_taa_resolve(TriTaaArgs a) {
-    const uint32_t tiles_x = (a.W + kTileW - 1u) / kTileW;
-    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const uint32_t x = tx * kTileW + (threadIdx.x & (kTileW - 1u)), y = ty * kTileH + threadIdx.x / kTileW;
+    const auto [x, y] = temporal::tile_pixel(a.W);
     if (x >= a.W || y >= a.H) return;  // every index below lies inside the frame
     const uint32_t p = y * a.W + x;
     const uint32_t rid = a.ids[p];  // the rule compares and stores the id as it is
@@ -59,10 +35,9 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_taa_resolve(TriTaaArgs a) {
         const float depth = a.depth[p];
         const uint32_t id = min(rid, a.ndraws);  // an id beyond the table cannot come out of the id pass; clamped all the same
         const history::Frame f{a.W, a.H, a.sx, a.sy, a.hw, a.hh, 0.0f};
-        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);
-        // one draw (or the background) under the whole wave: one lookup, broadcast
-        const Rows R = __all(id == first) ? load_rows(a.table, first) : load_rows(a.table, id);
-        o = taa::resolve_pixel(R.r, x, y, rid, depth, a.colour, f, true, a.reject_id != 0u, a.alpha, a.prev_ids, AccAt{a.prev_acc});
+        const temporal::WaveId w = temporal::wave_id(id);
+        const temporal::Rows R = w.shared ? temporal::load_rows(a.table, w.first) : temporal::load_rows(a.table, id);
+        o = taa::resolve_pixel(R.r, x, y, rid, depth, a.colour, f, true, a.reject_id != 0u, a.alpha, a.prev_ids, temporal::AccAt{a.prev_acc});
     }
     a.next_acc[p] = make_uint2(o.acc.bg, o.acc.ra);
     a.next_ids[p] = rid;
@@ -73,9 +48,8 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_taa_resolve(TriTaaArgs a) {
 }  // namespace
 
 hipError_t tri_launch_taa_resolve(const TriTaaArgs& args, hipStream_t stream) {
-    // at most 2^31 pixels (history::check_extent): fewer than 2^31 tiles whatever the frame's shape
-    const uint64_t tiles = (uint64_t)((args.W + kTileW - 1u) / kTileW) * (uint64_t)((args.H + kTileH - 1u) / kTileH);
-    if (tiles == 0 || tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_taa_resolve<<<dim3((uint32_t)tiles), dim3(TRI_BLOCK), 0, stream>>>(args);
+    const uint32_t tiles = temporal::tile_count(args.W, args.H);
+    if (tiles == 0) return hipErrorInvalidValue;
+    k_taa_resolve<<<dim3(tiles), dim3(TRI_BLOCK), 0, stream>>>(args);
     return hipGetLastError();
 }

@@ -1,8 +1,9 @@
 // tri_ctx.h — the context, geometry and font objects behind the C-ABI handles, and the owning holders their members
 // are made of. Internal to the units that implement the entry points over a context (tri_raster_capi.hip: lifecycle,
 // frame and readback; tri_geometry.hip: geometry; tri_resources.hip: every other upload; tri_ids.hip: the entity-id
-// entry points; tri_motion.hip: the motion-vector entry points); the other units keep to the
-// accessors of capi_util.h.
+// entry points; tri_motion.hip: the motion-vector entry points) and to the objects that read a context's frame and keep
+// state of their own between frames (tri_temporal.h: their shared core; tri_history.hip, tri_taa.hip, tri_upscale.hip);
+// the other units keep to the accessors of capi_util.h.
 //
 // Ownership: a DevBuf, PinBuf, Event or Staged member frees what it holds when its object is deleted (with the
 // object's device current), so a new buffer needs no line in tri_destroy. Raw pointers in these structs are borrowed:
@@ -28,6 +29,9 @@ inline int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return tri_internal_fail(code, buf);
 }
+
+// Whether a 16-B vector access may start at p (the choice between a kernel's vector and scalar variants).
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Device memory: count elements of T. grow() frees and allocates (the contents are not kept).
 template <typename T>

@@ -4,67 +4,23 @@
 // every argument rule are in history_math.h (plain C++, checked on the CPU by host/tools/history_check.cpp). Every
 // argument check comes before the device is made current.
 //
-// Ordering: a pass runs on the stream of the context it reads, behind that context's tri_render. The object's event
-// `done` is recorded behind every pass and waited for by the next one, which may run on another context's stream (two
-// frames in flight are two contexts); the readers wait for it on the host.
+// The bookkeeping, the ordering between passes and the readers' wait are TemporalCore's (tri_temporal.h).
 #include "history_math.h"
-#include "tri_ctx.h"
+#include "tri_temporal.h"
 
-struct tri_history {
-    int device = 0;
+struct tri_history : TemporalCore {
     uint32_t W = 0, H = 0;
     DevBuf<uint32_t> colour[2], ids[2];
     DevBuf<float> depth[2];
     DevBuf<uint32_t> warped;
     DevBuf<uint8_t> mask;
-    history::Sets sets;
-    Event done;            // behind the last pass
-    bool has_output = false;  // a pass was enqueued: warped and mask hold (or will hold) an image
-    Event stamp[2];        // round a stamped pass
-    bool stamped = false;  // ... whose interval has not been collected yet
-    double acc_ms = 0.0;
-    uint64_t acc_passes = 0;
 };
 
 namespace {
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+constexpr char kPass[] = "tri_history_reproject";
 
 size_t pixels(const tri_history* h) { return (size_t)h->W * (size_t)h->H; }
-
-// Add a finished stamped pass to the sums. wait: block for it; otherwise leave it pending when it has not finished.
-int collect(tri_history* h, bool wait) {
-    if (!h->stamped) return TRI_OK;
-    if (wait) TRI_HIP_TRY(hipEventSynchronize(h->stamp[1].e));
-    else {
-        const hipError_t q = hipEventQuery(h->stamp[1].e);
-        if (q == hipErrorNotReady) return TRI_OK;
-        TRI_HIP_TRY(q);
-    }
-    float ms = 0.0f;
-    TRI_HIP_TRY(hipEventElapsedTime(&ms, h->stamp[0].e, h->stamp[1].e));
-    h->acc_ms += ms;
-    h->acc_passes += 1;
-    h->stamped = false;
-    return TRI_OK;
-}
-
-int reader_ready(tri_history* h, const char* who) {
-    if (!h->has_output) return fail(TRI_E_STATE, "%s: no pass has run (tri_history_reproject)", who);
-    TRI_HIP_TRY(hipSetDevice(h->device));
-    TRI_HIP_TRY(hipEventSynchronize(h->done.e));
-    return TRI_OK;
-}
-
-void fill_image(const tri_history* h, tri_image* out, void* p, uint32_t bytes_per_pixel, uint32_t format) {
-    out->device_ptr = p;
-    out->width = h->W;
-    out->height = h->H;
-    out->pitch_bytes = h->W * bytes_per_pixel;
-    out->format = format;
-    out->device = h->device;
-    out->reserved = 0;
-}
 
 }  // namespace
 
@@ -79,7 +35,6 @@ int tri_history_create(int32_t device, uint32_t width, uint32_t height, tri_hist
     if (const int rc = tri_resolve_device(device, "tri_history_create", &dev)) return rc;
     TRI_HIP_TRY(hipSetDevice(dev));
     tri_history* h = new tri_history;
-    h->device = dev;
     h->W = width;
     h->H = height;
     const size_t n = pixels(h);
@@ -91,7 +46,7 @@ int tri_history_create(int32_t device, uint32_t width, uint32_t height, tri_hist
     }
     if (!rc) rc = h->warped.grow(n);
     if (!rc) rc = h->mask.grow((n + 3) & ~(size_t)3);
-    if (!rc) rc = h->done.ensure(hipEventDisableTiming);
+    if (!rc) rc = h->init(dev);
     if (rc) {
         delete h;  // (the holders free what was allocated)
         return rc;
@@ -100,39 +55,16 @@ int tri_history_create(int32_t device, uint32_t width, uint32_t height, tri_hist
     return TRI_OK;
 }
 
-int tri_history_destroy(tri_history* h) {
-    if (!h) return TRI_OK;
-    (void)hipSetDevice(h->device);
-    // a pass still queued on a context's stream reads and writes the buffers: wait for it before they go
-    if (h->has_output) (void)hipEventSynchronize(h->done.e);
-    delete h;
-    return TRI_OK;
-}
+int tri_history_destroy(tri_history* h) { return temporal_destroy(h); }
 
 int tri_history_reproject(tri_history* h, tri_ctx* c, const tri_reproject_params* params) {
     if (!h || !c) return fail(TRI_E_INVALID, "tri_history_reproject: null argument");
     history::Msg m;
     if (const int rc = history::check_params(params, m)) return fail(rc, "tri_history_reproject: %s", m.text);
-    if (const int rc = history::check_context(h->device, h->W, h->H, c->device, (uint32_t)c->W, (uint32_t)c->H, m))
-        return fail(rc, "tri_history_reproject: %s", m.text);
-    if (c->y0 != 0 || c->y1 != c->H)
-        return fail(TRI_E_UNSUPPORTED, "tri_history_reproject: a row-band context (the fetch leaves the band)");
-    if (!c->motion_on) return fail(TRI_E_STATE, "tri_history_reproject: the context's motion output is off (tri_set_motion_output)");
-    if (!c->motion_rendered || c->motion_table.size() < 16 || !c->motion_stage.d.p)
-        return fail(TRI_E_STATE, "tri_history_reproject: no frame was rendered with the motion output on");
-    int rc = make_current(c);
-    if (rc) return rc;
-    if ((rc = collect(h, false))) return rc;
-    const bool stamp = c->timing && !h->stamped;
-    if (stamp)
-        for (int i = 0; i < 2; ++i)
-            if ((rc = h->stamp[i].ensure(hipEventDefault))) return rc;
-    // the object's previous pass may have run on another context's stream
-    if (h->has_output) TRI_HIP_TRY(hipStreamWaitEvent(c->stream, h->done.e, 0));
-
-    history::Sets next = h->sets;  // committed once the pass is enqueued
-    bool valid = false;
-    const uint32_t rd = next.begin((params->flags & TRI_HISTORY_REDO) != 0, &valid), wr = rd ^ 1u;
+    if (const int rc = h->check_source(c, h->W, h->H, kPass, "", "the fetch leaves the band")) return rc;
+    TemporalPass pass;
+    if (const int rc = h->begin(c, (params->flags & TRI_HISTORY_REDO) != 0, &pass)) return rc;
+    const uint32_t rd = pass.rd, wr = pass.wr;
     const history::Frame f = history::make_frame(h->W, h->H, params->depth_tolerance);
     TriReprojectArgs a{};
     a.colour = c->d_color;
@@ -156,30 +88,22 @@ int tri_history_reproject(tri_history* h, tri_ctx* c, const tri_reproject_params
     a.hw = f.hw;
     a.hh = f.hh;
     a.tolerance = f.tolerance;
-    a.has_prev = valid ? 1u : 0u;
+    a.has_prev = pass.valid ? 1u : 0u;
     // the object's images and the context's own come from hipMalloc; a caller's targets (tri_bind_output) may start anywhere
     const bool vec4 = aligned16(a.colour) && aligned16(a.ids) && aligned16(a.depth);
-    if (stamp) TRI_HIP_TRY(hipEventRecord(h->stamp[0].e, c->stream));
     TRI_HIP_TRY(tri_launch_reproject(a, vec4, c->stream));
-    if (stamp) {
-        TRI_HIP_TRY(hipEventRecord(h->stamp[1].e, c->stream));
-        h->stamped = true;
-    }
-    TRI_HIP_TRY(hipEventRecord(h->done.e, c->stream));
-    h->sets = next;
-    h->has_output = true;
-    return TRI_OK;
+    return h->end(c, pass, nullptr);
 }
 
 int tri_history_reset(tri_history* h) {
     if (!h) return fail(TRI_E_INVALID, "tri_history_reset: null history");
-    h->sets.reset();
+    h->reset();
     return TRI_OK;
 }
 
 int tri_history_read(tri_history* h, uint8_t* bgra8, uint8_t* mask) {
     if (!h) return fail(TRI_E_INVALID, "tri_history_read: null history");
-    if (const int rc = reader_ready(h, "tri_history_read")) return rc;
+    if (const int rc = h->reader_ready("tri_history_read", kPass)) return rc;
     if (bgra8) TRI_HIP_TRY(hipMemcpy(bgra8, h->warped.p, pixels(h) * 4, hipMemcpyDeviceToHost));
     if (mask) TRI_HIP_TRY(hipMemcpy(mask, h->mask.p, pixels(h), hipMemcpyDeviceToHost));
     return TRI_OK;
@@ -187,20 +111,15 @@ int tri_history_read(tri_history* h, uint8_t* bgra8, uint8_t* mask) {
 
 int tri_history_get_output(tri_history* h, tri_image* colour, tri_image* mask) {
     if (!h) return fail(TRI_E_INVALID, "tri_history_get_output: null history");
-    if (!h->has_output) return fail(TRI_E_STATE, "tri_history_get_output: no pass has run (tri_history_reproject)");
-    if (colour) fill_image(h, colour, h->warped.p, 4, TRI_FORMAT_B8G8R8A8_UNORM);
-    if (mask) fill_image(h, mask, h->mask.p, 1, TRI_FORMAT_R8_UINT);
+    if (!h->has_output) return h->no_pass("tri_history_get_output", kPass);
+    if (colour) h->fill_image(colour, h->warped.p, h->W, h->H, 4, TRI_FORMAT_B8G8R8A8_UNORM);
+    if (mask) h->fill_image(mask, h->mask.p, h->W, h->H, 1, TRI_FORMAT_R8_UINT);
     return TRI_OK;
 }
 
 int tri_history_get_timing(tri_history* h, double* ms, uint64_t* passes) {
     if (!h || !ms || !passes) return fail(TRI_E_INVALID, "tri_history_get_timing: null argument");
-    if (!h->has_output) return fail(TRI_E_STATE, "tri_history_get_timing: no pass has run (tri_history_reproject)");
-    TRI_HIP_TRY(hipSetDevice(h->device));
-    if (const int rc = collect(h, true)) return rc;
-    *ms = h->acc_ms;
-    *passes = h->acc_passes;
-    return TRI_OK;
+    return h->get_timing("tri_history_get_timing", kPass, ms, passes);
 }
 
 }  // extern "C"

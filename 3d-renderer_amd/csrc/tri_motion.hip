@@ -16,8 +16,6 @@ int reader_ready(tri_ctx* c, const char* who) {
     return tri_synchronize(c);
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 int tri_motion_release(tri_ctx* c) {

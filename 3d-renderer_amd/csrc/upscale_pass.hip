@@ -20,38 +20,14 @@
 // host/tools/upscale_check.cpp runs under the sanitizers; the unit is built with -ffp-contract=off like the rest of the
 // library, so a float32 restatement gives the same bytes.
 #define TRI_KERNEL_TU 1
-#include "raster_launch.h"
+#include "temporal_device.h"
 
 #include "upscale_math.h"
 
 namespace {
 
-constexpr uint32_t kTileW = 64, kTileH = TRI_BLOCK / kTileW;
-static_assert(kTileW * kTileH == TRI_BLOCK, "a workgroup is one tile");
-
-struct Rows {
-    float r[16];
-};
-
-__device__ __forceinline__ Rows load_rows(TRI_G const float* table, uint32_t k) {
-    TRI_G const float4* t = reinterpret_cast<TRI_G const float4*>(table) + (size_t)k * 4;  // 64-B rows: 16-B aligned
-    const float4 a = t[0], b = t[1], c = t[2], d = t[3];
-    return Rows{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w}};
-}
-
-// The accumulated history as upscale::resolve_pixel indexes it: one 8-B load per texel.
-struct AccAt {
-    TRI_G const uint2* p;
-    __device__ __forceinline__ taa::Texel operator[](uint32_t i) const {
-        const uint2 v = p[i];
-        return taa::Texel{v.x, v.y};
-    }
-};
-
 __global__ __launch_bounds__(TRI_BLOCK) void k_upscale_resolve(TriUpscaleArgs a) {
-    const uint32_t tiles_x = (a.Wo + kTileW - 1u) / kTileW;
-    const uint32_t ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-    const uint32_t X = tx * kTileW + (threadIdx.x & (kTileW - 1u)), Y = ty * kTileH + threadIdx.x / kTileW;
+    const auto [X, Y] = temporal::tile_pixel(a.Wo);
     if (X >= a.Wo || Y >= a.Ho) return;  // every output index below lies inside the output frame
     const upscale::Scale s{a.Wr, a.Hr, a.Wo, a.Ho, a.rx, a.ry, a.ox, a.oy};
     const upscale::Sample sm = upscale::sample(X, Y, s, a.jx, a.jy);  // xr < Wr, yr < Hr: clamped by the rule
@@ -64,11 +40,10 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_upscale_resolve(TriUpscaleArgs a)
         const float depth = a.depth[q];
         const uint32_t id = min(rid, a.ndraws);  // an id beyond the table cannot come out of the id pass; clamped all the same
         const history::Frame f{a.Wo, a.Ho, a.sx, a.sy, a.hw, a.hh, 0.0f};
-        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)id);
-        // one draw (or the background) under the whole wave: one lookup, broadcast
-        const Rows R = __all(id == first) ? load_rows(a.table, first) : load_rows(a.table, id);
+        const temporal::WaveId w = temporal::wave_id(id);
+        const temporal::Rows R = w.shared ? temporal::load_rows(a.table, w.first) : temporal::load_rows(a.table, id);
         o = upscale::resolve_pixel(R.r, X, Y, sm, rid, depth, a.colour, s, f, true, a.reject_id != 0u, a.alpha, a.prev_ids,
-                                   AccAt{a.prev_acc});
+                                   temporal::AccAt{a.prev_acc});
     }
     const uint32_t p = Y * a.Wo + X;
     a.next_acc[p] = make_uint2(o.acc.bg, o.acc.ra);
@@ -79,9 +54,8 @@ __global__ __launch_bounds__(TRI_BLOCK) void k_upscale_resolve(TriUpscaleArgs a)
 }  // namespace
 
 hipError_t tri_launch_upscale_resolve(const TriUpscaleArgs& args, hipStream_t stream) {
-    // at most 2^31 output pixels (history::check_extent): fewer than 2^31 tiles whatever the frame's shape
-    const uint64_t tiles = (uint64_t)((args.Wo + kTileW - 1u) / kTileW) * (uint64_t)((args.Ho + kTileH - 1u) / kTileH);
-    if (tiles == 0 || tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    k_upscale_resolve<<<dim3((uint32_t)tiles), dim3(TRI_BLOCK), 0, stream>>>(args);
+    const uint32_t tiles = temporal::tile_count(args.Wo, args.Ho);
+    if (tiles == 0) return hipErrorInvalidValue;
+    k_upscale_resolve<<<dim3(tiles), dim3(TRI_BLOCK), 0, stream>>>(args);
     return hipGetLastError();
 }

@@ -507,25 +507,27 @@ private:
     bool BeginUpscaleFrame(const ViewportContext& target, uint32_t viewportId, float jitter[2]);
     // behind the target's tri_render: the frame resolved over the viewport's full-size history
     bool UpscaleTarget(ViewportContext& target, uint32_t viewportId, bool redo);
-    void RedoUpscale(ViewportContext& target);  // FinishOldestFrame re-rendered the target's frame
-    void DropUpscale();                         // with the targets (DestroyViewportTargets)
-    Upscale* UpscaleOutput(uint32_t viewportId);  // fenced; null unless the latest frame was upscaled
     struct Taa;
     // before the target's tri_render: this frame's jitter of the viewport (false: the switch is off, no jitter)
     bool BeginTaaFrame(const ViewportContext& target, uint32_t viewportId, float jitter[2]);
     // behind the target's tri_render: the frame resolved over the viewport's history (redo: it was rendered again)
     bool ResolveTarget(ViewportContext& target, uint32_t viewportId, bool redo);
-    void RedoTaa(ViewportContext& target);      // FinishOldestFrame re-rendered the target's frame
-    void DropTaa();                             // with the targets (DestroyViewportTargets)
-    Taa* TaaOutput(uint32_t viewportId);        // fenced; null unless the latest frame was resolved
     // the presentation blit of a target: its viewport's resolved image while that frame was resolved, else its colour
     int PresentBlit(ViewportContext& target, uint32_t width, uint32_t height);
     struct Reprojection;
     // behind the target's tri_render: the viewport's history warped by this frame (redo: the frame was rendered again)
     bool ReprojectTarget(ViewportContext& target, uint32_t viewportId, bool redo);
-    void RedoReprojection(ViewportContext& target);  // FinishOldestFrame re-rendered the target's frame
-    void DropHistories();                            // with the targets (DestroyViewportTargets)
-    Reprojection* ReprojectionOutput(uint32_t viewportId);  // fenced; null unless the latest frame was reprojected
+    // What the three passes above share, over m_Reprojection, m_Taa or m_Upscale (Renderer.cpp):
+    // FinishOldestFrame re-rendered the target's frame: `pass` again as a redo when it was the object's last, else `reset`
+    template <typename Map, typename Reset>
+    void RedoTemporal(Map& records, ViewportContext& target, bool (Renderer::*pass)(ViewportContext&, uint32_t, bool),
+                      Reset reset, const char* what);
+    // fenced; the viewport's record, or null unless the latest frame went through its pass
+    template <typename Map>
+    typename Map::mapped_type* TemporalOutput(Map& records, uint32_t viewportId);
+    // the viewport's object while the target's frame is the one it resolved last, else null (PresentBlit)
+    template <typename Map>
+    auto ResolvedBy(Map& records, const ViewportContext& target) -> decltype(records.begin()->second.m_Object);
     const Camera* GetActiveCamera(const ViewportContext& context) const;
     bool PrepareViewport(ViewportContext& context);
     // One viewport pass: pre-pass / palette / UBO / draws, then tri_render (asynchronous); false on error.
@@ -624,38 +626,35 @@ private:
     };
     std::map<uint32_t, bool> m_MotionViewports;  // SetMotionVectorOutputEnabled, by viewport id
     std::map<uint32_t, MotionHistory> m_MotionHistory;
-    struct Reprojection {  // SetHistoryReprojectionEnabled, by viewport id
+    struct TemporalRecord {  // what a viewport's history reprojection, anti-aliasing and upscaling records share
         bool m_Enabled = false;
-        float m_DepthTolerance = 0.0f;
-        tri_history* m_History = nullptr;  // made at the viewport's first reprojected frame, again after a resize
-        uint32_t m_Width = 0, m_Height = 0;
         const ViewportContext* m_LastTarget = nullptr;  // the target whose frame the last pass read
+        uint32_t m_FrameIndex = 0;  // the jittered passes: the viewport's frames since the switch went on or the extent changed
+    };
+    struct Reprojection : TemporalRecord {  // SetHistoryReprojectionEnabled, by viewport id
+        float m_DepthTolerance = 0.0f;
+        tri_history* m_Object = nullptr;  // made at the viewport's first reprojected frame, again after a resize
+        uint32_t m_Width = 0, m_Height = 0;
         tri_image m_Colour{}, m_Mask{};
     };
     std::map<uint32_t, Reprojection> m_Reprojection;
-    struct Taa {  // SetTemporalAntiAliasingEnabled, by viewport id
-        bool m_Enabled = false;
+    struct Taa : TemporalRecord {  // SetTemporalAntiAliasingEnabled, by viewport id
         float m_Alpha = 0.1f;
         uint32_t m_Period = 8;
         bool m_RejectIds = true;
         tri_taa* m_Object = nullptr;  // made at the viewport's first resolved frame, again after a resize
         uint32_t m_ObjectWidth = 0, m_ObjectHeight = 0;
         uint32_t m_Width = 0, m_Height = 0;  // the extent m_FrameIndex counts frames of
-        uint32_t m_FrameIndex = 0;    // the viewport's frames since the switch went on or the last resize
-        const ViewportContext* m_LastTarget = nullptr;  // the target whose frame the last pass read
         tri_image m_Resolved{};
     };
     std::map<uint32_t, Taa> m_Taa;
-    struct Upscale {  // SetTemporalUpscalingEnabled, by viewport id
-        bool m_Enabled = false;
+    struct Upscale : TemporalRecord {  // SetTemporalUpscalingEnabled, by viewport id
         float m_Scale = 0.5f, m_Alpha = 0.1f;
         bool m_RejectIds = true;
         tri_upscale* m_Object = nullptr;  // made at the viewport's first upscaled frame, again after a resize or a scale change
         uint32_t m_RenderWidth = 0, m_RenderHeight = 0, m_OutWidth = 0, m_OutHeight = 0;  // the object's extents
-        uint32_t m_Width = 0, m_Height = 0;  // the render extent m_FrameIndex counts frames of
-        uint32_t m_FrameIndex = 0;           // the viewport's frames since the switch went on, the last resize or scale change
+        uint32_t m_Width = 0, m_Height = 0;  // the render extent m_FrameIndex counts frames of (a scale change changes it)
         float m_Jitter[2] = {0.0f, 0.0f};    // of the frame being rendered (BeginUpscaleFrame)
-        const ViewportContext* m_LastTarget = nullptr;  // the target whose frame the last pass read
         tri_image m_Resolved{};
     };
     std::map<uint32_t, Upscale> m_Upscale;

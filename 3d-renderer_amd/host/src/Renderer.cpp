@@ -29,6 +29,46 @@ constexpr size_t kInvalidMeshIndex = std::numeric_limits<size_t>::max();
 
 void LogError(const char* what, const char* detail) { std::fprintf(stderr, "[Trident] %s: %s\n", what, detail); }
 
+// The readers' byte order (QuerySwapchainFormatInfo): the device's BGRA as RGBA.
+void BgraToRgba(const std::vector<uint8_t>& bgra, std::vector<uint8_t>& rgba) {
+    rgba.resize(bgra.size());
+    for (size_t i = 0; i < bgra.size(); i += 4) {
+        rgba[i + 0] = bgra[i + 2];
+        rgba[i + 1] = bgra[i + 1];
+        rgba[i + 2] = bgra[i + 0];
+        rgba[i + 3] = bgra[i + 3];
+    }
+}
+
+// The objects of m_Reprojection, m_Taa or m_Upscale go with the targets: the new targets' first frames have no history.
+template <typename Map, typename Destroy>
+void DropObjects(Map& records, Destroy destroy) {
+    for (auto& it : records) {
+        destroy(it.second.m_Object);  // (waits for its last pass)
+        it.second.m_Object = nullptr;
+        it.second.m_LastTarget = nullptr;
+        it.second.m_FrameIndex = 0;
+    }
+}
+
+// A viewport's object for a target's extent (matches: the one there is was made for it): made at the first frame, and
+// again, with no history, after a resize; create(device, &object).
+template <typename Object, typename Destroy, typename Create>
+bool EnsureObject(Object*& object, bool matches, tri_ctx* ctx, Destroy destroy, Create create, const char* what) {
+    if (object && !matches) {
+        destroy(object);
+        object = nullptr;
+    }
+    if (object) return true;
+    tri_image img{};
+    if (tri_get_output(ctx, &img) != TRI_OK || create(img.device, &object) != TRI_OK) {
+        LogError(what, tri_last_error());
+        object = nullptr;
+        return false;
+    }
+    return true;
+}
+
 std::string DefaultDatasetDirectory() {  // current_path()/DatasetCapture (Renderer.cpp:551, :2508-2511)
     std::error_code ec;
     const std::filesystem::path cwd = std::filesystem::current_path(ec);
@@ -253,9 +293,9 @@ void Renderer::Init() {
 
 void Renderer::DestroyViewportTargets() {
     m_Pending.clear();  // (its targets go; tri_destroy / tri_group_destroy wait for their streams)
-    DropHistories();    // (each waits for its last pass; the new targets' first frames have no history)
-    DropTaa();          // (likewise)
-    DropUpscale();      // (likewise)
+    DropObjects(m_Reprojection, tri_history_destroy);
+    DropObjects(m_Taa, tri_taa_destroy);
+    DropObjects(m_Upscale, tri_upscale_destroy);
     tri_recorder_destroy(m_Recorder);  // (waits for its captures; the next recorded DrawFrame makes a new one)
     m_Recorder = nullptr;
     DropGrab();  // (likewise; the next captured DrawFrame makes a new one)
@@ -468,17 +508,17 @@ bool Renderer::SetDeviceCount(uint32_t count, const std::vector<int32_t>& device
         any = false;
         for (auto& it : m_Reprojection) any |= it.second.m_Enabled;
         if (any) LogError("SetDeviceCount", "multi-device viewports have no history reprojection: it was turned off");
-        DropHistories();
+        DropObjects(m_Reprojection, tri_history_destroy);
         m_Reprojection.clear();
         any = false;
         for (auto& it : m_Taa) any |= it.second.m_Enabled;
         if (any) LogError("SetDeviceCount", "multi-device viewports have no temporal anti-aliasing: it was turned off");
-        DropTaa();
+        DropObjects(m_Taa, tri_taa_destroy);
         m_Taa.clear();
         any = false;
         for (auto& it : m_Upscale) any |= it.second.m_Enabled;
         if (any) LogError("SetDeviceCount", "multi-device viewports have no temporal upscaling: it was turned off");
-        DropUpscale();
+        DropObjects(m_Upscale, tri_upscale_destroy);
         m_Upscale.clear();
     }
     DestroyViewportTargets();  // rebuilt by the next DrawFrame's PrepareViewport
@@ -1605,9 +1645,11 @@ void Renderer::FinishOldestFrame() {  // the frame fence (Renderer.cpp:744-772)
             rerendered = true;
         }
         if (rc != TRI_OK) LogError("frame fence", tri_last_error());
-        if (rc == TRI_OK && rerendered) RedoTaa(*vc);           // the passes behind the first render read an incomplete frame
-        if (rc == TRI_OK && rerendered) RedoUpscale(*vc);
-        if (rc == TRI_OK && rerendered) RedoReprojection(*vc);
+        if (rc == TRI_OK && rerendered) {  // the passes behind the first render read an incomplete frame
+            RedoTemporal(m_Taa, *vc, &Renderer::ResolveTarget, tri_taa_reset, "temporal anti-aliasing");
+            RedoTemporal(m_Upscale, *vc, &Renderer::UpscaleTarget, tri_upscale_reset, "temporal upscaling");
+            RedoTemporal(m_Reprojection, *vc, &Renderer::ReprojectTarget, tri_history_reset, "history reprojection");
+        }
         if (rc == TRI_OK) vc->m_HasImage = t.Output(&vc->m_Image) == TRI_OK;  // a re-render moves a group's buffer
         if (vc == p.m_Legacy && rc == TRI_OK) {
             m_PresentSource = vc->m_Ctx;
@@ -2427,7 +2469,7 @@ void Renderer::SetHistoryReprojectionEnabled(uint32_t viewportId, bool enabled, 
     }
     Reprojection& st = m_Reprojection[viewportId];
     // the first frame after the switch goes on has no history (frames rendered meanwhile were not stored)
-    if (enabled && !st.m_Enabled && st.m_History && tri_history_reset(st.m_History) != TRI_OK)
+    if (enabled && !st.m_Enabled && st.m_Object && tri_history_reset(st.m_Object) != TRI_OK)
         LogError("history reprojection", tri_last_error());
     if (!enabled) st.m_LastTarget = nullptr;  // the readers answer for reprojected frames only
     st.m_Enabled = enabled;
@@ -2439,12 +2481,40 @@ bool Renderer::IsHistoryReprojectionEnabled(uint32_t viewportId) const {
     return it != m_Reprojection.end() && it->second.m_Enabled;
 }
 
-void Renderer::DropHistories() {
-    for (auto& it : m_Reprojection) {
-        tri_history_destroy(it.second.m_History);  // (waits for its last pass)
-        it.second.m_History = nullptr;
-        it.second.m_LastTarget = nullptr;
+// ---- what the three temporal passes' records share (Renderer.h) ---------------------------------------------------------
+// The target's frame overflowed a queue and was rendered again. When its pass was the object's last, a redo pass reads
+// the same previous frame and stores the complete one. With several frames in flight a later frame has already been
+// built from the incomplete one: nothing can mend that frame, and the object is reset so that nothing builds on it.
+template <typename Map, typename Reset>
+void Renderer::RedoTemporal(Map& records, ViewportContext& vc, bool (Renderer::*pass)(ViewportContext&, uint32_t, bool),
+                            Reset reset, const char* what) {
+    auto it = records.find(vc.m_Info.ViewportID);
+    if (it == records.end() || !it->second.m_Enabled || !it->second.m_Object || &vc == &m_LegacyTarget) return;
+    if (it->second.m_LastTarget == &vc) {
+        if ((this->*pass)(vc, vc.m_Info.ViewportID, true)) {
+            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError(what, tri_last_error());
+        }
+    } else if (reset(it->second.m_Object) != TRI_OK) {
+        LogError(what, tri_last_error());
     }
+}
+
+template <typename Map>
+typename Map::mapped_type* Renderer::TemporalOutput(Map& records, uint32_t viewportId) {
+    FinishFrame();
+    auto it = records.find(viewportId);
+    if (it == records.end() || !it->second.m_Object || !it->second.m_LastTarget) return nullptr;
+    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame did not go through the pass
+    return &it->second;
+}
+
+template <typename Map>
+auto Renderer::ResolvedBy(Map& records, const ViewportContext& vc) -> decltype(records.begin()->second.m_Object) {
+    auto it = records.find(vc.m_Info.ViewportID);
+    if (it != records.end() && it->second.m_Enabled && it->second.m_Object && it->second.m_LastTarget == &vc && vc.m_Ctx &&
+        &vc != &m_LegacyTarget)
+        return it->second.m_Object;
+    return nullptr;
 }
 
 // One tri_history per viewport, whichever of its targets renders the frame: ring targets are separate contexts and the
@@ -2455,25 +2525,17 @@ bool Renderer::ReprojectTarget(ViewportContext& vc, uint32_t viewportId, bool re
     Reprojection& st = it->second;
     st.m_LastTarget = nullptr;
     if (!vc.m_Ctx || !vc.m_MotionOutput) return false;
-    if (st.m_History && (st.m_Width != vc.m_Width || st.m_Height != vc.m_Height)) {  // a resize: a new object, no history
-        tri_history_destroy(st.m_History);
-        st.m_History = nullptr;
-    }
-    if (!st.m_History) {
-        tri_image img{};
-        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK || tri_history_create(img.device, vc.m_Width, vc.m_Height, &st.m_History) != TRI_OK) {
-            LogError("history reprojection", tri_last_error());
-            st.m_History = nullptr;
-            return false;
-        }
-        st.m_Width = vc.m_Width;
-        st.m_Height = vc.m_Height;
-    }
+    if (!EnsureObject(st.m_Object, st.m_Width == vc.m_Width && st.m_Height == vc.m_Height, vc.m_Ctx, tri_history_destroy,
+                      [&](int32_t device, tri_history** out) { return tri_history_create(device, vc.m_Width, vc.m_Height, out); },
+                      "history reprojection"))
+        return false;
+    st.m_Width = vc.m_Width;
+    st.m_Height = vc.m_Height;
     tri_reproject_params params{};
     params.depth_tolerance = st.m_DepthTolerance;
     params.flags = redo ? TRI_HISTORY_REDO : 0u;
-    if (tri_history_reproject(st.m_History, vc.m_Ctx, &params) != TRI_OK ||
-        tri_history_get_output(st.m_History, &st.m_Colour, &st.m_Mask) != TRI_OK) {
+    if (tri_history_reproject(st.m_Object, vc.m_Ctx, &params) != TRI_OK ||
+        tri_history_get_output(st.m_Object, &st.m_Colour, &st.m_Mask) != TRI_OK) {
         LogError("history reprojection", tri_last_error());
         return false;
     }
@@ -2481,36 +2543,12 @@ bool Renderer::ReprojectTarget(ViewportContext& vc, uint32_t viewportId, bool re
     return true;
 }
 
-// The target's frame overflowed a queue and was rendered again. When its pass was the history's last, a redo pass reads
-// the same previous frame and stores the complete one. With several frames in flight a later frame has already been
-// warped from the incomplete one: nothing can mend that frame, and the history is reset so that nothing builds on it.
-void Renderer::RedoReprojection(ViewportContext& vc) {
-    auto it = m_Reprojection.find(vc.m_Info.ViewportID);
-    if (it == m_Reprojection.end() || !it->second.m_Enabled || !it->second.m_History || &vc == &m_LegacyTarget) return;
-    Reprojection& st = it->second;
-    if (st.m_LastTarget == &vc) {
-        if (ReprojectTarget(vc, vc.m_Info.ViewportID, true)) {
-            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError("history reprojection", tri_last_error());
-        }
-    } else if (tri_history_reset(st.m_History) != TRI_OK) {
-        LogError("history reprojection", tri_last_error());
-    }
-}
-
-Renderer::Reprojection* Renderer::ReprojectionOutput(uint32_t viewportId) {
-    FinishFrame();
-    auto it = m_Reprojection.find(viewportId);
-    if (it == m_Reprojection.end() || !it->second.m_History || !it->second.m_LastTarget) return nullptr;
-    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame was not reprojected
-    return &it->second;
-}
-
 bool Renderer::ReadViewportReprojection(uint32_t viewportId, std::vector<uint8_t>& bgra, std::vector<uint8_t>& mask) {
-    Reprojection* st = ReprojectionOutput(viewportId);
+    Reprojection* st = TemporalOutput(m_Reprojection, viewportId);
     if (!st) return false;
     bgra.resize((size_t)st->m_Width * st->m_Height * 4);
     mask.resize((size_t)st->m_Width * st->m_Height);
-    if (tri_history_read(st->m_History, bgra.data(), mask.data()) != TRI_OK) {
+    if (tri_history_read(st->m_Object, bgra.data(), mask.data()) != TRI_OK) {
         LogError("history reprojection", tri_last_error());
         return false;
     }
@@ -2518,12 +2556,12 @@ bool Renderer::ReadViewportReprojection(uint32_t viewportId, std::vector<uint8_t
 }
 
 void* Renderer::GetViewportReprojectedTexture(uint32_t viewportId) {
-    Reprojection* st = ReprojectionOutput(viewportId);
+    Reprojection* st = TemporalOutput(m_Reprojection, viewportId);
     return st ? &st->m_Colour : nullptr;
 }
 
 void* Renderer::GetViewportDisocclusionTexture(uint32_t viewportId) {
-    Reprojection* st = ReprojectionOutput(viewportId);
+    Reprojection* st = TemporalOutput(m_Reprojection, viewportId);
     return st ? &st->m_Mask : nullptr;
 }
 
@@ -2562,15 +2600,6 @@ bool Renderer::IsTemporalAntiAliasingEnabled(uint32_t viewportId) const {
     return it != m_Taa.end() && it->second.m_Enabled;
 }
 
-void Renderer::DropTaa() {
-    for (auto& it : m_Taa) {
-        tri_taa_destroy(it.second.m_Object);  // (waits for its last pass)
-        it.second.m_Object = nullptr;
-        it.second.m_LastTarget = nullptr;
-        it.second.m_FrameIndex = 0;
-    }
-}
-
 bool Renderer::BeginTaaFrame(const ViewportContext& vc, uint32_t viewportId, float jitter[2]) {
     auto it = m_Taa.find(viewportId);
     if (it == m_Taa.end() || !it->second.m_Enabled || !vc.m_Ctx) return false;
@@ -2595,20 +2624,12 @@ bool Renderer::ResolveTarget(ViewportContext& vc, uint32_t viewportId, bool redo
     Taa& st = it->second;
     st.m_LastTarget = nullptr;
     if (!vc.m_Ctx || !vc.m_MotionOutput) return false;
-    if (st.m_Object && (st.m_ObjectWidth != vc.m_Width || st.m_ObjectHeight != vc.m_Height)) {  // a resize: a new object, no history
-        tri_taa_destroy(st.m_Object);
-        st.m_Object = nullptr;
-    }
-    if (!st.m_Object) {
-        tri_image img{};
-        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK || tri_taa_create(img.device, vc.m_Width, vc.m_Height, &st.m_Object) != TRI_OK) {
-            LogError("temporal anti-aliasing", tri_last_error());
-            st.m_Object = nullptr;
-            return false;
-        }
-        st.m_ObjectWidth = vc.m_Width;
-        st.m_ObjectHeight = vc.m_Height;
-    }
+    if (!EnsureObject(st.m_Object, st.m_ObjectWidth == vc.m_Width && st.m_ObjectHeight == vc.m_Height, vc.m_Ctx, tri_taa_destroy,
+                      [&](int32_t device, tri_taa** out) { return tri_taa_create(device, vc.m_Width, vc.m_Height, out); },
+                      "temporal anti-aliasing"))
+        return false;
+    st.m_ObjectWidth = vc.m_Width;
+    st.m_ObjectHeight = vc.m_Height;
     tri_taa_params params{};
     params.alpha = st.m_Alpha;
     params.flags = (redo ? TRI_TAA_REDO : 0u) | (st.m_RejectIds ? TRI_TAA_REJECT_ID : 0u);
@@ -2621,30 +2642,9 @@ bool Renderer::ResolveTarget(ViewportContext& vc, uint32_t viewportId, bool redo
     return true;
 }
 
-// As RedoReprojection: a redo pass when the target's pass was the object's last, else (a later frame has already been
-// accumulated over the incomplete one) a reset.
-void Renderer::RedoTaa(ViewportContext& vc) {
-    auto it = m_Taa.find(vc.m_Info.ViewportID);
-    if (it == m_Taa.end() || !it->second.m_Enabled || !it->second.m_Object || &vc == &m_LegacyTarget) return;
-    Taa& st = it->second;
-    if (st.m_LastTarget == &vc) {
-        if (ResolveTarget(vc, vc.m_Info.ViewportID, true)) {
-            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError("temporal anti-aliasing", tri_last_error());
-        }
-    } else if (tri_taa_reset(st.m_Object) != TRI_OK) {
-        LogError("temporal anti-aliasing", tri_last_error());
-    }
-}
-
 int Renderer::PresentBlit(ViewportContext& vc, uint32_t width, uint32_t height) {
-    auto it = m_Taa.find(vc.m_Info.ViewportID);
-    if (it != m_Taa.end() && it->second.m_Enabled && it->second.m_Object && it->second.m_LastTarget == &vc && vc.m_Ctx &&
-        &vc != &m_LegacyTarget)
-        return tri_taa_blit_linear(it->second.m_Object, vc.m_Ctx, nullptr, width, height);
-    auto up = m_Upscale.find(vc.m_Info.ViewportID);
-    if (up != m_Upscale.end() && up->second.m_Enabled && up->second.m_Object && up->second.m_LastTarget == &vc && vc.m_Ctx &&
-        &vc != &m_LegacyTarget)
-        return tri_upscale_blit_linear(up->second.m_Object, vc.m_Ctx, nullptr, width, height);
+    if (tri_taa* taa = ResolvedBy(m_Taa, vc)) return tri_taa_blit_linear(taa, vc.m_Ctx, nullptr, width, height);
+    if (tri_upscale* up = ResolvedBy(m_Upscale, vc)) return tri_upscale_blit_linear(up, vc.m_Ctx, nullptr, width, height);
     return Target{vc.m_Ctx, vc.m_Group}.Blit(width, height);
 }
 
@@ -2711,15 +2711,6 @@ void Renderer::RenderExtent(const ViewportContext& vc, uint32_t& width, uint32_t
     height = ScaledExtent(height, it->second.m_Scale);
 }
 
-void Renderer::DropUpscale() {
-    for (auto& it : m_Upscale) {
-        tri_upscale_destroy(it.second.m_Object);  // (waits for its last pass)
-        it.second.m_Object = nullptr;
-        it.second.m_LastTarget = nullptr;
-        it.second.m_FrameIndex = 0;
-    }
-}
-
 bool Renderer::BeginUpscaleFrame(const ViewportContext& vc, uint32_t viewportId, float jitter[2]) {
     auto it = m_Upscale.find(viewportId);
     if (it == m_Upscale.end() || !it->second.m_Enabled || !vc.m_Ctx || &vc == &m_LegacyTarget) return false;
@@ -2752,23 +2743,15 @@ bool Renderer::UpscaleTarget(ViewportContext& vc, uint32_t viewportId, bool redo
     st.m_LastTarget = nullptr;
     if (!vc.m_Ctx || !vc.m_MotionOutput) return false;
     const uint32_t ow = (uint32_t)std::max(vc.m_Info.Size.x, 0.0f), oh = (uint32_t)std::max(vc.m_Info.Size.y, 0.0f);
-    if (st.m_Object && (st.m_RenderWidth != vc.m_Width || st.m_RenderHeight != vc.m_Height || st.m_OutWidth != ow || st.m_OutHeight != oh)) {
-        tri_upscale_destroy(st.m_Object);  // a resize or another scale: a new object, no history
-        st.m_Object = nullptr;
-    }
-    if (!st.m_Object) {
-        tri_image img{};
-        if (tri_get_output(vc.m_Ctx, &img) != TRI_OK ||
-            tri_upscale_create(img.device, vc.m_Width, vc.m_Height, ow, oh, &st.m_Object) != TRI_OK) {
-            LogError("temporal upscaling", tri_last_error());
-            st.m_Object = nullptr;
-            return false;
-        }
-        st.m_RenderWidth = vc.m_Width;
-        st.m_RenderHeight = vc.m_Height;
-        st.m_OutWidth = ow;
-        st.m_OutHeight = oh;
-    }
+    const bool matches = st.m_RenderWidth == vc.m_Width && st.m_RenderHeight == vc.m_Height && st.m_OutWidth == ow && st.m_OutHeight == oh;
+    if (!EnsureObject(st.m_Object, matches, vc.m_Ctx, tri_upscale_destroy,  // (another scale is another extent)
+                      [&](int32_t device, tri_upscale** out) { return tri_upscale_create(device, vc.m_Width, vc.m_Height, ow, oh, out); },
+                      "temporal upscaling"))
+        return false;
+    st.m_RenderWidth = vc.m_Width;
+    st.m_RenderHeight = vc.m_Height;
+    st.m_OutWidth = ow;
+    st.m_OutHeight = oh;
     tri_upscale_params params{};
     params.alpha = st.m_Alpha;
     params.jitter[0] = st.m_Jitter[0];
@@ -2783,50 +2766,22 @@ bool Renderer::UpscaleTarget(ViewportContext& vc, uint32_t viewportId, bool redo
     return true;
 }
 
-// As RedoTaa: a redo pass when the target's pass was the object's last, else a reset.
-void Renderer::RedoUpscale(ViewportContext& vc) {
-    auto it = m_Upscale.find(vc.m_Info.ViewportID);
-    if (it == m_Upscale.end() || !it->second.m_Enabled || !it->second.m_Object || &vc == &m_LegacyTarget) return;
-    Upscale& st = it->second;
-    if (st.m_LastTarget == &vc) {
-        if (UpscaleTarget(vc, vc.m_Info.ViewportID, true)) {
-            if (tri_synchronize(vc.m_Ctx) != TRI_OK) LogError("temporal upscaling", tri_last_error());
-        }
-    } else if (tri_upscale_reset(st.m_Object) != TRI_OK) {
-        LogError("temporal upscaling", tri_last_error());
-    }
-}
-
-Renderer::Upscale* Renderer::UpscaleOutput(uint32_t viewportId) {
-    FinishFrame();
-    auto it = m_Upscale.find(viewportId);
-    if (it == m_Upscale.end() || !it->second.m_Object || !it->second.m_LastTarget) return nullptr;
-    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame was not upscaled
-    return &it->second;
-}
-
 bool Renderer::ReadViewportUpscaledPixels(uint32_t viewportId, std::vector<uint8_t>& rgba, uint32_t* width, uint32_t* height) {
-    Upscale* st = UpscaleOutput(viewportId);
+    Upscale* st = TemporalOutput(m_Upscale, viewportId);
     if (!st) return false;
     std::vector<uint8_t> bgra((size_t)st->m_OutWidth * st->m_OutHeight * 4);
     if (tri_upscale_read(st->m_Object, bgra.data(), nullptr, nullptr) != TRI_OK) {
         LogError("temporal upscaling", tri_last_error());
         return false;
     }
-    rgba.resize(bgra.size());
-    for (size_t i = 0; i < bgra.size(); i += 4) {  // BGRA -> RGBA, as ReadViewportPixels
-        rgba[i + 0] = bgra[i + 2];
-        rgba[i + 1] = bgra[i + 1];
-        rgba[i + 2] = bgra[i + 0];
-        rgba[i + 3] = bgra[i + 3];
-    }
+    BgraToRgba(bgra, rgba);
     if (width) *width = st->m_OutWidth;
     if (height) *height = st->m_OutHeight;
     return true;
 }
 
 bool Renderer::ReadViewportUpscaleMask(uint32_t viewportId, std::vector<uint8_t>& mask) {
-    Upscale* st = UpscaleOutput(viewportId);
+    Upscale* st = TemporalOutput(m_Upscale, viewportId);
     if (!st) return false;
     mask.resize((size_t)st->m_OutWidth * st->m_OutHeight);
     if (tri_upscale_read(st->m_Object, nullptr, nullptr, mask.data()) != TRI_OK) {
@@ -2837,38 +2792,24 @@ bool Renderer::ReadViewportUpscaleMask(uint32_t viewportId, std::vector<uint8_t>
 }
 
 void* Renderer::GetViewportUpscaledTexture(uint32_t viewportId) {
-    Upscale* st = UpscaleOutput(viewportId);
+    Upscale* st = TemporalOutput(m_Upscale, viewportId);
     return st ? &st->m_Resolved : nullptr;
 }
 
-Renderer::Taa* Renderer::TaaOutput(uint32_t viewportId) {
-    FinishFrame();
-    auto it = m_Taa.find(viewportId);
-    if (it == m_Taa.end() || !it->second.m_Object || !it->second.m_LastTarget) return nullptr;
-    if (it->second.m_LastTarget != LatestTarget(viewportId)) return nullptr;  // the latest frame was not resolved
-    return &it->second;
-}
-
 bool Renderer::ReadViewportResolvedPixels(uint32_t viewportId, std::vector<uint8_t>& rgba) {
-    Taa* st = TaaOutput(viewportId);
+    Taa* st = TemporalOutput(m_Taa, viewportId);
     if (!st) return false;
     std::vector<uint8_t> bgra((size_t)st->m_ObjectWidth * st->m_ObjectHeight * 4);
     if (tri_taa_read(st->m_Object, bgra.data(), nullptr, nullptr) != TRI_OK) {
         LogError("temporal anti-aliasing", tri_last_error());
         return false;
     }
-    rgba.resize(bgra.size());
-    for (size_t i = 0; i < bgra.size(); i += 4) {  // BGRA -> RGBA, as ReadViewportPixels
-        rgba[i + 0] = bgra[i + 2];
-        rgba[i + 1] = bgra[i + 1];
-        rgba[i + 2] = bgra[i + 0];
-        rgba[i + 3] = bgra[i + 3];
-    }
+    BgraToRgba(bgra, rgba);
     return true;
 }
 
 bool Renderer::ReadViewportTaaMask(uint32_t viewportId, std::vector<uint8_t>& mask) {
-    Taa* st = TaaOutput(viewportId);
+    Taa* st = TemporalOutput(m_Taa, viewportId);
     if (!st) return false;
     mask.resize((size_t)st->m_ObjectWidth * st->m_ObjectHeight);
     if (tri_taa_read(st->m_Object, nullptr, nullptr, mask.data()) != TRI_OK) {
@@ -2879,7 +2820,7 @@ bool Renderer::ReadViewportTaaMask(uint32_t viewportId, std::vector<uint8_t>& ma
 }
 
 void* Renderer::GetViewportResolvedTexture(uint32_t viewportId) {
-    Taa* st = TaaOutput(viewportId);
+    Taa* st = TemporalOutput(m_Taa, viewportId);
     return st ? &st->m_Resolved : nullptr;
 }
 
@@ -2902,13 +2843,7 @@ bool Renderer::ReadViewportPixels(uint32_t viewportId, std::vector<uint8_t>& rgb
         LogError("readback", tri_last_error());
         return false;
     }
-    rgba.resize(bgra.size());
-    for (size_t i = 0; i < bgra.size(); i += 4) {  // QuerySwapchainFormatInfo: BGRA -> RGBA
-        rgba[i + 0] = bgra[i + 2];
-        rgba[i + 1] = bgra[i + 1];
-        rgba[i + 2] = bgra[i + 0];
-        rgba[i + 3] = bgra[i + 3];
-    }
+    BgraToRgba(bgra, rgba);
     if (depth) {
         depth->resize(dbits.size());
         std::memcpy(depth->data(), dbits.data(), dbits.size() * 4);
@@ -2927,13 +2862,7 @@ bool Renderer::ReadPresentPixels(std::vector<uint8_t>& rgba, uint32_t& width, ui
         LogError("present readback", tri_last_error());
         return false;
     }
-    rgba.resize(bgra.size());
-    for (size_t i = 0; i < bgra.size(); i += 4) {
-        rgba[i + 0] = bgra[i + 2];
-        rgba[i + 1] = bgra[i + 1];
-        rgba[i + 2] = bgra[i + 0];
-        rgba[i + 3] = bgra[i + 3];
-    }
+    BgraToRgba(bgra, rgba);
     width = m_PresentedWidth;
     height = m_PresentedHeight;
     return true;

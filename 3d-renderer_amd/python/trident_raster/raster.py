@@ -399,20 +399,15 @@ def motion_matrices(ubo, draws, history=None):
     return out
 
 
-class TriHistory:
-    """tri_history: the previous frame of one view (colour, ids, depth) outside any context, and the pass that warps it
-    by a rendered frame's motion."""
+class _TemporalObject:
+    """What TriHistory, TriTaa and TriUpscale share: the handle's lifetime, reset and timing. A subclass names its
+    destroy, reset and get_timing entry points and sets self._h."""
 
-    def __init__(self, width, height, device=-1):
-        lib = load_library()
-        h = C.c_void_p()
-        _check(lib.tri_history_create(device, width, height, C.byref(h)))
-        self._h = h
-        self.width, self.height = width, height
+    _destroy = _reset = _timing = None
 
     def close(self):
         if self._h:
-            _lib.tri_history_destroy(self._h)
+            getattr(_lib, self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -427,14 +422,34 @@ class TriHistory:
     def __exit__(self, *exc):
         self.close()
 
+    def reset(self):
+        _check(getattr(_lib, self._reset)(self._h))
+
+    def timing(self):
+        """get_timing: (summed ms of the stamped passes, their number)."""
+        ms, n = C.c_double(), C.c_uint64()
+        _check(getattr(_lib, self._timing)(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+
+class TriHistory(_TemporalObject):
+    """tri_history: the previous frame of one view (colour, ids, depth) outside any context, and the pass that warps it
+    by a rendered frame's motion."""
+
+    _destroy, _reset, _timing = "tri_history_destroy", "tri_history_reset", "tri_history_get_timing"
+
+    def __init__(self, width, height, device=-1):
+        lib = load_library()
+        h = C.c_void_p()
+        _check(lib.tri_history_create(device, width, height, C.byref(h)))
+        self._h = h
+        self.width, self.height = width, height
+
     def reproject(self, raster, depth_tolerance=0.0, redo=False, flags=None):
         """tri_history_reproject behind the raster's last render (asynchronous). flags overrides redo's bit (for the
         error cases)."""
         p = abi.TriReprojectParams(float(depth_tolerance), (abi.TRI_HISTORY_REDO if redo else 0) if flags is None else flags)
         _check(_lib.tri_history_reproject(self._h, raster._ctx, C.byref(p)))
-
-    def reset(self):
-        _check(_lib.tri_history_reset(self._h))
 
     def read(self):
         """tri_history_read: (warped colour uint8 [H, W, 4] B G R A, mask uint8 [H, W])."""
@@ -448,12 +463,6 @@ class TriHistory:
         col, mask = abi.TriImage(), abi.TriImage()
         _check(_lib.tri_history_get_output(self._h, C.byref(col), C.byref(mask)))
         return col, mask
-
-    def timing(self):
-        """tri_history_get_timing: (summed ms of the stamped passes, their number)."""
-        ms, n = C.c_double(), C.c_uint64()
-        _check(_lib.tri_history_get_timing(self._h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
 
 
 def taa_jitter(index, period):
@@ -474,9 +483,11 @@ def taa_jitter_projection(projection, jx, jy, width, height):
     return np.array(out[:], dtype=np.float32)
 
 
-class TriTaa:
+class TriTaa(_TemporalObject):
     """tri_taa: the accumulated colour of one view (16-bit) outside any context, and the pass that resolves a jittered
     frame over it."""
+
+    _destroy, _reset, _timing = "tri_taa_destroy", "tri_taa_reset", "tri_taa_get_timing"
 
     def __init__(self, width, height, device=-1):
         lib = load_library()
@@ -485,32 +496,12 @@ class TriTaa:
         self._h = h
         self.width, self.height = width, height
 
-    def close(self):
-        if self._h:
-            _lib.tri_taa_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def resolve(self, raster, alpha=0.1, reject_ids=True, redo=False, flags=None):
         """tri_taa_resolve behind the raster's last render (asynchronous). flags overrides the two switches' bits (for
         the error cases)."""
         bits = (abi.TRI_TAA_REDO if redo else 0) | (abi.TRI_TAA_REJECT_ID if reject_ids else 0)
         p = abi.TriTaaParams(float(alpha), bits if flags is None else flags)
         _check(_lib.tri_taa_resolve(self._h, raster._ctx, C.byref(p)))
-
-    def reset(self):
-        _check(_lib.tri_taa_reset(self._h))
 
     def read(self):
         """tri_taa_read: (resolved uint8 [H, W, 4] B G R A, accumulated uint16 [H, W, 4] B G R A, mask uint8 [H, W])."""
@@ -525,12 +516,6 @@ class TriTaa:
         col, acc, mask = abi.TriImage(), abi.TriImage(), abi.TriImage()
         _check(_lib.tri_taa_get_output(self._h, C.byref(col), C.byref(acc), C.byref(mask)))
         return col, acc, mask
-
-    def timing(self):
-        """tri_taa_get_timing: (summed ms of the stamped passes, their number)."""
-        ms, n = C.c_double(), C.c_uint64()
-        _check(_lib.tri_taa_get_timing(self._h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
 
     def blit(self, raster, width, height, dst_ptr=None):
         """tri_taa_blit_linear: the resolved image scaled to width x height into dst_ptr, or into the raster's present
@@ -547,9 +532,11 @@ def upscale_jitter_period(render_w, render_h, out_w, out_h):
     return n.value
 
 
-class TriUpscale:
+class TriUpscale(_TemporalObject):
     """tri_upscale: the accumulated colour of one view at an output extent (16-bit) outside any context, and the pass that
     resolves a jittered frame of the render extent over it."""
+
+    _destroy, _reset, _timing = "tri_upscale_destroy", "tri_upscale_reset", "tri_upscale_get_timing"
 
     def __init__(self, render_w, render_h, out_w, out_h, device=-1):
         lib = load_library()
@@ -559,32 +546,12 @@ class TriUpscale:
         self.render_width, self.render_height = render_w, render_h
         self.width, self.height = out_w, out_h
 
-    def close(self):
-        if self._h:
-            _lib.tri_upscale_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def resolve(self, raster, jitter=(0.0, 0.0), alpha=0.1, reject_ids=True, redo=False, flags=None):
         """tri_upscale_resolve behind the raster's last render (asynchronous). jitter: the one the frame was rendered
         under, in render pixels. flags overrides the two switches' bits (for the error cases)."""
         bits = (abi.TRI_UPSCALE_REDO if redo else 0) | (abi.TRI_UPSCALE_REJECT_ID if reject_ids else 0)
         p = abi.TriUpscaleParams(float(alpha), (C.c_float * 2)(float(jitter[0]), float(jitter[1])), bits if flags is None else flags)
         _check(_lib.tri_upscale_resolve(self._h, raster._ctx, C.byref(p)))
-
-    def reset(self):
-        _check(_lib.tri_upscale_reset(self._h))
 
     def read(self):
         """tri_upscale_read: (resolved uint8 [Ho, Wo, 4] B G R A, accumulated uint16 [Ho, Wo, 4], mask uint8 [Ho, Wo])."""
@@ -605,12 +572,6 @@ class TriUpscale:
         col, acc, mask = abi.TriImage(), abi.TriImage(), abi.TriImage()
         _check(_lib.tri_upscale_get_output(self._h, C.byref(col), C.byref(acc), C.byref(mask)))
         return col, acc, mask
-
-    def timing(self):
-        """tri_upscale_get_timing: (summed ms of the stamped passes, their number)."""
-        ms, n = C.c_double(), C.c_uint64()
-        _check(_lib.tri_upscale_get_timing(self._h, C.byref(ms), C.byref(n)))
-        return ms.value, n.value
 
     def blit(self, raster, width, height, dst_ptr=None):
         """tri_upscale_blit_linear: the resolved image scaled to width x height into dst_ptr, or into the raster's

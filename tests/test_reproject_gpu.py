@@ -324,19 +324,28 @@ def test_error_codes():
             call()
         return ei.value.code
 
+    def fails(call, rc, text):  # the code, and the whole of tri_last_error's text
+        assert code(call) == rc
+        assert lib.tri_last_error().decode() == text
+
     assert code(lambda: raster.TriHistory(0, 70)) == abi.TRI_E_INVALID
     assert code(lambda: raster.TriHistory(65536, 32769)) == abi.TRI_E_INVALID
     assert code(lambda: raster.TriHistory(16, 16, device=torch.cuda.device_count())) == abi.TRI_E_INVALID
     with raster.TriHistory(s.width, s.height) as h:
         assert code(h.read) == abi.TRI_E_STATE and code(h.images) == abi.TRI_E_STATE and code(h.timing) == abi.TRI_E_STATE
+        fails(h.read, abi.TRI_E_STATE, "tri_history_read: no pass has run (tri_history_reproject)")
+        fails(h.images, abi.TRI_E_STATE, "tri_history_get_output: no pass has run (tri_history_reproject)")
+        fails(h.timing, abi.TRI_E_STATE, "tri_history_get_timing: no pass has run (tri_history_reproject)")
+        off = "tri_history_reproject: the context's motion output is off (tri_set_motion_output)"
         with raster.TriRaster(s.width, s.height) as r:
             scenes.load_scene(r, s)
-            assert code(lambda: h.reproject(r)) == abi.TRI_E_STATE  # the motion output is off
+            fails(lambda: h.reproject(r), abi.TRI_E_STATE, off)  # the motion output is off
             r.set_id_output(True)
             r.render_frame()
-            assert code(lambda: h.reproject(r)) == abi.TRI_E_STATE
+            fails(lambda: h.reproject(r), abi.TRI_E_STATE, off)
             r.set_motion_output(True)
-            assert code(lambda: h.reproject(r)) == abi.TRI_E_STATE  # on, but no frame yet
+            fails(lambda: h.reproject(r), abi.TRI_E_STATE,  # on, but no frame yet
+                  "tri_history_reproject: no frame was rendered with the motion output on")
             r.render_frame()
             params = abi.TriReprojectParams(0.0, 0)
             assert lib.tri_history_reproject(None, r._ctx, C.byref(params)) == abi.TRI_E_INVALID
@@ -346,24 +355,27 @@ def test_error_codes():
                 assert code(lambda: h.reproject(r, tol)) == abi.TRI_E_INVALID, tol
             for flags in (2, 3, 0x80000000):
                 assert code(lambda: h.reproject(r, flags=flags)) == abi.TRI_E_INVALID, flags
-            assert code(h.read) == abi.TRI_E_STATE  # none of these ran a pass
+            fails(h.read, abi.TRI_E_STATE, "tri_history_read: no pass has run (tri_history_reproject)")  # none of these ran a pass
             h.reproject(r)
             _, m = h.read()
             assert (m == rr.NO_HISTORY).all()
             assert lib.tri_history_read(h._h, None, None) == abi.TRI_OK
             r.set_motion_output(False)
-            assert code(lambda: h.reproject(r)) == abi.TRI_E_STATE
+            fails(lambda: h.reproject(r), abi.TRI_E_STATE, off)
         for w, hh in ((s.width + 1, s.height), (s.height, s.width)):  # another extent
             with open_raster(id_ref.cubes_and_quad(w, hh)) as other:
                 other.render_frame()
-                assert code(lambda: h.reproject(other)) == abi.TRI_E_INVALID
+                fails(lambda: h.reproject(other), abi.TRI_E_INVALID,
+                      f"tri_history_reproject: the context is {w} x {hh}, the history {s.width} x {s.height}")
         with open_raster(s, band=(16, 48)) as band:  # a row band
             band.render_frame()
-            assert code(lambda: h.reproject(band)) == abi.TRI_E_UNSUPPORTED
+            fails(lambda: h.reproject(band), abi.TRI_E_UNSUPPORTED,
+                  "tri_history_reproject: a row-band context (the fetch leaves the band)")
         if torch.cuda.device_count() > 1:  # another device
             with open_raster(s, device=1) as far:
                 far.render_frame()
-                assert code(lambda: h.reproject(far)) == abi.TRI_E_INVALID
+                fails(lambda: h.reproject(far), abi.TRI_E_INVALID,
+                      "tri_history_reproject: the context is on device 1, the history on 0")
 
 
 def test_images_and_timing():

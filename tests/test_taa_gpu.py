@@ -341,21 +341,31 @@ def test_error_codes():
             call()
         return ei.value.code
 
+    def fails(call, rc, text):  # the code, and the whole of tri_last_error's text
+        assert code(call) == rc
+        assert lib.tri_last_error().decode() == text
+
     assert code(lambda: raster.TriTaa(0, 70)) == abi.TRI_E_INVALID
     assert code(lambda: raster.TriTaa(65536, 32769)) == abi.TRI_E_INVALID
     assert code(lambda: raster.TriTaa(16, 16, device=torch.cuda.device_count())) == abi.TRI_E_INVALID
     with raster.TriTaa(s.width, s.height) as t:
         assert code(t.read) == abi.TRI_E_STATE and code(t.images) == abi.TRI_E_STATE and code(t.timing) == abi.TRI_E_STATE
+        fails(t.read, abi.TRI_E_STATE, "tri_taa_read: no pass has run (tri_taa_resolve)")
+        fails(t.images, abi.TRI_E_STATE, "tri_taa_get_output: no pass has run (tri_taa_resolve)")
+        fails(t.timing, abi.TRI_E_STATE, "tri_taa_get_timing: no pass has run (tri_taa_resolve)")
+        off = "tri_taa_resolve: the context's motion output is off (tri_set_motion_output)"
         with raster.TriRaster(s.width, s.height) as r:
             scenes.load_scene(r, s)
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE  # the motion output is off
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE, off)  # the motion output is off
             r.set_id_output(True)
             r.render_frame()
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE, off)
             r.set_motion_output(True)
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE  # on, but no frame yet
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE,  # on, but no frame yet
+                  "tri_taa_resolve: no frame was rendered with the motion output on")
             r.render_frame()
-            assert code(lambda: t.blit(r, s.width, s.height)) == abi.TRI_E_STATE  # no pass has run
+            fails(lambda: t.blit(r, s.width, s.height), abi.TRI_E_STATE,  # no pass has run
+                  "tri_taa_blit_linear: no pass has run (tri_taa_resolve)")
             params = abi.TriTaaParams(0.1, 0)
             assert lib.tri_taa_resolve(None, r._ctx, C.byref(params)) == abi.TRI_E_INVALID
             assert lib.tri_taa_resolve(t._h, None, C.byref(params)) == abi.TRI_E_INVALID
@@ -364,7 +374,7 @@ def test_error_codes():
                 assert code(lambda: t.resolve(r, alpha)) == abi.TRI_E_INVALID, alpha
             for flags in (4, 7, 0x80000000):
                 assert code(lambda: t.resolve(r, flags=flags)) == abi.TRI_E_INVALID, flags
-            assert code(t.read) == abi.TRI_E_STATE  # none of these ran a pass
+            fails(t.read, abi.TRI_E_STATE, "tri_taa_read: no pass has run (tri_taa_resolve)")  # none of these ran a pass
             t.resolve(r)
             _, _, m = t.read()
             assert (m == tr.NO_HISTORY).all()
@@ -372,20 +382,22 @@ def test_error_codes():
             assert lib.tri_taa_get_output(t._h, None, None, None) == abi.TRI_OK
             assert code(lambda: t.blit(r, 0, 4)) == abi.TRI_E_INVALID
             r.set_motion_output(False)
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE, off)
         for w, hh in ((s.width + 1, s.height), (s.height, s.width)):  # another extent
             with open_raster(id_ref.cubes_and_quad(w, hh)) as other:
                 other.render_frame()
-                assert code(lambda: t.resolve(other)) == abi.TRI_E_INVALID
-                assert code(lambda: t.blit(other, 8, 8)) == abi.TRI_E_INVALID
+                extent = f"the context is {w} x {hh}, the history {s.width} x {s.height}"
+                fails(lambda: t.resolve(other), abi.TRI_E_INVALID, "tri_taa_resolve: " + extent)
+                fails(lambda: t.blit(other, 8, 8), abi.TRI_E_INVALID, "tri_taa_blit_linear: " + extent)
         with open_raster(s, band=(16, 48)) as band:  # a row band
             band.render_frame()
-            assert code(lambda: t.resolve(band)) == abi.TRI_E_UNSUPPORTED
-            assert code(lambda: t.blit(band, 8, 8)) == abi.TRI_E_STATE
+            fails(lambda: t.resolve(band), abi.TRI_E_UNSUPPORTED, "tri_taa_resolve: a row-band context (the fetch and the 3 x 3 windows leave the band)")
+            fails(lambda: t.blit(band, 8, 8), abi.TRI_E_STATE, "tri_taa_blit_linear: a row-band context has no whole frame")
         if torch.cuda.device_count() > 1:  # another device
             with open_raster(s, device=1) as far:
                 far.render_frame()
-                assert code(lambda: t.resolve(far)) == abi.TRI_E_INVALID
+                fails(lambda: t.resolve(far), abi.TRI_E_INVALID,
+                      "tri_taa_resolve: the context is on device 1, the history on 0")
 
 
 def test_images_blit_and_timing():

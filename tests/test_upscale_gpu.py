@@ -362,23 +362,33 @@ def test_error_codes():
             call()
         return ei.value.code
 
+    def fails(call, rc, text):  # the code, and the whole of tri_last_error's text
+        assert code(call) == rc
+        assert lib.tri_last_error().decode() == text
+
     for bad in [(0, 35, 100, 70), (50, 35, 49, 70), (50, 35, 100, 34), (50, 35, 151, 70), (50, 35, 100, 106),
                 (65536, 32768, 65536, 32769)]:
         assert code(lambda: raster.TriUpscale(*bad)) == abi.TRI_E_INVALID, bad
     assert code(lambda: raster.TriUpscale(16, 16, 32, 32, device=torch.cuda.device_count())) == abi.TRI_E_INVALID
     with raster.TriUpscale(s.width, s.height, *OUT2(s)) as t:
         assert code(t.read) == abi.TRI_E_STATE and code(t.images) == abi.TRI_E_STATE and code(t.timing) == abi.TRI_E_STATE
-        assert code(t.read_ids) == abi.TRI_E_STATE
+        fails(t.read, abi.TRI_E_STATE, "tri_upscale_read: no pass has run (tri_upscale_resolve)")
+        fails(t.images, abi.TRI_E_STATE, "tri_upscale_get_output: no pass has run (tri_upscale_resolve)")
+        fails(t.timing, abi.TRI_E_STATE, "tri_upscale_get_timing: no pass has run (tri_upscale_resolve)")
+        off = "tri_upscale_resolve: the context's motion output is off (tri_set_motion_output)"
+        fails(t.read_ids, abi.TRI_E_STATE, "tri_upscale_read_ids: no pass has run (tri_upscale_resolve)")
         with raster.TriRaster(s.width, s.height) as r:
             scenes.load_scene(r, s)
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE  # the motion output is off
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE, off)  # the motion output is off
             r.set_id_output(True)
             r.render_frame()
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE, off)
             r.set_motion_output(True)
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE  # on, but no frame yet
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE,  # on, but no frame yet
+                  "tri_upscale_resolve: no frame was rendered with the motion output on")
             r.render_frame()
-            assert code(lambda: t.blit(r, s.width, s.height)) == abi.TRI_E_STATE  # no pass has run
+            fails(lambda: t.blit(r, s.width, s.height), abi.TRI_E_STATE,  # no pass has run
+                  "tri_upscale_blit_linear: no pass has run (tri_upscale_resolve)")
             params = abi.TriUpscaleParams(0.1, (C.c_float * 2)(0.0, 0.0), 0)
             assert lib.tri_upscale_resolve(None, r._ctx, C.byref(params)) == abi.TRI_E_INVALID
             assert lib.tri_upscale_resolve(t._h, None, C.byref(params)) == abi.TRI_E_INVALID
@@ -390,7 +400,7 @@ def test_error_codes():
                 assert code(lambda: t.resolve(r, (0.0, j))) == abi.TRI_E_INVALID, j
             for flags in (4, 7, 0x80000000):
                 assert code(lambda: t.resolve(r, flags=flags)) == abi.TRI_E_INVALID, flags
-            assert code(t.read) == abi.TRI_E_STATE  # none of these ran a pass
+            fails(t.read, abi.TRI_E_STATE, "tri_upscale_read: no pass has run (tri_upscale_resolve)")  # none of these ran a pass
             t.resolve(r, (-0.5, 0.5))
             _, _, m = t.read()
             assert (m == ur.NO_HISTORY).all()
@@ -399,21 +409,23 @@ def test_error_codes():
             assert lib.tri_upscale_get_output(t._h, None, None, None) == abi.TRI_OK
             assert code(lambda: t.blit(r, 0, 4)) == abi.TRI_E_INVALID
             r.set_motion_output(False)
-            assert code(lambda: t.resolve(r)) == abi.TRI_E_STATE
+            fails(lambda: t.resolve(r), abi.TRI_E_STATE, off)
         # a context of another extent — the object's OUTPUT extent included
         for w, hh in ((s.width + 1, s.height), (s.height, s.width), OUT2(s)):
             with open_raster(id_ref.cubes_and_quad(w, hh)) as other:
                 other.render_frame()
-                assert code(lambda: t.resolve(other)) == abi.TRI_E_INVALID
-                assert code(lambda: t.blit(other, 8, 8)) == abi.TRI_E_INVALID
+                extent = f"the context is {w} x {hh}, the history {s.width} x {s.height} (the render extent)"
+                fails(lambda: t.resolve(other), abi.TRI_E_INVALID, "tri_upscale_resolve: " + extent)
+                fails(lambda: t.blit(other, 8, 8), abi.TRI_E_INVALID, "tri_upscale_blit_linear: " + extent)
         with open_raster(s, band=(16, 32)) as band:  # a row band
             band.render_frame()
-            assert code(lambda: t.resolve(band)) == abi.TRI_E_UNSUPPORTED
-            assert code(lambda: t.blit(band, 8, 8)) == abi.TRI_E_STATE
+            fails(lambda: t.resolve(band), abi.TRI_E_UNSUPPORTED, "tri_upscale_resolve: a row-band context (the samples and the 3 x 3 windows leave the band)")
+            fails(lambda: t.blit(band, 8, 8), abi.TRI_E_STATE, "tri_upscale_blit_linear: a row-band context has no whole frame")
         if torch.cuda.device_count() > 1:  # another device
             with open_raster(s, device=1) as far:
                 far.render_frame()
-                assert code(lambda: t.resolve(far)) == abi.TRI_E_INVALID
+                fails(lambda: t.resolve(far), abi.TRI_E_INVALID,
+                      "tri_upscale_resolve: the context is on device 1, the history on 0 (the render extent)")
 
 
 def test_images_blit_and_timing():
